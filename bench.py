@@ -8,9 +8,9 @@ i.e. completed Match* calls, per second).
                     FastCorrelativeScanMatcher2D::MatchFullSubmap of a 1000-point scan against
                     one 400x400 submap, depth 7, full-angle.  Stack and point cloud are
                     resident in HBM before the timed region; only the result returns.
-                    The other BASELINE configs (C1 real-time 2D single + batched, one GPU's
-                    share of C3, C4 real-time 3D, C5 fast 3D) are measured after the timed
-                    region and reported under config.other (skip with --no-other).
+                    With --full, the other BASELINE configs (C1 real-time 2D single + batched,
+                    one GPU's share of C3, C4 real-time 3D, C5 fast 3D) are measured after the
+                    timed region and reported under config.other (skip with --no-other).
   N > 1             BASELINE config[2] "C3": one scan against 64 N DISTINCT submaps (seeds
                     42 ..., N = 8: the 512 submaps of the config), submap-sharded with
                     sharding.shard_range, every rank searching its own block.  Per step the
@@ -20,11 +20,17 @@ i.e. completed Match* calls, per second).
                     RCCL over xGMI.  Per-GPU work is fixed as N grows: weak scaling.
   --config c1|c2|c3|c4|c5 selects the timed workload explicitly (single GPU for c1/c4/c5).
 
+A plain run sets up, calibrates the passes of a step, warms up, times `--steps` steps and prints
+the line (`--dump-outputs DIR`: the results of the last timed step as .npy files first).
+Everything else -- the parity gate in front of the timed region, the instrumented step and the
+roofline, the single-stream leg, the other configs, the CPU baselines, the details file -- runs
+with `--full` only.
+
 Timed regions run the library as a production caller does: WITHOUT the HIP-event brackets behind
 cmx_match_stats' *_ms fields (they are packets the chain of launches waits behind: 24 of a single
 search's 156 us).  The kernel / device times of the roofline blocks come from a few untimed
 "instrumented" passes of the same workload right behind each region, with the brackets switched
-on (set_timing, instrumented; the headline: one extra step after the K timed ones).
+on (set_timing, instrumented; the headline: one extra step after the K timed ones, --full).
 
 Prints ONE JSON line on rank 0.
 """
@@ -116,6 +122,15 @@ def parse_args():
                     help="file the FULL record goes to (per-config blocks, notes, nested "
                          "rooflines); the line on stdout is the compact headline (< 4 KB); "
                          "'' = do not write it")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: the parity gate, the instrumented step "
+                         "and the roofline, the single-stream leg, the other BASELINE configs, the "
+                         "CPU baselines and the details file (--no-parity, --no-other and "
+                         "--no-cpu-baseline select among them).  Without it a run sets up, warms "
+                         "up, times the steps and prints the line")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the timed path returned to its caller "
+                         "in the last step as DIR/<name>.npy (float32 / float64)")
     return ap.parse_args()
 
 
@@ -1516,10 +1531,11 @@ def headline(out, details_path):
     cfg = out["config"]
     line["config"] = {"workload": _clip(cfg["workload"], 150)}
     line["config"].update({k: cfg[k] for k in CONFIG_KEYS if k in cfg})
-    roof = out["roofline"]
-    line["roofline"] = {"kernel": _clip(roof.get("kernel", ""), 80)}
-    line["roofline"].update({k: roof[k] for k in ROOFLINE_KEYS if k in roof})
-    line["roofline"]["traffic_source"] = None if roof.get("traffic") is None else "profiles/"
+    if "roofline" in out:       # (--full)
+        roof = out["roofline"]
+        line["roofline"] = {"kernel": _clip(roof.get("kernel", ""), 80)}
+        line["roofline"].update({k: roof[k] for k in ROOFLINE_KEYS if k in roof})
+        line["roofline"]["traffic_source"] = None if roof.get("traffic") is None else "profiles/"
     if "cpu_baseline" in out:
         base = out["cpu_baseline"]
         line["cpu_baseline"] = {k: base[k] for k in CPU_KEYS if k in base}
@@ -1548,6 +1564,71 @@ def write_details(out, path):
     except OSError as e:
         sys.stderr.write(f"bench details not written ({e})\n")
         return None
+
+
+# --------------------------------------------------------------------------------------
+# --dump-outputs: the results of the last timed step, for comparing two builds output for output.
+# Pass k of a step searches input k mod the number of inputs (the scans of Fast2DWorkload; every
+# other workload repeats one input), so a step returns one result per input it reached.  Only the
+# inputs every step reaches whatever the calibrated pass count are written: the dump depends on
+# the arguments alone.
+# --------------------------------------------------------------------------------------
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def _pose_rows(poses):
+    """A result's poses as a float64 [n, d] array: 2D poses as they are (x, y, theta), 3D poses
+    (Rigid3d, or the result dicts of the fast 3D matcher; None = not found) as translation +
+    quaternion (w, x, y, z), zeros where nothing was found."""
+    if isinstance(poses, np.ndarray):
+        return np.asarray(poses, np.float64).reshape(len(poses), -1)
+    rows = np.zeros((len(poses), 7), np.float64)
+    for i, p in enumerate(poses):
+        if isinstance(p, dict):
+            p = p["pose_estimate"]
+        if p is not None:
+            rows[i, :3] = p.translation
+            rows[i, 3:] = p.rotation
+    return rows
+
+
+def output_arrays(kept, inputs):
+    """{name: array} of the results kept from the last timed step: found / score / pose with one
+    row per input (axis 0) and one column per match of a pass (axis 1); after a sharded step's
+    exchange also what every rank received, node_* (every submap's optional constraint) and
+    node_best (score, global submap; -1 where none)."""
+    keys = [k for k in range(inputs) if k in kept]
+    out = {"found": np.stack([np.asarray(kept[k][0][0], np.float32) for k in keys]),
+           "score": np.stack([np.asarray(kept[k][0][1]) for k in keys]),
+           "pose": np.stack([_pose_rows(kept[k][0][2]) for k in keys])}
+    if out["score"].dtype != np.float64:
+        out["score"] = out["score"].astype(np.float32)
+    gathered = [kept[k][1] for k in keys]
+    if gathered and gathered[0] is not None:
+        if isinstance(gathered[0], tuple):          # 2D: (found, scores, poses)
+            out["node_found"] = np.stack([np.asarray(g[0], np.float32) for g in gathered])
+            out["node_score"] = np.stack([np.asarray(g[1], np.float32) for g in gathered])
+            out["node_pose"] = np.stack([np.asarray(g[2], np.float64) for g in gathered])
+        else:                                       # 3D: rows of found, score, pose
+            out["node_rows"] = np.stack([np.asarray(g, np.float64) for g in gathered])
+        out["node_best"] = np.array([[-1.0 if v is None else float(v) for v in kept[k][2]]
+                                     for k in keys], np.float64)
+    return out
+
+
+def dump_outputs(directory, arrays):
+    """Writes `arrays` as DIR/<name>.npy.  Beyond DUMP_LIMIT_BYTES in all, every array keeps a
+    fixed, seeded sample of its columns (axis 1), whose indices go to DIR/<name>_columns.npy."""
+    os.makedirs(directory, exist_ok=True)
+    total = sum(a.nbytes for a in arrays.values())
+    for name, a in arrays.items():
+        if total > DUMP_LIMIT_BYTES and a.ndim > 1:
+            n = a.shape[1]
+            keep = max(1, int(n * DUMP_LIMIT_BYTES / total))
+            cols = np.sort(np.random.default_rng(0).choice(n, keep, replace=False))
+            a = a[:, cols]
+            np.save(os.path.join(directory, f"{name}_columns.npy"), cols.astype(np.float64))
+        np.save(os.path.join(directory, f"{name}.npy"), a)
 
 
 def main():
@@ -1588,20 +1669,33 @@ def main():
         from concurrent.futures import ThreadPoolExecutor
         pool = ThreadPoolExecutor(threads)
 
-    def run_passes(num_passes, acc):
+    # --dump-outputs: pass k searches input k mod `period`; every step reaches the first `inputs`
+    # of them (a step is at least `threads` passes, or exactly --passes-per-step)
+    period = len(getattr(workload, "clouds", [None]))
+    inputs = min(period, args.passes_per_step if args.passes_per_step > 0 else threads)
+
+    def run_passes(num_passes, acc, keep=None):
         """`num_passes` passes of the hot path (one step, or a warmup / calibration run); returns
-        the last result."""
+        the last result.  `keep`: a dict that receives, per input k < `inputs`, the result of a
+        pass that searched it (and what the exchange behind it left)."""
         last = None
 
         def add(result):
             for k in STAT_KEYS:
                 acc[k] += result[3].get(k, 0)
 
+        def kept(k, result):
+            if keep is not None and k % period < inputs:
+                keep[k % period] = (result, getattr(workload, "gathered", None),
+                                    getattr(workload, "best", None))
+
         if pool is None:
             for k in range(num_passes):
                 last = workload.search(k)
                 if exchange is not None:
                     exchange(last[0], last[1], last[2], torch_device)
+                if keep is not None:
+                    kept(k, last)
                 add(last)
         elif exchange is None:
             # Independent searches issued from T host threads, each looping over its share.
@@ -1617,6 +1711,8 @@ def main():
                 r = None
                 for j in range(n):
                     r = workload.search(first + j)
+                    if keep is not None:
+                        kept(first + j, r)
                     for k in STAT_KEYS:
                         mine[k] += r[3].get(k, 0)
                 return mine, r
@@ -1632,9 +1728,10 @@ def main():
             done = 0
             while done < num_passes:
                 n = min(threads, num_passes - done)
-                for r in [f.result() for f in [pool.submit(workload.search, done + j)
-                                               for j in range(n)]]:
+                for j, r in enumerate([f.result() for f in [pool.submit(workload.search, done + j)
+                                                            for j in range(n)]]):
                     exchange(r[0], r[1], r[2], torch_device)
+                    kept(done + j, r)
                     add(r)
                     last = r
                 done += n
@@ -1646,8 +1743,9 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
-    # ---- parity gate: this rank's device result against the reference, before any timing ----
-    parity = None if args.no_parity else parity_gate(workload)
+    # ---- parity gate (--full): this rank's device result against the reference, before any
+    # timing ----
+    parity = None if args.no_parity or not args.full else parity_gate(workload)
 
     # ---- passes per step: a step is one pass over a BATCH of searches, sized (untimed) so that
     # it lasts >= 30 ms; every rank uses the same number ------------------------------------
@@ -1700,24 +1798,29 @@ def main():
     gc.collect()
     gc.disable()        # see measure()
     acc = {k: 0.0 for k in STAT_KEYS}
+    kept = {} if args.dump_outputs else None
     t0 = time.perf_counter()
-    for _ in range(args.steps):
-        found, scores, poses, stats = run_passes(passes, acc)
+    for step in range(args.steps):
+        found, scores, poses, stats = run_passes(
+            passes, acc, kept if step == args.steps - 1 else None)
     fence()
     elapsed = time.perf_counter() - t0
     gc.enable()
     total_passes = passes * args.steps
-    # One more step, untimed, with the library's HIP-event brackets on: the kernel / device times
-    # of the roofline block (every rank runs it: a sharded pass contains collectives).
-    set_timing(True)
-    try:
-        acc_ms = {k: 0.0 for k in STAT_KEYS}
-        run_passes(passes, acc_ms)
-        fence()
-    finally:
-        set_timing(False)
-    for k in MS_KEYS:
-        acc[k] = acc_ms[k] * args.steps
+    if kept is not None and rank == 0:
+        dump_outputs(args.dump_outputs, output_arrays(kept, inputs))
+    if args.full:
+        # One more step, untimed, with the library's HIP-event brackets on: the kernel / device
+        # times of the roofline block (every rank runs it: a sharded pass contains collectives).
+        set_timing(True)
+        try:
+            acc_ms = {k: 0.0 for k in STAT_KEYS}
+            run_passes(passes, acc_ms)
+            fence()
+        finally:
+            set_timing(False)
+        for k in MS_KEYS:
+            acc[k] = acc_ms[k] * args.steps
 
     # MAX over ranks of the elapsed time; SUM of the work.
     cand_local = acc["candidates_scored"]
@@ -1747,7 +1850,6 @@ def main():
             "candidates_per_pass": cand_local / total_passes,
             "lowest_resolution_candidates_per_pass": acc["coarse_candidates"] / total_passes,
             "matches_per_s": matches_total / elapsed,
-            "device_ms_per_pass": acc["device_ms"] / total_passes,
             "timed_region_s": elapsed,
             "candidate_count": "every scored candidate at every depth, counted once where it is "
                                "scored (dive and tie re-scoring included); fast 2D from depth 5 on: "
@@ -1757,10 +1859,13 @@ def main():
         if name in ("c2", "c3") and args.depth >= 5:
             coarse = acc["coarse_candidates"] / total_passes
             config["candidates_summed_per_pass"] = cand_local / total_passes - coarse + coarse / 3.0
-        roof = workload.roofline(acc, total_passes, pmc)
-        roof["traffic_source"] = (None if roof.get("traffic") is None else
-                                  f"rocprofv3 --pmc passes of this command, {args.pmc_dir}/"
-                                  f"{args.pmc_tag}*_pmc_*.csv (not measured in this run)")
+        roof = {}
+        if args.full:       # (the instrumented step's kernel times)
+            config["device_ms_per_pass"] = acc["device_ms"] / total_passes
+            roof = workload.roofline(acc, total_passes, pmc)
+            roof["traffic_source"] = (None if roof.get("traffic") is None else
+                                      f"rocprofv3 --pmc passes of this command, {args.pmc_dir}/"
+                                      f"{args.pmc_tag}*_pmc_*.csv (not measured in this run)")
         out = {
             "metric": "candidate poses scored/sec",
             "value": cand_total / elapsed,
@@ -1778,14 +1883,15 @@ def main():
             "data": "synthetic",
             "constraints_per_s": matches_total / elapsed,
             "config": config,
-            "roofline": roof,
         }
+        if args.full:
+            out["roofline"] = roof
         if parity is not None:
             out["parity"] = parity
         summary = {name: {"ms": config["ms_per_pass"], "cand_per_s": out["value"],
                           "frac": roof.get("frac"), "bound": roof.get("bound"),
                           "parity": _parity_word(parity)}}
-        if world_size == 1 and not use_dist and not args.no_other and name == "c2":
+        if args.full and world_size == 1 and not use_dist and not args.no_other and name == "c2":
             # Single-stream latency of the headline workload, then every other BASELINE config.
             single = Fast2DWorkload(args, device, 0, 1, sharded=False)
             dt1, acc1, _ = measure(single, 200, 20, torch.cuda.synchronize)
@@ -1844,11 +1950,12 @@ def main():
                                   "parity": _parity_word(e.get("parity"))}
         # The headline's CPU baseline runs LAST (after every GPU leg: seconds of 32 busy host
         # threads right before a host-bound GPU leg distort it).  JSON key order is irrelevant.
-        if not args.no_cpu_baseline and world_size == 1 and name in ("c2", "c3"):   # rank 0, N = 1
+        cpu_leg = args.full and not args.no_cpu_baseline
+        if cpu_leg and world_size == 1 and name in ("c2", "c3"):   # rank 0, N = 1
             out["cpu_baseline"] = cpu_baseline(workload.cells0, workload.lim0, args.depth,
                                                workload.host_scans, args.min_score,
                                                args.cpu_seconds)
-        elif not args.no_cpu_baseline and world_size == 1 and not use_dist:
+        elif cpu_leg and world_size == 1 and not use_dist:
             leg = {"c1": cpu_baseline_c1, "c4": cpu_baseline_c4, "c5": cpu_baseline_c5}[name]
             try:
                 out["cpu_baseline"] = leg(workload, args.cpu_seconds)
@@ -1869,7 +1976,7 @@ def main():
         # drain it first so that the JSON line is the LAST thing on stdout.
         import ctypes
         ctypes.CDLL(None).fflush(None)
-        details = write_details(out, args.details)
+        details = write_details(out, args.details) if args.full else None
         sys.stdout.write(headline(out, details) + "\n")
         sys.stdout.flush()
 

@@ -2,6 +2,9 @@
 this checks what the driver depends on -- exactly `warmup + steps` matches (+ one untimed instrumented step) are issued, ONE JSON
 line comes out last, it carries every required key plus `roofline`, and the optional paths
 (`--concurrency`, the distributed branch on a 1-rank gloo group) keep the same accounting.
+The instrumented step, `roofline`, `parity`, the CPU baselines and the details file belong to
+`--full`; a plain run issues `warmup + steps` steps and nothing else, and `--dump-outputs` writes
+what the last timed step returned.
 """
 import contextlib
 import io
@@ -29,11 +32,11 @@ def stubbed_bench(monkeypatch):
     monkeypatch.syspath_prepend(root)
     import bench
 
-    def run(*argv):
+    def run(*argv, full=True):
         calls.clear()
         monkeypatch.setattr(sys, "argv", ["bench.py", "--no-cpu-baseline", "--no-other", "--grid",
                                           "120", "--passes-per-step", "1", "--concurrency", "1"]
-                            + list(argv))
+                            + (["--full"] if full else []) + list(argv))
         buf = io.StringIO()
         with contextlib.redirect_stdout(buf):
             bench.main()
@@ -88,7 +91,7 @@ def test_bench_cpu_baseline_leg(stubbed_bench, monkeypatch):
     oracle/_ref is built, otherwise the oracle port; a bounded sample."""
     import bench
     argv = ["bench.py", "--grid", "120", "--steps", "2", "--warmup", "1", "--cpu-seconds", "0.3",
-            "--no-other"]
+            "--no-other", "--full"]
     monkeypatch.setattr(sys, "argv", argv)
     buf = io.StringIO()
     with contextlib.redirect_stdout(buf):
@@ -114,7 +117,7 @@ def test_bench_two_ranks_gloo():
         procs.append(subprocess.Popen(
             [sys.executable, os.path.join(root, "tests", "bench_stub.py"), "--gpus", "2",
              "--steps", "5", "--warmup", "2", "--grid", "120", "--submaps", "3",
-             "--passes-per-step", "1"],
+             "--passes-per-step", "1", "--full"],
             env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True))
     outs = [p.communicate(timeout=300) for p in procs]
     assert all(p.returncode == 0 for p in procs), outs
@@ -149,7 +152,7 @@ def test_bench_two_ranks_gloo_c5():
         procs.append(subprocess.Popen(
             [sys.executable, os.path.join(root, "tests", "bench_stub.py"), "--config", "c5",
              "--gpus", "2", "--steps", "4", "--warmup", "1", "--submaps", "3",
-             "--passes-per-step", "1"],
+             "--passes-per-step", "1", "--full"],
             env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True))
     outs = [p.communicate(timeout=600) for p in procs]
     assert all(p.returncode == 0 for p in procs), outs
@@ -224,7 +227,8 @@ def test_line_is_small_and_the_details_go_to_a_file(stubbed_bench, tmp_path, mon
     details = tmp_path / "details.json"
     calls = []
     monkeypatch.setattr(sys, "argv", ["bench.py", "--no-cpu-baseline", "--no-other", "--grid", "120",
-                                      "--steps", "3", "--warmup", "1", "--details", str(details)])
+                                      "--steps", "3", "--warmup", "1", "--details", str(details),
+                                      "--full"])
     buf = io.StringIO()
     with contextlib.redirect_stdout(buf):
         bench.main()
@@ -316,3 +320,118 @@ def test_parity_gate_of_the_headline_workload_against_the_reference(monkeypatch)
     device[2][0, 0] += 0.05
     with pytest.raises(bench.ParityError):
         bench.parity_gate(w, device)
+
+
+def test_plain_run_times_the_steps_and_nothing_else(stubbed_bench, tmp_path, monkeypatch):
+    """Without --full: exactly `warmup + steps` steps are issued -- no parity gate, no
+    instrumented step, no other config, no CPU baseline -- no details file is written, and the line
+    carries the headline keys (no `roofline`, `parity`, `cpu_baseline`)."""
+    import bench
+
+    def must_not_run(*a, **k):
+        raise AssertionError("not part of a plain run")
+    for name in ("parity_gate", "other_configs", "cpu_baseline", "cpu_baseline_c1",
+                 "cpu_baseline_c4", "cpu_baseline_c5", "write_details"):
+        monkeypatch.setattr(bench, name, must_not_run)
+    timing = []
+    monkeypatch.setattr(bench, "set_timing", timing.append)
+    details = tmp_path / "details.json"
+    out, calls, num_lines = stubbed_bench("--steps", "7", "--warmup", "3", "--details",
+                                          str(details), full=False)
+    assert num_lines == 1 and calls == [1] * 10
+    assert True not in timing and not details.exists()
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "steps",
+                "warmup", "n_gpus", "config"):
+        assert key in out, key
+    for key in ("roofline", "parity", "cpu_baseline"):
+        assert key not in out, key
+    assert out["metric"] == "candidate poses scored/sec" and out["unit"] == "candidates/s"
+    assert out["higher_is_better"] is True and out["dtype"] == "u8/int32"
+    assert out["steps"] == 7 and out["warmup"] == 3 and out["details"] is None
+    assert abs(out["value"] * out["ms_per_step"] * 1e-3 * 7 / 7000.0 - 1) < 1e-4
+
+
+def _scan_keyed_matches(monkeypatch):
+    """The stub's batch call with a result that depends on the scan searched (its sum as the
+    score), and the workload bench.main() makes."""
+    import bench
+    from cartographer_amd import scan_matching as sm
+
+    def batch(matchers, cloud, min_score):
+        n = len(matchers)
+        return (np.ones(n, np.int32), np.full(n, cloud.sum(), np.float32),
+                np.tile(cloud[:1, :2].astype(np.float64), (n, 1))[:, [0, 1, 0]],
+                dict(candidates_scored=1000 * n, coarse_candidates=900 * n, num_scans=50 * n,
+                     nodes_expanded=30))
+    monkeypatch.setattr(sm, "match_full_submap_batch", batch)
+    made = {}
+    real = bench.make_workload
+    monkeypatch.setattr(bench, "make_workload", lambda *a: made.setdefault("w", real(*a)))
+    return made
+
+
+@pytest.mark.parametrize("extra,inputs", [(("--passes-per-step", "16", "--concurrency", "4"), 8),
+                                          (("--passes-per-step", "3"), 3),
+                                          (("--config", "c3", "--submaps", "2",
+                                            "--passes-per-step", "5"), 5)])
+def test_dump_outputs_writes_the_last_steps_results(stubbed_bench, tmp_path, monkeypatch, extra,
+                                                    inputs):
+    """--dump-outputs DIR: found / score / pose of every input the last timed step searched (pass k:
+    scan k mod --scans), float32 / float64, row k = scan k; a sharded step adds what the exchange
+    handed every rank.  The dump changes nothing about the run: still warmup + steps steps."""
+    made = _scan_keyed_matches(monkeypatch)
+    out_dir = tmp_path / "outputs"
+    out, calls, _ = stubbed_bench("--steps", "3", "--warmup", "1", "--dump-outputs", str(out_dir),
+                                  *extra, full=False)
+    w = made["w"]
+    files = sorted(p.name for p in out_dir.iterdir())
+    sharded = "c3" in extra
+    assert files == sorted(["found.npy", "score.npy", "pose.npy"] +
+                           (["node_best.npy", "node_found.npy", "node_pose.npy", "node_score.npy"]
+                            if sharded else []))
+    arrays = {f[:-4]: np.load(out_dir / f) for f in files}
+    assert all(a.dtype in (np.float32, np.float64) for a in arrays.values())
+    assert sum(a.nbytes for a in arrays.values()) <= 64 << 20
+    submaps = len(w.matchers)
+    assert arrays["found"].shape == (inputs, submaps) and np.all(arrays["found"] == 1)
+    assert arrays["pose"].shape == (inputs, submaps, 3)
+    want = np.array([[np.float32(w.host_scans[k].sum())] * submaps for k in range(inputs)])
+    np.testing.assert_array_equal(arrays["score"], want)
+    if sharded:
+        np.testing.assert_array_equal(arrays["node_score"], want)
+        assert arrays["node_best"].shape == (inputs, 2)
+
+
+def test_dump_outputs_depend_on_the_arguments_only(stubbed_bench, tmp_path, monkeypatch):
+    """With a calibrated pass count (timing-dependent) the dump holds the inputs every step reaches
+    whatever the count: two runs write the same arrays."""
+    _scan_keyed_matches(monkeypatch)
+    dumps = []
+    for run in range(2):
+        d = tmp_path / f"run{run}"
+        monkeypatch.setattr(sys, "argv", ["bench.py", "--grid", "120", "--steps", "2", "--warmup",
+                                          "1", "--concurrency", "2", "--dump-outputs", str(d)])
+        import bench
+        with contextlib.redirect_stdout(io.StringIO()):
+            bench.main()
+        dumps.append({p.name: np.load(p) for p in sorted(d.iterdir())})
+    assert dumps[0].keys() == dumps[1].keys() and dumps[0]["score.npy"].shape == (2, 1)
+    for name in dumps[0]:
+        np.testing.assert_array_equal(dumps[0][name], dumps[1][name])
+
+
+def test_dump_outputs_sample_beyond_the_size_limit(tmp_path, monkeypatch):
+    """Beyond the limit every array keeps the same seeded sample of its columns."""
+    import bench
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 4000)
+    arrays = {"score": np.arange(2000, dtype=np.float32).reshape(2, 1000),
+              "pose": np.arange(6000, dtype=np.float64).reshape(2, 1000, 3)}
+    for run in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / run), arrays)
+    written = {p.name: np.load(p) for p in (tmp_path / "a").iterdir()}
+    assert sum(a.nbytes for n, a in written.items() if "_columns" not in n) <= 4000
+    cols = written["score_columns.npy"].astype(np.int64)
+    np.testing.assert_array_equal(written["score.npy"], arrays["score"][:, cols])
+    np.testing.assert_array_equal(written["pose_columns.npy"], written["score_columns.npy"])
+    for name, a in written.items():
+        np.testing.assert_array_equal(a, np.load(tmp_path / "b" / name))

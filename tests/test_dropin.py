@@ -17,7 +17,10 @@ import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 DROPIN = os.path.join(ROOT, "examples", "dropin")
-BINARY = os.path.join(DROPIN, "_build", "constraint_builder_2d_mi355x")
+# (built from the reference tree by `make -C oracle dropin`, with the oracle's other builds of
+# reference sources: oracle/_ref travels to machines that have no reference tree)
+DROPIN_BUILD = os.path.join(ROOT, "oracle", "_ref", "dropin")
+BINARY = os.path.join(DROPIN_BUILD, "constraint_builder_2d_mi355x")
 REFERENCE = "/root/reference"
 
 
@@ -47,7 +50,7 @@ def _write_fixture(path, submaps, scan, rel):
 
 @pytest.mark.gpu
 def test_reference_constraint_builder_on_the_gpu(oracle, synth, tmp_path):
-    assert os.path.exists(BINARY), "examples/dropin/_build is prebuilt by __graft_entry__.build()"
+    assert os.path.exists(BINARY), "oracle/_ref/dropin is prebuilt by __graft_entry__.build()"
     truth_world = None
     submaps = []
     for seed, origin in ((42, (1.5, -2.25)), (43, (0.0, 0.0)), (42, (-3.0, 4.5))):
@@ -100,7 +103,7 @@ def test_reference_constraint_builder_on_the_gpu(oracle, synth, tmp_path):
 
 
 # ------------------------------------------------------------------------------------- 3D
-BINARY_3D = os.path.join(DROPIN, "_build", "constraint_builder_3d_mi355x")
+BINARY_3D = os.path.join(DROPIN_BUILD, "constraint_builder_3d_mi355x")
 
 
 @pytest.mark.skipif(not os.path.isdir(REFERENCE), reason="needs the reference tree to compile")
@@ -149,7 +152,7 @@ def test_reference_constraint_builder_3d_on_the_gpu(oracle, synth, tmp_path):
     with the oracle (constraint_builder_3d.cc:188-281): Match / MatchFullSubmap, then
     CeresScanMatcher3D::Match from that pose with the high- and low-resolution pairs."""
     import math
-    assert os.path.exists(BINARY_3D), "examples/dropin/_build is prebuilt by __graft_entry__.build()"
+    assert os.path.exists(BINARY_3D), "oracle/_ref/dropin is prebuilt by __graft_entry__.build()"
     hist = np.zeros(16, np.float32)
     submaps, world = [], None
     for seed in (31, 32, 31):
@@ -201,7 +204,7 @@ def test_reference_constraint_builder_3d_on_the_gpu(oracle, synth, tmp_path):
 
 
 # ------------------------------------------------------------------- batched C++ front, 2D
-BINARY_BATCHED = os.path.join(DROPIN, "_build", "constraint_builder_2d_batched_mi355x")
+BINARY_BATCHED = os.path.join(DROPIN_BUILD, "constraint_builder_2d_batched_mi355x")
 
 
 @pytest.mark.skipif(not os.path.isdir(REFERENCE), reason="needs the reference tree to compile")
@@ -255,7 +258,7 @@ def test_batched_front_gives_the_reference_builders_constraints(synth, tmp_path)
 
 
 # ------------------------------------------------------------------- batched C++ front, 3D
-BINARY_BATCHED_3D = os.path.join(DROPIN, "_build", "constraint_builder_3d_batched_mi355x")
+BINARY_BATCHED_3D = os.path.join(DROPIN_BUILD, "constraint_builder_3d_batched_mi355x")
 
 
 @pytest.mark.skipif(not os.path.isdir(REFERENCE), reason="needs the reference tree to compile")
@@ -305,8 +308,8 @@ def test_batched_front_3d_gives_the_reference_builders_constraints(synth, tmp_pa
 
 
 # ---- the real-time matchers against the reference's REAL class headers -------------------------
-RT_REFERENCE = os.path.join(DROPIN, "_build", "real_time_matchers_reference")
-RT_MI355X = os.path.join(DROPIN, "_build", "real_time_matchers_mi355x")
+RT_REFERENCE = os.path.join(DROPIN_BUILD, "real_time_matchers_reference")
+RT_MI355X = os.path.join(DROPIN_BUILD, "real_time_matchers_mi355x")
 RT_GOLDEN = os.path.join(ROOT, "tests", "golden", "real_time_matchers_reference.txt")
 
 
@@ -342,15 +345,15 @@ def test_real_time_matchers_on_the_gpu_print_the_references_numbers():
     holds (the binary exits non-zero otherwise) and every score and pose -- ScoreCandidates on a
     ProbabilityGrid and a TSDF2D built by the reference's own inserters, Match() on both, the
     seven 3D cases -- is bit-identical to what the reference's own sources print."""
-    assert os.path.exists(RT_MI355X), "examples/dropin/_build is prebuilt by __graft_entry__.build()"
+    assert os.path.exists(RT_MI355X), "oracle/_ref/dropin is prebuilt by __graft_entry__.build()"
     out = subprocess.run([RT_MI355X], check=True, capture_output=True, text=True,
                          timeout=300).stdout
     assert out.splitlines() == open(RT_GOLDEN).read().splitlines()
 
 
 # ---- the reference's LocalTrajectoryBuilder2D, unmodified, scan after scan ---------------------
-LTB_REFERENCE = os.path.join(DROPIN, "_build", "local_trajectory_builder_2d_reference")
-LTB_MI355X = os.path.join(DROPIN, "_build", "local_trajectory_builder_2d_mi355x")
+LTB_REFERENCE = os.path.join(DROPIN_BUILD, "local_trajectory_builder_2d_reference")
+LTB_MI355X = os.path.join(DROPIN_BUILD, "local_trajectory_builder_2d_mi355x")
 LTB_GOLDEN = os.path.join(ROOT, "tests", "golden", "local_trajectory_builder_2d_reference.txt")
 
 
@@ -402,7 +405,7 @@ def test_local_trajectory_builder_2d_builds_unmodified_and_the_golden_is_the_ref
         assert run.returncode != 0 and "no CPU fallback" in run.stderr
 
 
-LTB_RESIDENT = os.path.join(DROPIN, "_build", "local_trajectory_builder_2d_resident_mi355x")
+LTB_RESIDENT = os.path.join(DROPIN_BUILD, "local_trajectory_builder_2d_resident_mi355x")
 
 
 @pytest.mark.skipif(not os.path.isdir(REFERENCE), reason="needs the reference tree to compile")
@@ -438,7 +441,7 @@ def test_local_trajectory_builder_2d_on_the_gpu_follows_the_references_drive(bin
     ten results must agree to 1e-6, all of them to 5 mm, the same scans must be inserted into the
     same number of submaps, and the drive must stay as close to the truth as the reference's."""
     path = LTB_MI355X if binary == "adapters" else LTB_RESIDENT
-    assert os.path.exists(path), "examples/dropin/_build is prebuilt by __graft_entry__.build()"
+    assert os.path.exists(path), "oracle/_ref/dropin is prebuilt by __graft_entry__.build()"
     out = subprocess.run([path], check=True, capture_output=True, text=True, timeout=300).stdout
     got, got_submaps, got_worst = _drive(out)
     want, want_submaps, want_worst = _drive(open(LTB_GOLDEN).read())
@@ -454,8 +457,8 @@ def test_local_trajectory_builder_2d_on_the_gpu_follows_the_references_drive(bin
 
 
 # ---- the reference's LocalTrajectoryBuilder3D, unmodified, scan after scan ---------------------
-LTB3_REFERENCE = os.path.join(DROPIN, "_build", "local_trajectory_builder_3d_reference")
-LTB3_MI355X = os.path.join(DROPIN, "_build", "local_trajectory_builder_3d_mi355x")
+LTB3_REFERENCE = os.path.join(DROPIN_BUILD, "local_trajectory_builder_3d_reference")
+LTB3_MI355X = os.path.join(DROPIN_BUILD, "local_trajectory_builder_3d_mi355x")
 LTB3_GOLDEN = os.path.join(ROOT, "tests", "golden", "local_trajectory_builder_3d_reference.txt")
 
 
@@ -511,7 +514,7 @@ def test_local_trajectory_builder_3d_builds_unmodified_and_the_golden_is_the_ref
         assert run.returncode != 0 and "no CPU fallback" in run.stderr
 
 
-LTB3_RESIDENT = os.path.join(DROPIN, "_build", "local_trajectory_builder_3d_resident_mi355x")
+LTB3_RESIDENT = os.path.join(DROPIN_BUILD, "local_trajectory_builder_3d_resident_mi355x")
 
 
 @pytest.mark.gpu
@@ -524,7 +527,7 @@ def test_local_trajectory_builder_3d_on_the_gpu_follows_the_references_drive(bin
     to the reference-linked build's; what is REQUIRED is the closed-loop bound of the 2D test:
     the first ten poses to 1e-6, all of them to 5 mm, the same insertions, the same submaps to 1 %."""
     path = LTB3_MI355X if binary == "adapters" else LTB3_RESIDENT
-    assert os.path.exists(path), "examples/dropin/_build is prebuilt by __graft_entry__.build()"
+    assert os.path.exists(path), "oracle/_ref/dropin is prebuilt by __graft_entry__.build()"
     out = subprocess.run([path], check=True, capture_output=True, text=True, timeout=600).stdout
     got, got_submaps, got_worst = _drive_3d(out)
     want, want_submaps, want_worst = _drive_3d(open(LTB3_GOLDEN).read())

@@ -706,7 +706,8 @@ def test_bench_force_dist_on_one_gpu():
                MASTER_PORT="29561")
     out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--force-dist", "--gpus",
                           "1", "--steps", "2", "--warmup", "1", "--submaps", "2", "--no-other",
-                          "--no-cpu-baseline", "--passes-per-step", "2", "--details", ""],
+                          "--no-cpu-baseline", "--passes-per-step", "2", "--details", "",
+                          "--full"],
                          env=env, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]

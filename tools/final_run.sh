@@ -13,7 +13,7 @@ echo "== smoke"; timeout 300 python -c "import __graft_entry__ as g; g.smoke()" 
 echo "== profiles"; bash tools/profile_all.sh $TAG 2>&1 | tail -3
 cp gpurun_out/${TAG}*_kernel_stats.csv gpurun_out/${TAG}*_pmc_*.csv profiles/ 2>/dev/null
 echo "== default bench (as the driver runs it)"
-timeout 900 python bench.py --steps 20 --warmup 5 > $OUT/bench.json 2> $OUT/bench.err; echo "rc $?"; wc -c $OUT/bench.json; cat $OUT/bench.json; tail -n 3 $OUT/bench.err
+timeout 900 python bench.py --full --steps 20 --warmup 5 > $OUT/bench.json 2> $OUT/bench.err; echo "rc $?"; wc -c $OUT/bench.json; cat $OUT/bench.json; tail -n 3 $OUT/bench.err
 cp gpurun_out/bench_details.json $OUT/bench_details.json
 echo "== c1 1024 as the timed config"
-timeout 600 python bench.py --config c1 --matches 1024 --steps 20 --warmup 5 --details $OUT/bench_c1b1024_details.json 2>/dev/null | tee $OUT/bench_c1b1024.json | cut -c1-600
+timeout 600 python bench.py --full --config c1 --matches 1024 --steps 20 --warmup 5 --details $OUT/bench_c1b1024_details.json 2>/dev/null | tee $OUT/bench_c1b1024.json | cut -c1-600

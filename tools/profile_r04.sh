@@ -11,7 +11,7 @@ export PYTHONUNBUFFERED=1
 ( time timeout 1200 python -m pytest tests -m gpu -q -p no:cacheprovider ) > $OUT/pytest_gpu.txt 2>&1 < /dev/null
 grep -E "passed|failed|error" $OUT/pytest_gpu.txt | tail -3
 grep -E "^FAILED|^ERROR" $OUT/pytest_gpu.txt | head -20
-( time timeout 900 python bench.py ) > $OUT/bench_full.log 2>&1 < /dev/null
+( time timeout 900 python bench.py --full ) > $OUT/bench_full.log 2>&1 < /dev/null
 tail -1 $OUT/bench_full.log | cut -c1-600
 export PROFILE_TIMEOUT=150
 P="bash tools/profile_cmd.sh"

@@ -11,7 +11,7 @@ export PYTHONUNBUFFERED=1
 
 echo "== gpu tests ==";          ( timeout 900 python -m pytest tests -m gpu -q -p no:cacheprovider 2>&1 | tail -5 ) | tee "$OUT/pytest_gpu.txt"
 echo "== device vs oracle, random odd-shaped problems ==";  timeout 300 python tools/gpu_fuzz.py 150 1 2>&1 | tail -20 | tee "$OUT/gpu_fuzz.txt"
-echo "== bench (default) ==";    timeout 600 python bench.py 2> "$OUT/bench_default.err" | tail -1 | tee "$OUT/bench_default.json" | cut -c1-400
+echo "== bench (default) ==";    timeout 600 python bench.py --full 2> "$OUT/bench_default.err" | tail -1 | tee "$OUT/bench_default.json" | cut -c1-400
 echo "== C2: single stream, 8 Python threads, 8 native threads, C3 share =="
 timeout 200 python tools/c2_probe.py 2>&1 | grep "^\[" | tee "$OUT/c2_probe.txt"
 echo "== C2 front end: block timeline with wavefront 0's first chunk step by step (DESIGN 5.1) =="
