@@ -45,6 +45,17 @@ class Fast2DOptions(C.Structure):
                 ("branch_and_bound_depth", C.c_int32)]
 
 
+class TSDFInserterOptions2D(C.Structure):
+    """cmx_tsdf_inserter_options_2d = proto::TSDFRangeDataInserterOptions2D (+ the
+    NormalEstimationOptions2D it holds)."""
+    _fields_ = [("truncation_distance", C.c_double), ("maximum_weight", C.c_double),
+                ("update_free_space", C.c_int32), ("num_normal_samples", C.c_int32),
+                ("sample_radius", C.c_double), ("project_sdf_distance_to_scan_normal", C.c_int32),
+                ("update_weight_range_exponent", C.c_int32),
+                ("update_weight_angle_scan_normal_to_ray_kernel_bandwidth", C.c_double),
+                ("update_weight_distance_cell_to_hit_kernel_bandwidth", C.c_double)]
+
+
 class Fast3DOptions(C.Structure):
     _fields_ = [("branch_and_bound_depth", C.c_int32), ("full_resolution_depth", C.c_int32),
                 ("min_rotational_score", C.c_double), ("min_low_resolution_score", C.c_double),
@@ -147,6 +158,9 @@ EXPORTED_SYMBOLS = [
     "cmx_rt2d_match", "cmx_rt2d_match_tsdf", "cmx_grid2d_create", "cmx_grid2d_destroy",
     "cmx_grid2d_get_limits", "cmx_grid2d_download", "cmx_grid2d_crop", "cmx_grid2d_insert",
     "cmx_rt2d_match_grid",
+    "cmx_tsdf2d_create", "cmx_tsdf2d_destroy", "cmx_tsdf2d_get_limits", "cmx_tsdf2d_download",
+    "cmx_tsdf2d_insert", "cmx_tsdf2d_crop", "cmx_rt2d_match_tsdf_grid",
+    "cmx_fast2d_create_from_tsdf",
     "cmx_rt2d_match_grid_batch", "cmx_rt2d_match_grid_batch_resident",
     "cmx_grid3d_create", "cmx_grid3d_destroy", "cmx_grid3d_insert", "cmx_grid3d_info",
     "cmx_grid3d_download",
@@ -249,6 +263,18 @@ def lib():
                                                      C.c_void_p, P(C.c_void_p), C.c_void_p,
                                                      C.c_void_p, P(MatchStats)]
     L.cmx_fast2d_create_from_grid.argtypes = [P(Fast2DOptions), C.c_void_p, P(C.c_void_p)]
+    L.cmx_tsdf2d_create.argtypes = [P(Grid2DLimits), C.c_float, C.c_float, C.c_void_p, C.c_void_p,
+                                    C.c_int32, P(C.c_void_p)]
+    L.cmx_tsdf2d_destroy.argtypes = [C.c_void_p]
+    L.cmx_tsdf2d_destroy.restype = None
+    L.cmx_tsdf2d_get_limits.argtypes = [C.c_void_p, P(Grid2DLimits)]
+    L.cmx_tsdf2d_download.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    L.cmx_tsdf2d_insert.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
+                                    P(TSDFInserterOptions2D)]
+    L.cmx_tsdf2d_crop.argtypes = [C.c_void_p]
+    L.cmx_rt2d_match_tsdf_grid.argtypes = [P(RtOptions), C.c_void_p, P(Pose2d), C.c_void_p,
+                                           C.c_int32, P(C.c_double), P(Pose2d), P(MatchStats)]
+    L.cmx_fast2d_create_from_tsdf.argtypes = [P(Fast2DOptions), C.c_void_p, P(C.c_void_p)]
     L.cmx_fast2d_create.argtypes = [P(Fast2DOptions), P(Grid2DLimits), C.c_void_p, C.c_int32,
                                     P(C.c_void_p)]
     L.cmx_fast2d_destroy.argtypes = [C.c_void_p]

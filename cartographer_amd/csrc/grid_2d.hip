@@ -23,6 +23,7 @@
 #include <memory>
 #include <vector>
 
+#include "ray_mask_2d.h"
 #include "scan_matching_2d.h"
 
 struct cmx_grid2d {
@@ -38,7 +39,6 @@ struct cmx_grid2d {
 namespace cmx {
 namespace {
 
-constexpr int kSubpixelScale = 1000;                     // ..._inserter_2d.cc:33
 constexpr uint16_t kUpdateMarker = 1u << 15;
 
 // ---- odds tables (host; mapping/probability_values.{h,cc}) -------------------
@@ -112,51 +112,16 @@ __global__ void GridHitKernel(GridView g, const float* __restrict__ points, int 
   if (i < num_returns) Apply(g, fine.x / kSubpixelScale, fine.y / kSubpixelScale, hit_table, error);
 }
 
-__device__ __forceinline__ long long FloorDiv(long long a, long long b) {
-  return a >= 0 ? a / b : -((-a + b - 1) / b);
-}
-__device__ __forceinline__ long long CeilDiv(long long a, long long b) { return -FloorDiv(-a, b); }
-
 // Rays: one wavefront per ray from the origin to ends[i]; the cells RayToPixelMask returns
-// (ray_to_pixel_mask.cc:34-156), column by column: the ray enters pixel column `col` at
-// height y_in and leaves it at y_out (exact integers in half-sub-pixel units scaled by dx);
-// the column contributes the pixels between them, a corner touched exactly adding none.
+// (ray_to_pixel_mask.h).
 __global__ void __launch_bounds__(256)
 GridMissKernel(GridView g, float origin_x, float origin_y, const int2* __restrict__ ends,
                int num_rays, const uint16_t* __restrict__ miss_table, int* __restrict__ error) {
   const int lane = threadIdx.x & 63;
   const int ray = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (ray >= num_rays) return;
-  int2 begin = FineIndex(g, origin_x, origin_y);
-  int2 end = ends[ray];
-  if (begin.x > end.x) { const int2 t = begin; begin = end; end = t; }
-  const int scale = kSubpixelScale;
-  const int col0 = begin.x / scale, col1 = end.x / scale;
-  if (col0 == col1) {                                    // stays inside one pixel column
-    const int lo = min(begin.y, end.y) / scale, hi = max(begin.y, end.y) / scale;
-    for (int y = lo + lane; y <= hi; y += 64) Apply(g, col0, y, miss_table, error);
-    return;
-  }
-  const long long dx = static_cast<long long>(end.x) - begin.x;
-  const long long dy = static_cast<long long>(end.y) - begin.y;
-  const long long x2_begin = 2ll * begin.x + 1, x2_end = 2ll * end.x + 1;
-  const long long y2_begin = 2ll * begin.y + 1;
-  const long long pixel = 2ll * scale * dx;
-  for (int col = col0 + lane; col <= col1; col += 64) {
-    const long long left = max(2ll * scale * col, x2_begin);
-    const long long right = min(2ll * scale * (col + 1), x2_end);
-    const long long y_in = y2_begin * dx + (left - x2_begin) * dy;
-    const long long y_out = y2_begin * dx + (right - x2_begin) * dy;
-    long long first, last;
-    if (dy > 0) {
-      first = FloorDiv(y_in, pixel);
-      last = CeilDiv(y_out, pixel) - 1;
-    } else {
-      last = CeilDiv(y_in, pixel) - 1;
-      first = FloorDiv(y_out, pixel);
-    }
-    for (long long y = first; y <= last; ++y) Apply(g, col, static_cast<int>(y), miss_table, error);
-  }
+  ForEachRayPixel(FineIndex(g, origin_x, origin_y), ends[ray], lane,
+                  [&](int x, int y) { Apply(g, x, y, miss_table, error); });
 }
 
 // Grid2D::FinishUpdate (grid_2d.cc:118-125) over the whole grid.
@@ -414,6 +379,18 @@ extern "C" cmx_status cmx_grid2d_insert(cmx_grid2d* grid, const float* origin_xy
 }
 
 namespace cmx {
+// GrowLimits and ComputeCroppedLimits of the TSDF (tsdf_2d.hip) on the same kernels.
+void LaunchGridGrow(const uint16_t* old_cells, int nx, int ny, uint16_t* grown, int x_offset,
+                    int y_offset, hipStream_t stream) {
+  GridGrowKernel<<<dim3(DivUp(nx, 256), ny), 256, 0, stream>>>(old_cells, nx, ny, grown, x_offset,
+                                                               y_offset);
+  CMX_HIP(hipGetLastError());
+}
+void LaunchKnownBox(const uint16_t* cells, int nx, int ny, int* box, hipStream_t stream) {
+  GridKnownBoxKernel<<<dim3(DivUp(nx, 256), ny), 256, 0, stream>>>(cells, nx, ny, box);
+  CMX_HIP(hipGetLastError());
+}
+
 // For the other translation units that read a resident grid (ceres_2d.hip).
 const uint16_t* Grid2DDeviceCells(const cmx_grid2d* grid, cmx_grid2d_limits* limits, int* device) {
   limits->resolution = grid->resolution;

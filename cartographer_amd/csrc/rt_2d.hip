@@ -403,7 +403,7 @@ void Rt2DLegacyBatch(const cmx_rt_options* options, const Rt2DItem* items, const
     size_t off_offsets, off_padded, off_scores;                // element offsets, device
   };
   std::vector<Plan> plan(num);
-  const bool tsdf = items[0].weight_cells != nullptr;
+  const bool tsdf = items[0].tsdf();
   size_t in_bytes = Align16(sizeof(Rt2DParams) * num);
   size_t offsets_total = 0, padded_bytes = 0, scores_total = 0;
   unsigned max_prep = 0, max_tiles = 0, max_tiles4 = 0, max_scans = 0, max_collect = 0;
@@ -429,7 +429,8 @@ void Rt2DLegacyBatch(const cmx_rt_options* options, const Rt2DItem* items, const
     pl.off_cells = pl.off_rot + Align16(sizeof(float2) * pl.num_scans);
     pl.off_weights =
         pl.off_cells + (it.device_cells ? 0 : Align16(sizeof(uint16_t) * cell_count));
-    in_bytes = pl.off_weights + (tsdf ? Align16(sizeof(uint16_t) * cell_count) : 0);
+    in_bytes = pl.off_weights +
+               (tsdf && !it.device_weight_cells ? Align16(sizeof(uint16_t) * cell_count) : 0);
     pl.off_offsets = offsets_total;
     offsets_total += static_cast<size_t>(pl.num_scans) * pl.n_pad;
     pl.off_padded = padded_bytes;
@@ -473,12 +474,15 @@ void Rt2DLegacyBatch(const cmx_rt_options* options, const Rt2DItem* items, const
     std::memcpy(h_in + pl.off_rot, table->data(), sizeof(float2) * pl.num_scans);
     if (!it.device_cells)
       std::memcpy(h_in + pl.off_cells, it.cells, sizeof(uint16_t) * cell_count);
-    if (tsdf) std::memcpy(h_in + pl.off_weights, it.weight_cells, sizeof(uint16_t) * cell_count);
+    if (tsdf && !it.device_weight_cells)
+      std::memcpy(h_in + pl.off_weights, it.weight_cells, sizeof(uint16_t) * cell_count);
 
     Rt2DParams P{};
     P.cells = it.device_cells ? it.device_cells
                               : reinterpret_cast<const uint16_t*>(d_in + pl.off_cells);
-    P.weights = tsdf ? reinterpret_cast<const uint16_t*>(d_in + pl.off_weights) : nullptr;
+    P.weights = !tsdf ? nullptr
+                : it.device_weight_cells ? it.device_weight_cells
+                                         : reinterpret_cast<const uint16_t*>(d_in + pl.off_weights);
     P.nx = pl.nx; P.ny = pl.ny;
     P.res = it.limits->resolution; P.max_x = it.limits->max_x; P.max_y = it.limits->max_y;
     P.inv_res = 1.0 / P.res;
@@ -645,7 +649,7 @@ void Rt2DMatchBatch(const cmx_rt_options* options, const Rt2DItem* items, int nu
     host_report += buf;
     t_last = now;
   };
-  const bool tsdf = items[0].weight_cells != nullptr;
+  const bool tsdf = items[0].tsdf();
   for (int m = 0; m < num; ++m) {
     const Rt2DItem& it = items[m];
     CMX_REQUIRE(it.limits && (it.cells || it.device_cells) && it.initial && it.xyz,
@@ -656,7 +660,7 @@ void Rt2DMatchBatch(const cmx_rt_options* options, const Rt2DItem* items, int nu
     CMX_REQUIRE(it.limits->resolution > 0. && it.limits->num_x_cells >= 1 &&
                     it.limits->num_y_cells >= 1,
                 "bad map limits");
-    CMX_REQUIRE((it.weight_cells != nullptr) == tsdf, "mixed grid types in one batch");
+    CMX_REQUIRE(it.tsdf() == tsdf, "mixed grid types in one batch");
     if (tsdf) CMX_REQUIRE(it.max_tsd > 0.f && it.max_weight > 0.f, "bad TSDF ranges");
   }
   // SearchParameters of every item (a range scan over its cloud, acos): on the host pool, part

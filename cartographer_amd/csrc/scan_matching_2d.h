@@ -219,6 +219,8 @@ struct Rt2DItem {            // one match of a batch
   int num_far_points = 0;
   Rt2DImageCache* image_cache = nullptr;  // with device_cells of a cmx_grid2d
   unsigned long long grid_version = 0;
+  const uint16_t* device_weight_cells = nullptr;  // TSDF weights already in HBM (cmx_tsdf2d)
+  bool tsdf() const { return weight_cells != nullptr || device_weight_cells != nullptr; }
 };
 // SearchParameters of one match (SM2/correlative_scan_matcher_2d.cc:27-47 on the cloud
 // pre-rotated by the initial yaw, real_time_..._2d.cc:123-130): host, libm.
@@ -257,6 +259,12 @@ class Rt2DTileCall {
 };
 void Rt2DMatchBatch(const cmx_rt_options* options, const Rt2DItem* items, int num, int32_t device,
                     cmx_match_stats* stats);
+// grid_2d.hip: Grid2D::GrowLimits of one uint16 plane (the old plane in the middle of one twice
+// as large, which the caller has filled with the unknown value) and the box of its non-zero
+// cells ({min_x, min_y, max_x, max_y}, preset by the caller to {INT_MAX, INT_MAX, -1, -1}).
+void LaunchGridGrow(const uint16_t* old_cells, int nx, int ny, uint16_t* grown, int x_offset,
+                    int y_offset, hipStream_t stream);
+void LaunchKnownBox(const uint16_t* cells, int nx, int ny, int* box, hipStream_t stream);
 void Rt2DMatch(const cmx_rt_options* options, const cmx_grid2d_limits* limits,
                const uint16_t* cells, const uint16_t* weight_cells, float max_tsd,
                float max_weight, const cmx_pose2d* initial_pose_estimate,

@@ -1,18 +1,19 @@
-"""Device-resident ProbabilityGrid: range-data insertion and real-time
-matching without moving the grid across PCIe.
+"""Device-resident ProbabilityGrid and TSDF2D: range-data insertion and
+real-time matching without moving the grid across PCIe.
 
 Mirrors what LocalTrajectoryBuilder2D does with the active submap
 (``mapping/internal/2d/local_trajectory_builder_2d.cc:78-80, 288-289``):
 ``ProbabilityGridRangeDataInserter2D::Insert`` (``insert``) and
 ``RealTimeCorrelativeScanMatcher2D::Match`` (``RealTimeCorrelativeScanMatcher2D.match`` accepts
-this class in place of a host ``Grid2D``).
+this class in place of a host ``Grid2D``).  ``TSDF2DOnDevice`` does the same for submaps of
+``grid_type = "TSDF"`` with ``TSDFRangeDataInserter2D::Insert``.
 """
 import ctypes as C
 
 import numpy as np
 
 from . import _lib
-from ._lib import Grid2DLimits, check
+from ._lib import Grid2DLimits, TSDFInserterOptions2D, check
 
 
 class ProbabilityGridOnDevice:
@@ -67,6 +68,85 @@ class ProbabilityGridOnDevice:
     def fast_matcher(self, branch_and_bound_depth, linear_search_window=7.0,
                      angular_search_window=float(np.deg2rad(30.0))):
         """FastCorrelativeScanMatcher2D of this (finished) grid."""
+        from .scan_matching import FastCorrelativeScanMatcher2D
+        return FastCorrelativeScanMatcher2D.from_device_grid(
+            self, branch_and_bound_depth, linear_search_window, angular_search_window)
+
+
+class TSDF2DOnDevice:
+    """TSDF2D(limits, truncation_distance, max_weight) in HBM: the tsd and weight planes (uint16,
+    0 = unknown).  The constructor takes the arguments of the test suite's ``ReferenceTSDF2D``;
+    ``tsd_cells`` / ``weight_cells`` start it from a copy of two planes instead of all unknown."""
+
+    def __init__(self, resolution, max_xy, num_x_cells, num_y_cells, truncation_distance,
+                 max_weight, tsd_cells=None, weight_cells=None, device=0):
+        limits = Grid2DLimits(resolution, max_xy[0], max_xy[1], num_x_cells, num_y_cells, 0.0, 0.0)
+        self.truncation_distance, self.max_weight = float(truncation_distance), float(max_weight)
+        self.device = device
+        self._h = C.c_void_p()
+        tsd = wgt = None
+        if (tsd_cells is None) != (weight_cells is None):
+            raise ValueError("give both planes or neither")
+        if tsd_cells is not None:
+            tsd = np.ascontiguousarray(tsd_cells, np.uint16)
+            wgt = np.ascontiguousarray(weight_cells, np.uint16)
+            assert tsd.shape == wgt.shape == (num_y_cells, num_x_cells)
+        check(_lib.lib().cmx_tsdf2d_create(
+            C.byref(limits), truncation_distance, max_weight,
+            None if tsd is None else tsd.ctypes.data, None if wgt is None else wgt.ctypes.data,
+            device, C.byref(self._h)))
+
+    def __del__(self):
+        if getattr(self, "_h", None):
+            _lib.lib().cmx_tsdf2d_destroy(self._h)
+            self._h = None
+
+    @property
+    def limits(self):
+        lim = Grid2DLimits()
+        check(_lib.lib().cmx_tsdf2d_get_limits(self._h, C.byref(lim)))
+        return dict(resolution=lim.resolution, max_x=lim.max_x, max_y=lim.max_y,
+                    num_x_cells=lim.num_x_cells, num_y_cells=lim.num_y_cells)
+
+    def planes(self):
+        """(tsd cells, weight cells), uint16 [ny, nx] each."""
+        lim = self.limits
+        shape = (lim["num_y_cells"], lim["num_x_cells"])
+        tsd, wgt = np.empty(shape, np.uint16), np.empty(shape, np.uint16)
+        check(_lib.lib().cmx_tsdf2d_download(self._h, tsd.ctypes.data, wgt.ctypes.data))
+        return tsd, wgt
+
+    def insert(self, origin_xyz, returns_xyz, truncation_distance, maximum_weight,
+               update_free_space, num_normal_samples, sample_radius,
+               project_sdf_distance_to_scan_normal, update_weight_range_exponent,
+               angle_kernel_bandwidth, distance_kernel_bandwidth):
+        """TSDFRangeDataInserter2D::Insert; points in the map frame.  The keywords are those of
+        ReferenceTSDF2D.insert, so one dict drives both."""
+        origin = np.ascontiguousarray(origin_xyz, np.float32).reshape(-1)[:3].copy()
+        ret = np.ascontiguousarray(returns_xyz, np.float32).reshape(-1, 3)
+        options = TSDFInserterOptions2D(
+            truncation_distance, maximum_weight, int(update_free_space), int(num_normal_samples),
+            sample_radius, int(project_sdf_distance_to_scan_normal),
+            int(update_weight_range_exponent), angle_kernel_bandwidth, distance_kernel_bandwidth)
+        check(_lib.lib().cmx_tsdf2d_insert(self._h, origin.ctypes.data,
+                                           ret.ctypes.data if ret.shape[0] else None,
+                                           ret.shape[0], C.byref(options)))
+
+    def crop(self):
+        """grid = grid->ComputeCroppedGrid() (tsdf_2d.cc:118-135)."""
+        check(_lib.lib().cmx_tsdf2d_crop(self._h))
+
+    def to_host(self):
+        """The planes as a host ``scan_matching.TSDF2D``."""
+        from .scan_matching import TSDF2D
+        lim = self.limits
+        tsd, wgt = self.planes()
+        return TSDF2D(tsd, wgt, lim["resolution"], lim["max_x"], lim["max_y"],
+                      self.truncation_distance, self.max_weight)
+
+    def fast_matcher(self, branch_and_bound_depth, linear_search_window=7.0,
+                     angular_search_window=float(np.deg2rad(30.0))):
+        """FastCorrelativeScanMatcher2D of this (finished) grid's tsd plane."""
         from .scan_matching import FastCorrelativeScanMatcher2D
         return FastCorrelativeScanMatcher2D.from_device_grid(
             self, branch_and_bound_depth, linear_search_window, angular_search_window)

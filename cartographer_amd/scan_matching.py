@@ -99,7 +99,16 @@ class RealTimeCorrelativeScanMatcher2D:
 
     def match(self, initial_pose_estimate, point_cloud, grid):
         xyz, n = _cloud(point_cloud)
-        from .grid_2d import ProbabilityGridOnDevice
+        from .grid_2d import ProbabilityGridOnDevice, TSDF2DOnDevice
+        if isinstance(grid, TSDF2DOnDevice):              # TSDF planes already in HBM
+            init = initial_pose_estimate.to_c()
+            score, pose, stats = C.c_double(), Pose2d(), MatchStats()
+            check(_lib.lib().cmx_rt2d_match_tsdf_grid(C.byref(self.options), grid._h,
+                                                      C.byref(init), xyz.ctypes.data, n,
+                                                      C.byref(score), C.byref(pose),
+                                                      C.byref(stats)))
+            self.last_stats = stats.as_dict()
+            return score.value, Rigid2d(pose.x, pose.y, pose.theta)
         if isinstance(grid, ProbabilityGridOnDevice):     # grid already in HBM
             init = initial_pose_estimate.to_c()
             score, pose, stats = C.c_double(), Pose2d(), MatchStats()
@@ -229,7 +238,9 @@ class FastCorrelativeScanMatcher2D:
     @classmethod
     def from_device_grid(cls, device_grid, branch_and_bound_depth, linear_search_window=7.0,
                          angular_search_window=float(np.deg2rad(30.0))):
-        """Matcher of a grid that lives in HBM (cartographer_amd.grid_2d.ProbabilityGridOnDevice)."""
+        """Matcher of a grid that lives in HBM (cartographer_amd.grid_2d.ProbabilityGridOnDevice,
+        or TSDF2DOnDevice: the tsd plane over the cost range [-truncation, truncation])."""
+        from .grid_2d import TSDF2DOnDevice
         self = cls.__new__(cls)
         self.grid = device_grid
         self.options = Fast2DOptions(linear_search_window, angular_search_window,
@@ -237,8 +248,9 @@ class FastCorrelativeScanMatcher2D:
         self.device = device_grid.device
         self.last_stats = None
         self._h = C.c_void_p()
-        check(_lib.lib().cmx_fast2d_create_from_grid(C.byref(self.options), device_grid._h,
-                                                     C.byref(self._h)))
+        create = (_lib.lib().cmx_fast2d_create_from_tsdf if isinstance(device_grid, TSDF2DOnDevice)
+                  else _lib.lib().cmx_fast2d_create_from_grid)
+        check(create(C.byref(self.options), device_grid._h, C.byref(self._h)))
         return self
 
     def __del__(self):

@@ -244,6 +244,60 @@ cmx_status cmx_rt2d_match_grid_batch_resident(const cmx_rt_options* options,
                                               const cmx_cloud* const* clouds, double* scores,
                                               cmx_pose2d* pose_estimates, cmx_match_stats* stats);
 
+/* ---- device-resident TSDF2D ------------------------------------------------ */
+/* The active submap of grid_type = "TSDF" (mapping/2d/submap_2d.cc:58-60, :183-186) kept in
+ * HBM: the tsd plane (Grid2D's correspondence_cost_cells) and the weight plane, both uint16
+ * row-major nx*iy+ix, 0 = unknown.
+ *   cmx_tsdf2d_create     TSDF2D(limits, truncation_distance, max_weight) (all unknown) or a
+ *                         copy of the two planes (mapping/internal/2d/tsdf_2d.cc:24-47).  The
+ *                         two values are the grid's TSDValueConverter, separate from the
+ *                         inserter's options.  A cell whose tsd value carries the update marker
+ *                         (bit 15) is never updated and keeps the bit, as in the reference.
+ *   cmx_tsdf2d_get_limits the MapLimits; the cost range is [-truncation, truncation]
+ *   cmx_tsdf2d_insert     TSDFRangeDataInserter2D::Insert (mapping/internal/2d/
+ *                         tsdf_range_data_inserter_2d.cc:131-240, normal_estimation_2d.cc:23-110);
+ *                         grows the limits like GrowAsNeeded / Grid2D::GrowLimits.  Points are
+ *                         in the map frame, xyz triples; `origin_xyz` is the sensor origin.
+ *                         Range data whose rays leave the grown limits (z != 0 shortens the
+ *                         box GrowAsNeeded builds from 3D directions) is CMX_INVALID_ARGUMENT.
+ *   cmx_tsdf2d_crop       grid = grid->ComputeCroppedGrid() (tsdf_2d.cc:118-135)
+ *   cmx_rt2d_match_tsdf_grid  cmx_rt2d_match_tsdf with the planes read from HBM
+ *   cmx_fast2d_create_from_tsdf  FastCorrelativeScanMatcher2D of the tsd plane over the cost
+ *                         range [-truncation, truncation] */
+/* proto::TSDFRangeDataInserterOptions2D with its proto::NormalEstimationOptions2D
+ * (num_normal_samples > 0 and sample_radius > 0, normal_estimation_2d.cc:64-74). */
+typedef struct cmx_tsdf_inserter_options_2d {
+  double truncation_distance;
+  double maximum_weight;
+  int32_t update_free_space;
+  int32_t num_normal_samples;
+  double sample_radius;
+  int32_t project_sdf_distance_to_scan_normal;
+  int32_t update_weight_range_exponent;
+  double update_weight_angle_scan_normal_to_ray_kernel_bandwidth;
+  double update_weight_distance_cell_to_hit_kernel_bandwidth;
+} cmx_tsdf_inserter_options_2d;
+
+typedef struct cmx_tsdf2d cmx_tsdf2d;
+cmx_status cmx_tsdf2d_create(const cmx_grid2d_limits* limits, float truncation_distance,
+                             float max_weight, const uint16_t* tsd_cells_or_null,
+                             const uint16_t* weight_cells_or_null, int32_t device,
+                             cmx_tsdf2d** out);
+void cmx_tsdf2d_destroy(cmx_tsdf2d* grid);
+cmx_status cmx_tsdf2d_get_limits(const cmx_tsdf2d* grid, cmx_grid2d_limits* limits);
+cmx_status cmx_tsdf2d_download(const cmx_tsdf2d* grid, uint16_t* tsd_cells,
+                               uint16_t* weight_cells);
+cmx_status cmx_tsdf2d_insert(cmx_tsdf2d* grid, const float* origin_xyz, const float* returns_xyz,
+                             int32_t num_returns, const cmx_tsdf_inserter_options_2d* options);
+cmx_status cmx_tsdf2d_crop(cmx_tsdf2d* grid);
+cmx_status cmx_rt2d_match_tsdf_grid(const cmx_rt_options* options, const cmx_tsdf2d* grid,
+                                    const cmx_pose2d* initial_pose_estimate,
+                                    const float* point_cloud_xyz, int32_t num_points,
+                                    double* score, cmx_pose2d* pose_estimate,
+                                    cmx_match_stats* stats);
+cmx_status cmx_fast2d_create_from_tsdf(const cmx_fast2d_options* options, const cmx_tsdf2d* grid,
+                                       cmx_fast2d** out);
+
 /* ---- fast 2D (branch and bound) ---------------------------------------- */
 /* Uploads the grid and builds the PrecomputationGridStack2D on `device`
  * (SM2/fast_correlative_scan_matcher_2d.cc:171-186). */

@@ -1,0 +1,104 @@
+#!/usr/bin/env python3
+"""Timing of the device-resident TSDF2D (cartographer_amd/csrc/tsdf_2d.hip); prints one JSON line.
+
+Legs (each after warm-up, median over --calls calls, host clock around the call; every call ends
+in a synchronise):
+  insert_lua_ms / insert_free_space_ms   cmx_tsdf2d_insert of one ~1000-point room scan
+                                         (tests/golden/tsdf_insert_golden.npz inputs) into a grid
+                                         that already holds the room, lua defaults / free space on
+  ref_cpu_insert_*_ms                    the reference's own inserter (oracle/_ref) on this host,
+                                         same scans (null where oracle/_ref is not built)
+  rt_match_resident_ms / rt_match_host_planes_ms
+                                         cmx_rt2d_match_tsdf_grid against cmx_rt2d_match_tsdf
+                                         (planes uploaded per call) on a 200x200 grid
+  cells_changed_per_insert_*             cells whose (tsd, weight) the insert changed (median)
+Usage: python tools/tsdf_timing.py [--calls 60]
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests", "golden"))
+
+
+def _median_ms(fn, calls, warmup=5):
+    for k in range(warmup):
+        fn(k)
+    times = []
+    for k in range(calls):
+        t0 = time.perf_counter()
+        fn(k)
+        times.append((time.perf_counter() - t0) * 1e3)
+    return float(np.median(times))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--calls", type=int, default=60)
+    args = ap.parse_args()
+    import make_tsdf_insert_golden as mk
+    from cartographer_amd import grid_2d, scan_matching as sm
+    golden = dict(np.load(os.path.join(ROOT, "tests", "golden", "tsdf_insert_golden.npz")))
+    scans = [mk.step_inputs(golden, "room_lua", k)[:2] for k in range(12)]
+    out = {"points_per_scan": float(np.mean([r.shape[0] for _, r in scans]))}
+    res, mx, my, _, _, t, w = golden["room_lua/meta"]
+    # 200 x 200 cells of 5 cm over the room's points: no insert grows the grid
+    pts = np.concatenate([r for _, r in scans] + [o[None] for o, _ in scans])
+    lo, hi = pts.min(0), pts.max(0)
+    assert (hi - lo)[:2].max() < 9.0, "the room does not fit 200 x 200 cells"
+    margin = (10.0 - (hi - lo)) / 2
+    centre = (float(hi[0] + margin[0]), float(hi[1] + margin[1]))
+    try:
+        from oracle import pyoracle as orc
+        ref = orc if orc.ref_lib() is not None else None
+    except Exception:  # pragma: no cover - the oracle is optional here
+        ref = None
+    for label, opts in (("lua", mk.LUA_DEFAULTS),
+                        ("free_space", dict(mk.LUA_DEFAULTS, update_free_space=True))):
+        dev = grid_2d.TSDF2DOnDevice(res, centre, 200, 200, t, w)
+        for o, r in scans:
+            dev.insert(o, r, **opts)
+        assert dev.limits["num_x_cells"] == 200, "the timing grid grew"
+        out[f"insert_{label}_ms"] = _median_ms(
+            lambda k: dev.insert(scans[k % 12][0], scans[k % 12][1], **opts), args.calls)
+        changed = []
+        for k in range(12):
+            a = dev.planes()
+            dev.insert(scans[k][0], scans[k][1], **opts)
+            b = dev.planes()
+            changed.append(int(np.count_nonzero((a[0] != b[0]) | (a[1] != b[1]))))
+        out[f"cells_changed_per_insert_{label}"] = float(np.median(changed))
+        if ref is not None:
+            g = ref.ReferenceTSDF2D(res, centre, 200, 200, t, w)
+            for o, r in scans:
+                g.insert(o, r, **opts)
+            out[f"ref_cpu_insert_{label}_ms"] = _median_ms(
+                lambda k: g.insert(scans[k % 12][0], scans[k % 12][1], **opts), args.calls)
+        else:
+            out[f"ref_cpu_insert_{label}_ms"] = None
+        if label == "lua":
+            host = dev.to_host()
+            rt = sm.RealTimeCorrelativeScanMatcher2D(0.3, np.deg2rad(8.0), 0.1, 0.1)
+            o, r = scans[3]
+            scan = r[::2] - np.array([o[0], o[1], 0.0], np.float32)
+            init = sm.Rigid2d(float(o[0]) + 0.05, float(o[1]) - 0.04, 0.02)
+            out["rt_match_points"] = int(scan.shape[0])
+            out["rt_match_resident_ms"] = _median_ms(lambda k: rt.match(init, scan, dev),
+                                                     args.calls)
+            out["rt_match_host_planes_ms"] = _median_ms(lambda k: rt.match(init, scan, host),
+                                                        args.calls)
+            a, b = rt.match(init, scan, dev), rt.match(init, scan, host)
+            out["rt_match_equal"] = bool(a[0] == b[0] and a[1].x == b[1].x and a[1].y == b[1].y
+                                         and a[1].theta == b[1].theta)
+    out["calls"] = args.calls
+    print(json.dumps(out, sort_keys=True))
+
+
+if __name__ == "__main__":
+    main()
