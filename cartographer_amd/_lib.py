@@ -173,6 +173,8 @@ EXPORTED_SYMBOLS = [
     "cmx_fast3d_match_batch",
     "cmx_fast3d_level_info", "cmx_fast3d_level_cells",
     "cmx_ceres2d_match", "cmx_ceres2d_match_grid", "cmx_fast2d_refine_batch", "cmx_ceres3d_match",
+    "cmx_ceres2d_match_tsdf", "cmx_ceres2d_match_tsdf_grid", "cmx_ceres2d_refine_batch_tsdf",
+    "cmx_ceres2d_tsdf_residuals",
     "cmx_ceres3d_match_grids", "cmx_rt2d_score_candidates", "cmx_rt3d_match_grid",
     "cmx_fast3d_refine_batch",
     "cmx_comm_init", "cmx_comm_destroy", "cmx_comm_num_devices", "cmx_comm_device_of",
@@ -298,6 +300,20 @@ def lib():
     L.cmx_fast2d_refine_batch.argtypes = [P(Ceres2DOptions), P(C.c_void_p), C.c_int32, C.c_void_p,
                                           C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p,
                                           C.c_void_p]
+    L.cmx_ceres2d_match_tsdf.argtypes = [P(Ceres2DOptions), P(Grid2DLimits), C.c_void_p,
+                                         C.c_void_p, C.c_float, C.c_float, C.c_void_p, P(Pose2d),
+                                         C.c_void_p, C.c_int32, C.c_int32, P(Pose2d),
+                                         P(CeresSummary)]
+    L.cmx_ceres2d_match_tsdf_grid.argtypes = [P(Ceres2DOptions), C.c_void_p, C.c_void_p,
+                                              P(Pose2d), C.c_void_p, C.c_int32, P(Pose2d),
+                                              P(CeresSummary)]
+    L.cmx_ceres2d_refine_batch_tsdf.argtypes = [P(Ceres2DOptions), P(C.c_void_p), C.c_int32,
+                                                C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
+                                                C.c_void_p, C.c_void_p]
+    L.cmx_ceres2d_tsdf_residuals.argtypes = [P(Grid2DLimits), C.c_void_p, C.c_void_p, C.c_float,
+                                             C.c_float, C.c_double, C.c_void_p, C.c_void_p,
+                                             C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
+                                             P(C.c_int32)]
     L.cmx_ceres3d_match.argtypes = [P(Ceres3DOptions), C.c_void_p, P(Pose3d), C.c_void_p, C.c_int32,
                                     P(Pose3d), P(CeresSummary)]
     L.cmx_rt2d_score_candidates.argtypes = [P(RtOptions), P(Grid2DLimits), C.c_void_p, C.c_void_p,

@@ -22,6 +22,18 @@
 // order -- results do not depend on scheduling.  Thread 0 then runs the trust-region logic.
 // Residual + Jacobian are evaluated together at every candidate (the Jacobian of a rejected
 // candidate is wasted; evaluating it separately would be a second pass over the points).
+//
+// On a TSDF2D (the GridType::TSDF case, ceres_scan_matcher_2d.cc:83-90) the point residuals are
+// SM2/tsdf_match_cost_function_2d.cc:40-66 over SM2/interpolated_tsdf_2d.h:42-125:
+// r_i = n s C_i w_i / S with S = sum_j w_j, so no residual is separable from the others.  One
+// pass accumulates, per thread, u_i = n s C_i w_i with its gradient a_i and w_i with its gradient
+// g_i: U = sum u^2, A = sum u a, B = sum a a^T, S and G = sum g (14 numbers), reduced in the same
+// fixed order.  Then sum r^2 = U / S^2, J^T r = (A - (U / S) G) / S^2 and
+// J^T J = (B - (A G^T + G A^T) / S + (U / S^2) G G^T) / S^2.  S == 0 makes the functor return
+// false (.cc:61): the evaluation fails, which the trust-region loop treats as the stand-in solver
+// does (oracle/ref_shims/ceres/ceres.h: a failed initial evaluation ends the solve with FAILURE,
+// a failed candidate costs DBL_MAX and is rejected).
+#include <cfloat>
 #include <climits>
 #include <cmath>
 #include <map>
@@ -30,8 +42,12 @@
 #include "scan_matching_2d.h"
 
 struct cmx_grid2d;   // grid_2d.hip
+struct cmx_tsdf2d;   // tsdf_2d.hip
 namespace cmx {
 const uint16_t* Grid2DDeviceCells(const cmx_grid2d* grid, cmx_grid2d_limits* limits, int* device);
+// The two planes of a resident TSDF2D; limits carry the cost range [-truncation, truncation].
+void Tsdf2DDevicePlanes(const cmx_tsdf2d* grid, cmx_grid2d_limits* limits, const uint16_t** tsd,
+                        const uint16_t** weight, float* max_weight, int* device);
 }
 
 namespace cmx {
@@ -41,10 +57,12 @@ constexpr int kCeresThreads = 256;
 constexpr int kPadding = INT_MAX / 4;   // occupied_space_cost_function_2d.cc:78
 
 struct Ceres2DProblem {
-  const uint16_t* cells;       // device grid
+  const uint16_t* cells;       // device grid (a TSDF's tsd plane)
+  const uint16_t* weights;     // device weight plane of a TSDF (null for a probability grid)
   int nx, ny;
   double res, max_x, max_y;
   float min_cc, max_cc;        // the grid's correspondence cost range (value table)
+  float max_weight;            // TSDF: the TSDValueConverter's weight range [0, max_weight]
   const float* xyz;            // device cloud
   int n;
   double init[3];              // initial pose estimate (x, y, theta)
@@ -90,8 +108,89 @@ __device__ __forceinline__ void Spline(double p0, double p1, double p2, double p
   *dfdx = c + x * (2.0 * b + 3.0 * a * x);
 }
 
-struct Sums {     // cost (sum of squares), g = J^T r, H = J^T J (upper triangle)
-  double v[10];
+// ceres::Jet<double, 3> over the pose (x, y, theta), with the operations of the TSDF cost in
+// oracle/ref_shims/ceres/jet.h's order.
+struct Jet3 {
+  double a, v[3];
+};
+__device__ __forceinline__ Jet3 JetConst(double a) { return {a, {0., 0., 0.}}; }
+__device__ __forceinline__ Jet3 operator+(const Jet3& f, const Jet3& g) {
+  return {f.a + g.a, {f.v[0] + g.v[0], f.v[1] + g.v[1], f.v[2] + g.v[2]}};
+}
+__device__ __forceinline__ Jet3 operator-(const Jet3& f, const Jet3& g) {
+  return {f.a - g.a, {f.v[0] - g.v[0], f.v[1] - g.v[1], f.v[2] - g.v[2]}};
+}
+__device__ __forceinline__ Jet3 operator*(const Jet3& f, const Jet3& g) {
+  return {f.a * g.a, {f.a * g.v[0] + f.v[0] * g.a, f.a * g.v[1] + f.v[1] * g.a,
+                      f.a * g.v[2] + f.v[2] * g.a}};
+}
+// f / g for a constant g: (f.v - (f.a / g) * 0) / g, through the inverse as the Jet does.
+__device__ __forceinline__ Jet3 DivConst(const Jet3& f, double g) {
+  const double inv = 1.0 / g;
+  return {f.a * inv, {f.v[0] * inv, f.v[1] * inv, f.v[2] * inv}};
+}
+
+// TSDF2D::GetWeight (tsdf_2d.cc:80-86): the TSDValueConverter's weight table over
+// [0, max_weight], 0 for unknown and outside cells.
+__device__ __forceinline__ float TsdfWeight(const Ceres2DProblem& P, int ix, int iy) {
+  const bool inside = static_cast<unsigned>(ix) < static_cast<unsigned>(P.nx) &&
+                      static_cast<unsigned>(iy) < static_cast<unsigned>(P.ny);
+  const unsigned raw = AsGlobal(P.weights)[inside ? P.nx * iy + ix : 0];
+  return inside ? BoundedValue(raw, 0.f, 0.f, P.max_weight) : 0.f;
+}
+
+// InterpolatedTSDF2D::InterpolateBilinear (interpolated_tsdf_2d.h:89-98).
+__device__ __forceinline__ Jet3 Bilinear(const Jet3& x, const Jet3& y, float x1, float y1,
+                                         float x2, float y2, float q11, float q12, float q21,
+                                         float q22) {
+  const Jet3 nx = DivConst(x - JetConst(static_cast<double>(x1)), static_cast<double>(x2 - x1));
+  const Jet3 ny = DivConst(y - JetConst(static_cast<double>(y1)), static_cast<double>(y2 - y1));
+  const Jet3 q1 = JetConst(static_cast<double>(q12 - q11)) * ny + JetConst(static_cast<double>(q11));
+  const Jet3 q2 = JetConst(static_cast<double>(q22 - q21)) * ny + JetConst(static_cast<double>(q21));
+  return (q2 - q1) * nx + q1;
+}
+
+// One point of TSDFMatchCostFunction2D::operator() (tsdf_match_cost_function_2d.cc:40-59) at the
+// pose whose rotation is (c, s): u = T(n) * scaling * C * w before the division by S, and w.
+__device__ __forceinline__ void TsdfPoint(const Ceres2DProblem& P, const double x[3], double c,
+                                          double s, double ns, int i, Jet3* u, Jet3* w) {
+  const double px = static_cast<double>(P.xyz[3 * i]), py = static_cast<double>(P.xyz[3 * i + 1]);
+  const Jet3 wx = {c * px + -s * py + x[0] * 1., {1., 0., -s * px - c * py}};
+  const Jet3 wy = {s * px + c * py + x[1] * 1., {0., 1., c * px - s * py}};
+  // CenterOfLowerPixel (interpolated_tsdf_2d.h:104-117) on the scalar parts: the point rounded
+  // to f32, MapLimits::GetCellIndex in double, GetCellCenter computed in double and stored as
+  // f32, compared with the double coordinate, moved down by one resolution in double.
+  const float fx = static_cast<float>(wx.a), fy = static_cast<float>(wy.a);
+  const int cx_index = LRoundF64((P.max_y - static_cast<double>(fy)) / P.res - 0.5);
+  const int cy_index = LRoundF64((P.max_x - static_cast<double>(fx)) / P.res - 0.5);
+  float x1 = static_cast<float>(P.max_x - P.res * (cy_index + 0.5));
+  float y1 = static_cast<float>(P.max_y - P.res * (cx_index + 0.5));
+  if (static_cast<double>(x1) > wx.a) x1 = static_cast<float>(static_cast<double>(x1) - P.res);
+  if (static_cast<double>(y1) > wy.a) y1 = static_cast<float>(static_cast<double>(y1) - P.res);
+  const float x2 = x1 + static_cast<float>(P.res), y2 = y1 + static_cast<float>(P.res);
+  // index1 = GetCellIndex(Vector2f(x1, y1)); neighbours (-1, 0), (0, -1), (-1, -1).
+  const int ix = LRoundF64((P.max_y - static_cast<double>(y1)) / P.res - 0.5);
+  const int iy = LRoundF64((P.max_x - static_cast<double>(x1)) / P.res - 0.5);
+  const float w11 = TsdfWeight(P, ix, iy), w12 = TsdfWeight(P, ix - 1, iy);
+  const float w21 = TsdfWeight(P, ix, iy - 1), w22 = TsdfWeight(P, ix - 1, iy - 1);
+  *w = Bilinear(wx, wy, x1, y1, x2, y2, w11, w12, w21, w22);
+  Jet3 cost = JetConst(static_cast<double>(P.max_cc));
+  if (!(w11 == 0.f || w12 == 0.f || w21 == 0.f || w22 == 0.f)) {
+    const float q11 = static_cast<float>(CellCost(P, ix, iy));
+    const float q12 = static_cast<float>(CellCost(P, ix - 1, iy));
+    const float q21 = static_cast<float>(CellCost(P, ix, iy - 1));
+    const float q22 = static_cast<float>(CellCost(P, ix - 1, iy - 1));
+    cost = Bilinear(wx, wy, x1, y1, x2, y2, q11, q12, q21, q22);
+  }
+  *u = (JetConst(ns) * cost) * *w;
+}
+
+// Per-thread sums of one evaluation.  Probability grid: cost (sum of squares), g = J^T r,
+// H = J^T J (upper triangle).  TSDF: U, A (3), B (upper triangle, 6), S, G (3).
+template <bool kTsdf>
+struct Sums {
+  static constexpr int kCount = kTsdf ? 14 : 10;
+  double v[kCount];
 };
 
 __device__ __forceinline__ double WaveSumF64(double v) {
@@ -100,52 +199,83 @@ __device__ __forceinline__ double WaveSumF64(double v) {
   return v;
 }
 
-// Residual blocks at `x`: leaves 1/2 |r|^2, J^T r and J^T J in `e` (valid in every thread).
-__device__ void Evaluate(const Ceres2DProblem& P, const double x[3], double (*scratch)[10],
-                         double* cost, double g[3], double H[3][3]) {
+// Residual blocks at `x`: leaves 1/2 |r|^2, J^T r and J^T J (valid in every thread).  False when
+// the cost function fails (a TSDF with S == 0); the outputs are then undefined.
+template <bool kTsdf>
+__device__ bool Evaluate(const Ceres2DProblem& P, const double x[3],
+                         double (*scratch)[Sums<kTsdf>::kCount], double* cost, double g[3],
+                         double H[3][3]) {
+  constexpr int kCount = Sums<kTsdf>::kCount;
   const double c = cos(x[2]), s = sin(x[2]);
-  Sums acc;
+  Sums<kTsdf> acc;
 #pragma unroll
-  for (int k = 0; k < 10; ++k) acc.v[k] = 0.;
-  for (int i = threadIdx.x; i < P.n; i += kCeresThreads) {
-    const double px = static_cast<double>(P.xyz[3 * i]), py = static_cast<double>(P.xyz[3 * i + 1]);
-    const double wx = c * px + -s * py + x[0] * 1.;
-    const double wy = s * px + c * py + x[1] * 1.;
-    const double r = (P.max_x - wx) / P.res - 0.5 + static_cast<double>(kPadding);
-    const double cc = (P.max_y - wy) / P.res - 0.5 + static_cast<double>(kPadding);
-    const int row = static_cast<int>(floor(r)), col = static_cast<int>(floor(cc));
-    double fr[4], dfr[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      const int rr = row - 1 + k;
-      Spline(AdapterValue(P, rr, col - 1), AdapterValue(P, rr, col), AdapterValue(P, rr, col + 1),
-             AdapterValue(P, rr, col + 2), cc - col, &fr[k], &dfr[k]);
+  for (int k = 0; k < kCount; ++k) acc.v[k] = 0.;
+  if constexpr (kTsdf) {
+    const double ns = static_cast<double>(P.n) * P.occupied_scaling;
+    for (int i = threadIdx.x; i < P.n; i += kCeresThreads) {
+      Jet3 u, w;
+      TsdfPoint(P, x, c, s, ns, i, &u, &w);
+      acc.v[0] += u.a * u.a;
+      acc.v[1] += u.a * u.v[0]; acc.v[2] += u.a * u.v[1]; acc.v[3] += u.a * u.v[2];
+      acc.v[4] += u.v[0] * u.v[0]; acc.v[5] += u.v[0] * u.v[1]; acc.v[6] += u.v[0] * u.v[2];
+      acc.v[7] += u.v[1] * u.v[1]; acc.v[8] += u.v[1] * u.v[2]; acc.v[9] += u.v[2] * u.v[2];
+      acc.v[10] += w.a;
+      acc.v[11] += w.v[0]; acc.v[12] += w.v[1]; acc.v[13] += w.v[2];
     }
-    double f, dfdr, dfdc, unused;
-    Spline(fr[0], fr[1], fr[2], fr[3], r - row, &f, &dfdr);
-    Spline(dfr[0], dfr[1], dfr[2], dfr[3], r - row, &dfdc, &unused);
-    const double res_i = P.occupied_scaling * f;
-    const double dwx_dt = -s * px - c * py, dwy_dt = c * px - s * py;
-    const double j0 = P.occupied_scaling * (dfdr * (-1. / P.res));
-    const double j1 = P.occupied_scaling * (dfdc * (-1. / P.res));
-    const double j2 = P.occupied_scaling * (dfdr * (-dwx_dt / P.res) + dfdc * (-dwy_dt / P.res));
-    acc.v[0] += res_i * res_i;
-    acc.v[1] += j0 * res_i; acc.v[2] += j1 * res_i; acc.v[3] += j2 * res_i;
-    acc.v[4] += j0 * j0; acc.v[5] += j0 * j1; acc.v[6] += j0 * j2;
-    acc.v[7] += j1 * j1; acc.v[8] += j1 * j2; acc.v[9] += j2 * j2;
+  } else {
+    for (int i = threadIdx.x; i < P.n; i += kCeresThreads) {
+      const double px = static_cast<double>(P.xyz[3 * i]), py = static_cast<double>(P.xyz[3 * i + 1]);
+      const double wx = c * px + -s * py + x[0] * 1.;
+      const double wy = s * px + c * py + x[1] * 1.;
+      const double r = (P.max_x - wx) / P.res - 0.5 + static_cast<double>(kPadding);
+      const double cc = (P.max_y - wy) / P.res - 0.5 + static_cast<double>(kPadding);
+      const int row = static_cast<int>(floor(r)), col = static_cast<int>(floor(cc));
+      double fr[4], dfr[4];
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        const int rr = row - 1 + k;
+        Spline(AdapterValue(P, rr, col - 1), AdapterValue(P, rr, col), AdapterValue(P, rr, col + 1),
+               AdapterValue(P, rr, col + 2), cc - col, &fr[k], &dfr[k]);
+      }
+      double f, dfdr, dfdc, unused;
+      Spline(fr[0], fr[1], fr[2], fr[3], r - row, &f, &dfdr);
+      Spline(dfr[0], dfr[1], dfr[2], dfr[3], r - row, &dfdc, &unused);
+      const double res_i = P.occupied_scaling * f;
+      const double dwx_dt = -s * px - c * py, dwy_dt = c * px - s * py;
+      const double j0 = P.occupied_scaling * (dfdr * (-1. / P.res));
+      const double j1 = P.occupied_scaling * (dfdc * (-1. / P.res));
+      const double j2 = P.occupied_scaling * (dfdr * (-dwx_dt / P.res) + dfdc * (-dwy_dt / P.res));
+      acc.v[0] += res_i * res_i;
+      acc.v[1] += j0 * res_i; acc.v[2] += j1 * res_i; acc.v[3] += j2 * res_i;
+      acc.v[4] += j0 * j0; acc.v[5] += j0 * j1; acc.v[6] += j0 * j2;
+      acc.v[7] += j1 * j1; acc.v[8] += j1 * j2; acc.v[9] += j2 * j2;
+    }
   }
   const int wave = threadIdx.x >> 6;
 #pragma unroll
-  for (int k = 0; k < 10; ++k) {
+  for (int k = 0; k < kCount; ++k) {
     const double t = WaveSumF64(acc.v[k]);
     if ((threadIdx.x & 63) == 0) scratch[wave][k] = t;
   }
   __syncthreads();
-  double total[10];
+  double total[kCount];
 #pragma unroll
-  for (int k = 0; k < 10; ++k)
+  for (int k = 0; k < kCount; ++k)
     total[k] = ((scratch[0][k] + scratch[1][k]) + scratch[2][k]) + scratch[3][k];
   __syncthreads();
+  if constexpr (kTsdf) {
+    const double S = total[10];
+    if (S == 0.) return false;                      // tsdf_match_cost_function_2d.cc:61
+    const double S2 = S * S, U_S = total[0] / S, U_S2 = total[0] / S2;
+    const double A[3] = {total[1], total[2], total[3]};
+    const double G[3] = {total[11], total[12], total[13]};
+    total[0] = U_S2;
+    for (int a = 0; a < 3; ++a) total[1 + a] = (A[a] - U_S * G[a]) / S2;
+    int k = 4;
+    for (int a = 0; a < 3; ++a)
+      for (int b = a; b < 3; ++b, ++k)
+        total[k] = (total[k] - (A[a] * G[b] + G[a] * A[b]) / S + U_S2 * (G[a] * G[b])) / S2;
+  }
   // TranslationDeltaCostFunctor2D / RotationDeltaCostFunctor2D.
   const double rt0 = P.translation_weight * (x[0] - P.target_x);
   const double rt1 = P.translation_weight * (x[1] - P.target_y);
@@ -161,6 +291,7 @@ __device__ void Evaluate(const Ceres2DProblem& P, const double x[3], double (*sc
   g[0] = total[1]; g[1] = total[2]; g[2] = total[3];
   H[0][0] = total[4]; H[0][1] = H[1][0] = total[5]; H[0][2] = H[2][0] = total[6];
   H[1][1] = total[7]; H[1][2] = H[2][1] = total[8]; H[2][2] = total[9];
+  return true;
 }
 
 // Cholesky solve of the symmetric positive definite 3 x 3 system; false if not SPD.
@@ -196,10 +327,11 @@ __device__ bool SolveSpd3(const double A[3][3], const double b[3], double x[3]) 
 // levenberg_marquardt_strategy.cc, trust_region_step_evaluator.cc), statement for statement.
 // Every thread carries the (identical) minimizer state: no broadcast is needed, the block
 // only meets inside Evaluate.
+template <bool kTsdf>
 __global__ void __launch_bounds__(kCeresThreads)
 Ceres2DKernel(const Ceres2DProblem* __restrict__ problems) {
   const Ceres2DProblem& P = problems[blockIdx.x];
-  __shared__ double scratch[4][10];
+  __shared__ double scratch[4][Sums<kTsdf>::kCount];
   if (P.skip) {
     if (threadIdx.x == 0) {
       P.out[0] = P.init[0]; P.out[1] = P.init[1]; P.out[2] = P.init[2];
@@ -215,7 +347,15 @@ Ceres2DKernel(const Ceres2DProblem* __restrict__ problems) {
 
   double x[3] = {P.init[0], P.init[1], P.init[2]};
   double x_cost, g[3], H[3][3];
-  Evaluate(P, x, scratch, &x_cost, g, H);
+  if (!Evaluate<kTsdf>(P, x, scratch, &x_cost, g, H)) {
+    // The initial evaluation failed: FAILURE, the pose untouched, and the summary fields keep
+    // ceres::Solver::Summary's initial values.
+    if (threadIdx.x == 0) {
+      P.out[0] = P.init[0]; P.out[1] = P.init[1]; P.out[2] = P.init[2];
+      P.out[3] = -1.; P.out[4] = -1.; P.out[5] = -1.; P.out[6] = -1.; P.out[7] = 2.;
+    }
+    return;
+  }
   const double initial_cost = x_cost;
   double scale[3];
   for (int a = 0; a < 3; ++a) scale[a] = 1. / (1. + sqrt(H[a][a]));
@@ -280,7 +420,7 @@ Ceres2DKernel(const Ceres2DProblem* __restrict__ problems) {
       candidate[a] = x[a] + delta[a];
     }
     double candidate_cost, cg[3], cH[3][3];
-    Evaluate(P, candidate, scratch, &candidate_cost, cg, cH);
+    if (!Evaluate<kTsdf>(P, candidate, scratch, &candidate_cost, cg, cH)) candidate_cost = DBL_MAX;
 
     const double step_norm = sqrt(delta[0] * delta[0] + delta[1] * delta[1] + delta[2] * delta[2]);
     if (step_norm <= kParameterTolerance * (x_norm + kParameterTolerance)) { termination = 0; break; }
@@ -290,7 +430,10 @@ Ceres2DKernel(const Ceres2DProblem* __restrict__ problems) {
     const double historical_relative_decrease =
         (reference_cost - candidate_cost) /
         (accumulated_reference_model_cost_change + model_cost_change);
-    const double relative_decrease = fmax(relative_decrease_now, historical_relative_decrease);
+    // A failed candidate evaluation is never a successful step (StepQuality: lowest()).
+    const double relative_decrease = candidate_cost >= DBL_MAX
+                                         ? -DBL_MAX
+                                         : fmax(relative_decrease_now, historical_relative_decrease);
     if (relative_decrease > kMinRelativeDecrease) {
       for (int a = 0; a < 3; ++a) {
         x[a] = candidate[a];
@@ -343,9 +486,52 @@ Ceres2DKernel(const Ceres2DProblem* __restrict__ problems) {
   }
 }
 
+// Residuals and Jacobian of TSDFMatchCostFunction2D alone (cmx_ceres2d_tsdf_residuals): S and G
+// first, then per point r = u / S and J = (a - r G) / S as the Jet division forms them.
+__global__ void __launch_bounds__(kCeresThreads)
+TsdfResidualsKernel(const Ceres2DProblem* __restrict__ problem) {
+  const Ceres2DProblem& P = *problem;
+  __shared__ double scratch[4][4];
+  const double x[3] = {P.init[0], P.init[1], P.init[2]};
+  const double c = cos(x[2]), s = sin(x[2]);
+  const double ns = static_cast<double>(P.n) * P.occupied_scaling;
+  double acc[4] = {0., 0., 0., 0.};
+  for (int i = threadIdx.x; i < P.n; i += kCeresThreads) {
+    Jet3 u, w;
+    TsdfPoint(P, x, c, s, ns, i, &u, &w);
+    acc[0] += w.a; acc[1] += w.v[0]; acc[2] += w.v[1]; acc[3] += w.v[2];
+  }
+  const int wave = threadIdx.x >> 6;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const double t = WaveSumF64(acc[k]);
+    if ((threadIdx.x & 63) == 0) scratch[wave][k] = t;
+  }
+  __syncthreads();
+  double total[4];
+#pragma unroll
+  for (int k = 0; k < 4; ++k)
+    total[k] = ((scratch[0][k] + scratch[1][k]) + scratch[2][k]) + scratch[3][k];
+  // out: [0] valid, [1, 1 + n) residuals, [1 + n, 1 + 4n) Jacobian rows.
+  if (threadIdx.x == 0) P.out[0] = total[0] == 0. ? 0. : 1.;
+  if (total[0] == 0.) return;
+  const double inv = 1.0 / total[0];
+  for (int i = threadIdx.x; i < P.n; i += kCeresThreads) {
+    Jet3 u, w;
+    TsdfPoint(P, x, c, s, ns, i, &u, &w);
+    const double r = u.a * inv;
+    P.out[1 + i] = r;
+    for (int k = 0; k < 3; ++k) P.out[1 + P.n + 3 * i + k] = (u.v[k] - r * total[1 + k]) * inv;
+  }
+}
+
 struct RefineItem {
   const uint16_t* device_cells;     // grid already in HBM, or null with host_cells
   const uint16_t* host_cells;
+  const uint16_t* device_weights;   // TSDF: weight plane in HBM, or null with host_weights
+  const uint16_t* host_weights;
+  int tsdf;                         // 1: TSDF2D (cells = tsd plane, limits' cost range = +-truncation)
+  float max_weight;
   cmx_grid2d_limits limits;
   double target[2];
   cmx_pose2d initial;
@@ -368,29 +554,43 @@ void RefineBatch(const cmx_ceres2d_options* options, const RefineItem* items, in
                  cmx_ceres_summary* summaries) {
   CheckOptions(options);
   CMX_REQUIRE(items && num >= 1 && poses, "null argument");
-  CMX_REQUIRE(host_xyz != nullptr && n >= 1 && n <= (1 << 24), "bad point cloud");
+  const bool tsdf = items[0].tsdf != 0;
+  // A TSDF takes an empty cloud: S == 0 then fails the initial evaluation, as in the reference.
+  CMX_REQUIRE((host_xyz != nullptr || (tsdf && n == 0)) && n >= (tsdf ? 0 : 1) && n <= (1 << 24),
+              "bad point cloud");
   WorkspaceLease ws(device);
   // Staging: problems | cloud | host grids.
   const auto align = [](size_t v) { return (v + 255) & ~static_cast<size_t>(255); };
   size_t bytes = align(sizeof(Ceres2DProblem) * num);
   const size_t off_xyz = bytes;
   bytes += align(12 * static_cast<size_t>(n));
-  std::vector<size_t> off_cells(num, 0);
+  std::vector<size_t> off_cells(num, 0), off_weights(num, 0);
   for (int p = 0; p < num; ++p) {
     const cmx_grid2d_limits& lim = items[p].limits;
     CMX_REQUIRE(lim.resolution > 0. && lim.num_x_cells >= 1 && lim.num_y_cells >= 1,
                 "bad map limits");
     CMX_REQUIRE(items[p].device_cells || items[p].host_cells, "null grid");
+    CMX_REQUIRE((items[p].tsdf != 0) == tsdf, "mixed grid types in one batch");
+    if (tsdf) {
+      CMX_REQUIRE(lim.max_correspondence_cost > 0.f && items[p].max_weight > 0.f,
+                  "bad TSDF ranges");
+      CMX_REQUIRE(items[p].device_weights || items[p].host_weights, "null weight plane");
+    }
+    const size_t plane = align(2 * static_cast<size_t>(lim.num_x_cells) * lim.num_y_cells);
     if (!items[p].device_cells) {
       off_cells[p] = bytes;
-      bytes += align(2 * static_cast<size_t>(lim.num_x_cells) * lim.num_y_cells);
+      bytes += plane;
+    }
+    if (tsdf && !items[p].device_weights) {
+      off_weights[p] = bytes;
+      bytes += plane;
     }
   }
   char* h_in = ws->pinned[0].ReserveAs<char>(bytes);
   char* d_in = ws->dev[0].ReserveAs<char>(bytes);
   double* d_out = ws->dev[1].ReserveAs<double>(8 * static_cast<size_t>(num));
   double* h_out = ws->pinned[1].ReserveAs<double>(8 * static_cast<size_t>(num));
-  std::memcpy(h_in + off_xyz, host_xyz, 12 * static_cast<size_t>(n));
+  if (n > 0) std::memcpy(h_in + off_xyz, host_xyz, 12 * static_cast<size_t>(n));
   Ceres2DProblem* h_prob = reinterpret_cast<Ceres2DProblem*>(h_in);
   for (int p = 0; p < num; ++p) {
     const RefineItem& it = items[p];
@@ -402,6 +602,14 @@ void RefineBatch(const cmx_ceres2d_options* options, const RefineItem* items, in
                   2 * static_cast<size_t>(it.limits.num_x_cells) * it.limits.num_y_cells);
       P.cells = reinterpret_cast<const uint16_t*>(d_in + off_cells[p]);
     }
+    if (tsdf && it.device_weights) {
+      P.weights = it.device_weights;
+    } else if (tsdf) {
+      std::memcpy(h_in + off_weights[p], it.host_weights,
+                  2 * static_cast<size_t>(it.limits.num_x_cells) * it.limits.num_y_cells);
+      P.weights = reinterpret_cast<const uint16_t*>(d_in + off_weights[p]);
+    }
+    P.max_weight = it.max_weight;
     P.nx = it.limits.num_x_cells; P.ny = it.limits.num_y_cells;
     P.res = it.limits.resolution; P.max_x = it.limits.max_x; P.max_y = it.limits.max_y;
     P.min_cc = it.limits.min_correspondence_cost; P.max_cc = it.limits.max_correspondence_cost;
@@ -419,7 +627,12 @@ void RefineBatch(const cmx_ceres2d_options* options, const RefineItem* items, in
     h_prob[p] = P;
   }
   SmallCopyAsync(d_in, h_in, bytes, /*to_device=*/true, ws->stream);
-  Ceres2DKernel<<<num, kCeresThreads, 0, ws->stream>>>(reinterpret_cast<const Ceres2DProblem*>(d_in));
+  const Ceres2DProblem* d_prob = reinterpret_cast<const Ceres2DProblem*>(d_in);
+  if (tsdf) {
+    Ceres2DKernel<true><<<num, kCeresThreads, 0, ws->stream>>>(d_prob);
+  } else {
+    Ceres2DKernel<false><<<num, kCeresThreads, 0, ws->stream>>>(d_prob);
+  }
   CMX_HIP(hipGetLastError());
   SmallCopyAsync(h_out, d_out, 64 * static_cast<size_t>(num), /*to_device=*/false, ws->stream);
   CMX_HIP(hipStreamSynchronize(ws->stream));
@@ -434,6 +647,85 @@ void RefineBatch(const cmx_ceres2d_options* options, const RefineItem* items, in
       summaries[p].termination = static_cast<int32_t>(o[7]);
       summaries[p].reserved = 0;
     }
+  }
+}
+
+// A host TSDF2D's item: the planes are uploaded with the call.
+RefineItem HostTsdfItem(const cmx_grid2d_limits* limits, const uint16_t* tsd_cells,
+                        const uint16_t* weight_cells, float truncation_distance,
+                        float max_weight) {
+  CMX_REQUIRE(limits && tsd_cells && weight_cells, "null argument");
+  CMX_REQUIRE(truncation_distance > 0.f && max_weight > 0.f, "bad TSDF ranges");
+  CMX_REQUIRE(limits->resolution > 0. && limits->num_x_cells >= 1 && limits->num_y_cells >= 1,
+              "bad map limits");
+  RefineItem item{};
+  item.host_cells = tsd_cells;
+  item.host_weights = weight_cells;
+  item.tsdf = 1;
+  item.max_weight = max_weight;
+  item.limits = *limits;
+  // Grid2D(limits, -truncation_distance, truncation_distance) (tsdf_2d.cc:25-26)
+  item.limits.min_correspondence_cost = -truncation_distance;
+  item.limits.max_correspondence_cost = truncation_distance;
+  return item;
+}
+
+// A resident TSDF2D's item: the planes are read where they lie.
+RefineItem ResidentTsdfItem(const cmx_tsdf2d* grid, int* device) {
+  CMX_REQUIRE(grid, "null grid");
+  RefineItem item{};
+  item.tsdf = 1;
+  Tsdf2DDevicePlanes(grid, &item.limits, &item.device_cells, &item.device_weights,
+                     &item.max_weight, device);
+  return item;
+}
+
+void TsdfResiduals(const RefineItem& it, double scaling, const double pose[3],
+                   const float* host_xyz, int n, int device, double* residuals,
+                   double* jacobian, int32_t* valid) {
+  CMX_REQUIRE(pose && valid && n >= 0 && n <= (1 << 24), "bad argument");
+  CMX_REQUIRE(n == 0 || (host_xyz && residuals && jacobian), "null argument");
+  const cmx_grid2d_limits& lim = it.limits;
+  CMX_REQUIRE(lim.resolution > 0. && lim.num_x_cells >= 1 && lim.num_y_cells >= 1,
+              "bad map limits");
+  WorkspaceLease ws(device);
+  const auto align = [](size_t v) { return (v + 255) & ~static_cast<size_t>(255); };
+  const size_t plane = align(2 * static_cast<size_t>(lim.num_x_cells) * lim.num_y_cells);
+  const size_t off_xyz = align(sizeof(Ceres2DProblem));
+  const size_t off_cells = off_xyz + align(12 * static_cast<size_t>(n));
+  const size_t bytes = off_cells + 2 * plane;
+  const size_t out_count = 1 + 4 * static_cast<size_t>(n);
+  char* h_in = ws->pinned[0].ReserveAs<char>(bytes);
+  char* d_in = ws->dev[0].ReserveAs<char>(bytes);
+  double* d_out = ws->dev[1].ReserveAs<double>(out_count);
+  double* h_out = ws->pinned[1].ReserveAs<double>(out_count);
+  if (n > 0) std::memcpy(h_in + off_xyz, host_xyz, 12 * static_cast<size_t>(n));
+  const size_t cell_bytes = 2 * static_cast<size_t>(lim.num_x_cells) * lim.num_y_cells;
+  std::memcpy(h_in + off_cells, it.host_cells, cell_bytes);
+  std::memcpy(h_in + off_cells + plane, it.host_weights, cell_bytes);
+  Ceres2DProblem P{};
+  P.cells = reinterpret_cast<const uint16_t*>(d_in + off_cells);
+  P.weights = reinterpret_cast<const uint16_t*>(d_in + off_cells + plane);
+  P.nx = lim.num_x_cells; P.ny = lim.num_y_cells;
+  P.res = lim.resolution; P.max_x = lim.max_x; P.max_y = lim.max_y;
+  P.min_cc = lim.min_correspondence_cost; P.max_cc = lim.max_correspondence_cost;
+  P.max_weight = it.max_weight;
+  P.xyz = reinterpret_cast<const float*>(d_in + off_xyz);
+  P.n = n;
+  P.init[0] = pose[0]; P.init[1] = pose[1]; P.init[2] = pose[2];
+  P.occupied_scaling = scaling;
+  P.out = d_out;
+  std::memcpy(h_in, &P, sizeof(P));
+  SmallCopyAsync(d_in, h_in, bytes, /*to_device=*/true, ws->stream);
+  TsdfResidualsKernel<<<1, kCeresThreads, 0, ws->stream>>>(
+      reinterpret_cast<const Ceres2DProblem*>(d_in));
+  CMX_HIP(hipGetLastError());
+  SmallCopyAsync(h_out, d_out, 8 * out_count, /*to_device=*/false, ws->stream);
+  CMX_HIP(hipStreamSynchronize(ws->stream));
+  *valid = h_out[0] != 0. ? 1 : 0;
+  if (*valid) {
+    std::memcpy(residuals, h_out + 1, 8 * static_cast<size_t>(n));
+    std::memcpy(jacobian, h_out + 1 + n, 24 * static_cast<size_t>(n));
   }
 }
 
@@ -520,6 +812,100 @@ cmx_status cmx_fast2d_refine_batch(const cmx_ceres2d_options* options,
         if (summaries) summaries[idx[k]] = sums[k];
       }
     }
+  });
+}
+
+cmx_status cmx_ceres2d_match_tsdf(const cmx_ceres2d_options* options,
+                                  const cmx_grid2d_limits* limits, const uint16_t* tsd_cells,
+                                  const uint16_t* weight_cells, float truncation_distance,
+                                  float max_weight, const double* target_translation_xy,
+                                  const cmx_pose2d* initial_pose_estimate,
+                                  const float* point_cloud_xyz, int32_t num_points, int32_t device,
+                                  cmx_pose2d* pose_estimate, cmx_ceres_summary* summary) {
+  return Guard([&] {
+    CMX_REQUIRE(target_translation_xy && initial_pose_estimate && pose_estimate, "null argument");
+    cmx::RefineItem item = cmx::HostTsdfItem(limits, tsd_cells, weight_cells, truncation_distance,
+                                             max_weight);
+    item.target[0] = target_translation_xy[0];
+    item.target[1] = target_translation_xy[1];
+    item.initial = *initial_pose_estimate;
+    cmx::RefineBatch(options, &item, 1, point_cloud_xyz, num_points, device, pose_estimate, summary);
+  });
+}
+
+cmx_status cmx_ceres2d_match_tsdf_grid(const cmx_ceres2d_options* options, const cmx_tsdf2d* grid,
+                                       const double* target_translation_xy,
+                                       const cmx_pose2d* initial_pose_estimate,
+                                       const float* point_cloud_xyz, int32_t num_points,
+                                       cmx_pose2d* pose_estimate, cmx_ceres_summary* summary) {
+  return Guard([&] {
+    CMX_REQUIRE(grid && target_translation_xy && initial_pose_estimate && pose_estimate,
+                "null argument");
+    int device = 0;
+    cmx::RefineItem item = cmx::ResidentTsdfItem(grid, &device);
+    item.target[0] = target_translation_xy[0];
+    item.target[1] = target_translation_xy[1];
+    item.initial = *initial_pose_estimate;
+    cmx::RefineBatch(options, &item, 1, point_cloud_xyz, num_points, device, pose_estimate, summary);
+  });
+}
+
+cmx_status cmx_ceres2d_refine_batch_tsdf(const cmx_ceres2d_options* options,
+                                         const cmx_tsdf2d* const* grids, int32_t num_grids,
+                                         const int32_t* found,
+                                         const cmx_pose2d* pose_estimates_in,
+                                         const float* point_cloud_xyz, int32_t num_points,
+                                         cmx_pose2d* pose_estimates_out,
+                                         cmx_ceres_summary* summaries) {
+  return Guard([&] {
+    CMX_REQUIRE(grids && num_grids >= 1 && pose_estimates_in && pose_estimates_out,
+                "null argument");
+    // As cmx_fast2d_refine_batch: one launch per device the grids live on.
+    std::map<int, std::vector<int>> by_device;
+    std::vector<cmx::RefineItem> all(num_grids);
+    for (int p = 0; p < num_grids; ++p) {
+      CMX_REQUIRE(grids[p], "null grid handle");
+      int device = 0;
+      all[p] = cmx::ResidentTsdfItem(grids[p], &device);
+      by_device[device].push_back(p);
+    }
+    for (const auto& group : by_device) {
+      const std::vector<int>& idx = group.second;
+      const int m = static_cast<int>(idx.size());
+      std::vector<cmx::RefineItem> items(m);
+      for (int k = 0; k < m; ++k) {
+        const int p = idx[k];
+        cmx::RefineItem& it = items[k];
+        it = all[p];
+        // constraint_builder_2d.cc:245-249: Match(pose_estimate.translation(), pose_estimate, ...)
+        it.initial = pose_estimates_in[p];
+        it.target[0] = pose_estimates_in[p].x;
+        it.target[1] = pose_estimates_in[p].y;
+        it.skip = found && !found[p] ? 1 : 0;
+      }
+      std::vector<cmx_pose2d> poses(m);
+      std::vector<cmx_ceres_summary> sums(m);
+      cmx::RefineBatch(options, items.data(), m, point_cloud_xyz, num_points, group.first,
+                       poses.data(), summaries ? sums.data() : nullptr);
+      for (int k = 0; k < m; ++k) {
+        pose_estimates_out[idx[k]] = poses[k];
+        if (summaries) summaries[idx[k]] = sums[k];
+      }
+    }
+  });
+}
+
+cmx_status cmx_ceres2d_tsdf_residuals(const cmx_grid2d_limits* limits, const uint16_t* tsd_cells,
+                                      const uint16_t* weight_cells, float truncation_distance,
+                                      float max_weight, double residual_scaling_factor,
+                                      const double* pose, const float* point_cloud_xyz,
+                                      int32_t num_points, int32_t device, double* residuals,
+                                      double* jacobian, int32_t* valid) {
+  return Guard([&] {
+    const cmx::RefineItem item = cmx::HostTsdfItem(limits, tsd_cells, weight_cells,
+                                                   truncation_distance, max_weight);
+    cmx::TsdfResiduals(item, residual_scaling_factor, pose, point_cloud_xyz, num_points, device,
+                       residuals, jacobian, valid);
   });
 }
 

@@ -34,6 +34,17 @@ __device__ __forceinline__ int LRoundF32(float x) {
   return static_cast<int>(t);
 }
 
+// ValueConversionTables (mapping/value_conversion_tables.cc:29-52): value 0 ->
+// `unknown`, [1, 32767] -> [lower, upper]; bit 15 (update marker) is masked.  Shared by the
+// TSDF kernels of rt_2d.hip (real-time scores) and ceres_2d.hip (the TSDF match cost).
+__device__ __forceinline__ float BoundedValue(unsigned raw, float unknown, float lower,
+                                              float upper) {
+  const unsigned v = raw & 32767u;
+  if (v == 0) return unknown;
+  const float scale = (upper - lower) / 32766.f;
+  return static_cast<float>(v) * scale + (lower - scale);
+}
+
 // Pointers read from descriptor structs in memory are "generic" to the compiler, which
 // then emits flat_load (LDS-aperture check, vmcnt and lgkmcnt both tied up, no partial
 // waits).  All such pointers are HBM addresses: say so, and the loads become global_load.

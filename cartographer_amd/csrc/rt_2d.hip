@@ -62,16 +62,6 @@ struct Rt2DParams {
   int prep_blocks;           // num_scans + blocks of the grid expansion
 };
 
-// ValueConversionTables (mapping/value_conversion_tables.cc:29-52): value 0 ->
-// `unknown`, [1, 32767] -> [lower, upper]; bit 15 (update marker) is masked.
-__device__ __forceinline__ float BoundedValue(unsigned raw, float unknown, float lower,
-                                              float upper) {
-  const unsigned v = raw & 32767u;
-  if (v == 0) return unknown;
-  const float scale = (upper - lower) / 32766.f;
-  return static_cast<float>(v) * scale + (lower - scale);
-}
-
 // The (term, weight) a TSDF cell contributes (real_time_..._2d.cc:38-59,
 // mapping/internal/2d/tsdf_2d.cc:88-98, tsd_value_converter.cc:22-33).
 __device__ __forceinline__ float2 TsdfTerm(float tsd, float weight, float max_tsd) {

@@ -363,6 +363,24 @@ TsdfParams MakeParams(const cmx_tsdf2d& g) {
 }
 
 }  // namespace
+
+// For ceres_2d.hip: the planes and ranges of a resident grid.
+void Tsdf2DDevicePlanes(const cmx_tsdf2d* grid, cmx_grid2d_limits* limits, const uint16_t** tsd,
+                        const uint16_t** weight, float* max_weight, int* device) {
+  limits->resolution = grid->resolution;
+  limits->max_x = grid->max_x;
+  limits->max_y = grid->max_y;
+  limits->num_x_cells = grid->nx;
+  limits->num_y_cells = grid->ny;
+  // Grid2D(limits, -truncation_distance, truncation_distance) (tsdf_2d.cc:25-26)
+  limits->min_correspondence_cost = -grid->max_tsd;
+  limits->max_correspondence_cost = grid->max_tsd;
+  *tsd = grid->tsd;
+  *weight = grid->weight;
+  *max_weight = grid->max_weight;
+  *device = grid->device;
+}
+
 }  // namespace cmx
 
 using cmx::Guard;

@@ -360,7 +360,9 @@ def match_batch(matchers, initial_pose_estimates, match_full_submap, min_scores,
 class CeresScanMatcher2D:
     """CeresScanMatcher2D(options).Match(target_translation, initial_pose_estimate, point_cloud,
     grid) -> (pose_estimate, summary)  (ceres_scan_matcher_2d.h:44-56).  `grid` is a Grid2D or a
-    grid resident in HBM (cartographer_amd.grid_2d.ProbabilityGridOnDevice)."""
+    grid resident in HBM (cartographer_amd.grid_2d.ProbabilityGridOnDevice), refined with the
+    occupied-space cost, or a TSDF2D / TSDF2DOnDevice, refined with TSDFMatchCostFunction2D
+    (the GridType::TSDF case, ceres_scan_matcher_2d.cc:83-90)."""
 
     def __init__(self, occupied_space_weight, translation_weight, rotation_weight,
                  use_nonmonotonic_steps=False, max_num_iterations=20, device=0):
@@ -369,12 +371,25 @@ class CeresScanMatcher2D:
         self.device = device
 
     def match(self, target_translation, initial_pose_estimate, point_cloud, grid):
-        from .grid_2d import ProbabilityGridOnDevice
+        from .grid_2d import ProbabilityGridOnDevice, TSDF2DOnDevice
         xyz, n = _cloud(point_cloud)
         target = np.ascontiguousarray(target_translation, np.float64)
         init = initial_pose_estimate.to_c()
         pose, summary = Pose2d(), CeresSummary()
-        if isinstance(grid, ProbabilityGridOnDevice):
+        cloud = xyz.ctypes.data if n else None
+        if isinstance(grid, TSDF2DOnDevice):
+            check(_lib.lib().cmx_ceres2d_match_tsdf_grid(C.byref(self.options), grid._h,
+                                                         target.ctypes.data, C.byref(init),
+                                                         cloud, n, C.byref(pose),
+                                                         C.byref(summary)))
+        elif isinstance(grid, TSDF2D):
+            limits = grid.limits_c()
+            check(_lib.lib().cmx_ceres2d_match_tsdf(
+                C.byref(self.options), C.byref(limits), grid.cells.ctypes.data,
+                grid.weight_cells.ctypes.data, grid.truncation_distance, grid.max_weight,
+                target.ctypes.data, C.byref(init), cloud, n, self.device, C.byref(pose),
+                C.byref(summary)))
+        elif isinstance(grid, ProbabilityGridOnDevice):
             check(_lib.lib().cmx_ceres2d_match_grid(C.byref(self.options), grid._h,
                                                     target.ctypes.data, C.byref(init),
                                                     xyz.ctypes.data, n, C.byref(pose),
@@ -402,3 +417,41 @@ class CeresScanMatcher2D:
             xyz.ctypes.data, n, C.cast(poses_out, C.c_void_p), C.cast(summaries, C.c_void_p)))
         return ([Rigid2d(p.x, p.y, p.theta) for p in poses_out],
                 [s_.as_dict() for s_ in summaries])
+
+    def refine_batch_tsdf(self, grids, found, pose_estimates, point_cloud):
+        """The same refinement against finished TSDF submaps kept in HBM (TSDF2DOnDevice): entry
+        i refines pose_estimates[i] towards its own translation; found[i] == 0 passes through.
+        One launch per device the grids live on."""
+        num = len(grids)
+        xyz, n = _cloud(point_cloud)
+        handles = (C.c_void_p * num)(*[g._h for g in grids])
+        found = None if found is None else np.ascontiguousarray(found, np.int32)
+        poses_in = (Pose2d * num)(*[p.to_c() for p in pose_estimates])
+        poses_out = (Pose2d * num)()
+        summaries = (CeresSummary * num)()
+        check(_lib.lib().cmx_ceres2d_refine_batch_tsdf(
+            C.byref(self.options), handles, num, None if found is None else found.ctypes.data,
+            C.cast(poses_in, C.c_void_p), xyz.ctypes.data if n else None, n,
+            C.cast(poses_out, C.c_void_p), C.cast(summaries, C.c_void_p)))
+        return ([Rigid2d(p.x, p.y, p.theta) for p in poses_out],
+                [s_.as_dict() for s_ in summaries])
+
+
+def tsdf_match_residuals(grid, residual_scaling_factor, pose, point_cloud, device=0):
+    """TSDFMatchCostFunction2D::Evaluate (tsdf_match_cost_function_2d.cc:40-66) on a host TSDF2D
+    at `pose` (x, y, theta): (valid, residuals [n], jacobian [n, 3]).  `valid` is False where the
+    reference's functor returns false (every interpolated weight 0); the arrays are then None."""
+    xyz, n = _cloud(point_cloud)
+    limits = grid.limits_c()
+    pose = np.ascontiguousarray(pose, np.float64).reshape(3)
+    residuals = np.zeros(max(n, 1), np.float64)
+    jacobian = np.zeros((max(n, 1), 3), np.float64)
+    valid = C.c_int32()
+    check(_lib.lib().cmx_ceres2d_tsdf_residuals(
+        C.byref(limits), grid.cells.ctypes.data, grid.weight_cells.ctypes.data,
+        grid.truncation_distance, grid.max_weight, residual_scaling_factor, pose.ctypes.data,
+        xyz.ctypes.data if n else None, n, device, residuals.ctypes.data, jacobian.ctypes.data,
+        C.byref(valid)))
+    if not valid.value:
+        return False, None, None
+    return True, residuals[:n].copy(), jacobian[:n].copy()

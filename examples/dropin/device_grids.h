@@ -22,6 +22,15 @@ class DeviceGrid2DView {
   ~DeviceGrid2DView() = default;
 };
 
+// The same for a TSDF2D whose planes live in HBM (a cmx_tsdf2d): the adapters take the
+// *_tsdf_grid entry points.
+class DeviceTsdf2DView {
+ public:
+  virtual const cmx_tsdf2d* device_tsdf() const = 0;
+ protected:
+  ~DeviceTsdf2DView() = default;
+};
+
 namespace internal {
 struct Registry3D {
   std::mutex mutex;

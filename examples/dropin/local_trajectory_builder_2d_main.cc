@@ -3,6 +3,8 @@
 // data collation, pose extrapolation, gravity alignment, voxel filtering, the real-time
 // correlative matcher, the Ceres matcher, the motion filter and submap insertion, scan after scan.
 //
+// With -DDROPIN_TSDF the submaps are TSDF2Ds (grid_type = "TSDF", the lua TSDF inserter
+// defaults; local_trajectory_builder_2d_tsdf_{reference,mi355x,resident_mi355x}).
 // The same file is linked twice (Makefile):
 //   _build/local_trajectory_builder_2d_reference  with the reference's own
 //       real_time_correlative_scan_matcher_2d.cc, ceres_scan_matcher_2d.cc (over the stand-in
@@ -113,7 +115,15 @@ proto::LocalTrajectoryBuilderOptions2D Options() {
   rt->set_translation_delta_cost_weight(1e-1);
   rt->set_rotation_delta_cost_weight(1e-1);
   auto* ceres = o.mutable_ceres_scan_matcher_options();
+#ifdef DROPIN_TSDF
+  // TSDF residuals are weighted-mean signed distances in metres, below the 0.3 m truncation: with
+  // lua's occupied_space_weight of 1 the translation / rotation priors (10 / 40) outweigh them, the
+  // scans stay at the extrapolated pose and the drive falls behind the truth by metres.  10 keeps
+  // the TSDF drive within 4 cm (both TSDF builds use the same value).
+  ceres->set_occupied_space_weight(10.);
+#else
   ceres->set_occupied_space_weight(1.);
+#endif
   ceres->set_translation_weight(10.);
   ceres->set_rotation_weight(40.);
   ceres->mutable_ceres_solver_options()->set_use_nonmonotonic_steps(false);
@@ -130,9 +140,25 @@ proto::LocalTrajectoryBuilderOptions2D Options() {
       ->set_imu_gravity_time_constant(10.);
   auto* submaps = o.mutable_submaps_options();
   submaps->set_num_range_data(8);
+#ifdef DROPIN_TSDF
+  // grid_type = "TSDF" with trajectory_builder_2d.lua's TSDF inserter defaults (:100-112)
+  submaps->mutable_grid_options_2d()->set_grid_type(proto::GridOptions2D_GridType_TSDF);
+  submaps->mutable_grid_options_2d()->set_resolution(0.05);
+  auto* tsdf = submaps->mutable_tsdf_range_data_inserter_options_2d();
+  tsdf->set_truncation_distance(0.3);
+  tsdf->set_maximum_weight(10.);
+  tsdf->set_update_free_space(false);
+  tsdf->mutable_normal_estimation_options()->set_num_normal_samples(4);
+  tsdf->mutable_normal_estimation_options()->set_sample_radius(0.5);
+  tsdf->set_project_sdf_distance_to_scan_normal(true);
+  tsdf->set_update_weight_range_exponent(0);
+  tsdf->set_update_weight_angle_scan_normal_to_ray_kernel_bandwidth(0.5);
+  tsdf->set_update_weight_distance_cell_to_hit_kernel_bandwidth(0.5);
+#else
   submaps->mutable_grid_options_2d()->set_grid_type(
       proto::GridOptions2D_GridType_PROBABILITY_GRID);
   submaps->mutable_grid_options_2d()->set_resolution(0.05);
+#endif
   auto* inserter = submaps->mutable_probability_grid_range_data_inserter_options_2d();
   inserter->set_hit_probability(0.55);
   inserter->set_miss_probability(0.49);

@@ -48,7 +48,8 @@ struct CellAccess : Grid2D {
 // (host cells: a grid resident in HBM -- device_grids.h -- hands out an all-zero host image;
 // Match() looks for the resident grid first, a path without a resident form stops here)
 const std::vector<uint16>& CellsOf(const Grid2D& grid) {
-  if (dynamic_cast<const dropin::DeviceGrid2DView*>(&grid) != nullptr) {
+  if (dynamic_cast<const dropin::DeviceGrid2DView*>(&grid) != nullptr ||
+      dynamic_cast<const dropin::DeviceTsdf2DView*>(&grid) != nullptr) {
     std::fprintf(stderr, "Check failed: a grid resident in HBM reached a host-upload path of the "
                          "real-time matcher adapters (real_time_matchers_mi355x.cc)\n");
     std::abort();
@@ -110,6 +111,15 @@ double RealTimeCorrelativeScanMatcher2D::Match(const transform::Rigid2d& initial
     CheckOk(cmx_rt2d_match_grid(&o, resident->device_grid(), &init, xyz.data(),
                                 static_cast<int32_t>(point_cloud.size()), &score, &pose, nullptr),
             "cmx_rt2d_match_grid");
+    *pose_estimate = transform::Rigid2d({pose.x, pose.y}, pose.theta);
+    return score;
+  }
+  if (const auto* resident = dynamic_cast<const dropin::DeviceTsdf2DView*>(&grid)) {
+    // a TSDF submap in HBM: both planes are read in place
+    CheckOk(cmx_rt2d_match_tsdf_grid(&o, resident->device_tsdf(), &init, xyz.data(),
+                                     static_cast<int32_t>(point_cloud.size()), &score, &pose,
+                                     nullptr),
+            "cmx_rt2d_match_tsdf_grid");
     *pose_estimate = transform::Rigid2d({pose.x, pose.y}, pose.theta);
     return score;
   }

@@ -32,7 +32,8 @@ struct CellAccess : Grid2D {
 // which must never be uploaded in its place: every caller below looks for the resident grid
 // first, and a path that has no resident form stops here instead of matching against nothing)
 const uint16_t* CellsOf(const Grid2D& grid) {
-  if (dynamic_cast<const dropin::DeviceGrid2DView*>(&grid) != nullptr) {
+  if (dynamic_cast<const dropin::DeviceGrid2DView*>(&grid) != nullptr ||
+      dynamic_cast<const dropin::DeviceTsdf2DView*>(&grid) != nullptr) {
     std::fprintf(stderr, "Check failed: a grid resident in HBM reached a host-upload path of the "
                          "2D scan matcher adapters (scan_matchers_2d_mi355x.cc)\n");
     std::abort();
@@ -145,6 +146,22 @@ void CeresScanMatcher2D::Match(const Eigen::Vector2d& target_translation,
     CheckOk(cmx_ceres2d_match_grid(&o, resident->device_grid(), target, &init, xyz.data(),
                                    static_cast<int32_t>(point_cloud.size()), &pose, &s),
             "cmx_ceres2d_match_grid");
+  } else if (const auto* tsdf = dynamic_cast<const dropin::DeviceTsdf2DView*>(&grid)) {
+    CheckOk(cmx_ceres2d_match_tsdf_grid(&o, tsdf->device_tsdf(), target, &init, xyz.data(),
+                                        static_cast<int32_t>(point_cloud.size()), &pose, &s),
+            "cmx_ceres2d_match_tsdf_grid");
+  } else if (grid.GetGridType() == GridType::TSDF) {
+    // TSDFMatchCostFunction2D (.cc:83-90).  The weight plane is private to TSDF2D; the virtual
+    // ToProto() (tsdf_2d.cc:113-124) is its public image, as in real_time_matchers_mi355x.cc.
+    const mapping::proto::Grid2D planes = grid.ToProto();
+    std::vector<uint16_t> weights;
+    weights.reserve(planes.tsdf_2d().weight_cells_size());
+    for (const auto w : planes.tsdf_2d().weight_cells()) weights.push_back(static_cast<uint16_t>(w));
+    CheckOk(cmx_ceres2d_match_tsdf(&o, &limits, CellsOf(grid), weights.data(),
+                                   planes.tsdf_2d().truncation_distance(),
+                                   planes.tsdf_2d().max_weight(), target, &init, xyz.data(),
+                                   static_cast<int32_t>(point_cloud.size()), Device(), &pose, &s),
+            "cmx_ceres2d_match_tsdf");
   } else {
     CheckOk(cmx_ceres2d_match(&o, &limits, CellsOf(grid), target, &init,
                               xyz.data(), static_cast<int32_t>(point_cloud.size()), Device(), &pose,

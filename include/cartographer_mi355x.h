@@ -18,6 +18,10 @@
  *                                  (node, submap) searches, constraints/constraint_builder_2d.cc:97-137
  *   cmx_ceres2d_match, cmx_ceres2d_match_grid, cmx_fast2d_refine_batch
  *                                  CeresScanMatcher2D::Match, SM2/ceres_scan_matcher_2d.cc:63-107
+ *   cmx_ceres2d_match_tsdf, cmx_ceres2d_match_tsdf_grid, cmx_ceres2d_refine_batch_tsdf
+ *                                  the same method on a TSDF2D (.cc:83-90, the GridType::TSDF case)
+ *   cmx_ceres2d_tsdf_residuals     TSDFMatchCostFunction2D::Evaluate,
+ *                                  SM2/tsdf_match_cost_function_2d.cc:40-66
  *   cmx_ceres3d_match, cmx_fast3d_refine_batch
  *                                  CeresScanMatcher3D::Match, SM3/ceres_scan_matcher_3d.cc:90-156
  *   cmx_rt3d_match                 RealTimeCorrelativeScanMatcher3D::Match
@@ -384,12 +388,63 @@ cmx_status cmx_ceres2d_match_grid(const cmx_ceres2d_options* options, const cmx_
  * 245-249) for the results of cmx_fast2d_match_batch, one launch for the whole batch, each
  * against the grid its matcher keeps in HBM: entry i refines pose_estimates_in[i] with target
  * translation pose_estimates_in[i].{x,y}; entries with found[i] == 0 (found may be NULL) are
- * passed through. */
+ * passed through.  The matchers' grids are probability grids, refined with the occupied-space
+ * cost; callers with TSDF submaps use cmx_ceres2d_refine_batch_tsdf. */
 cmx_status cmx_fast2d_refine_batch(const cmx_ceres2d_options* options,
                                    const cmx_fast2d* const* matchers, int32_t num_matchers,
                                    const int32_t* found, const cmx_pose2d* pose_estimates_in,
                                    const float* point_cloud_xyz, int32_t num_points,
                                    cmx_pose2d* pose_estimates_out, cmx_ceres_summary* summaries);
+
+/* ---- Ceres refinement on a TSDF2D ---------------------------------------------------------- */
+/* CeresScanMatcher2D::Match with grid_type = "TSDF" (SM2/ceres_scan_matcher_2d.cc:83-90): the
+ * point residuals are TSDFMatchCostFunction2D (SM2/tsdf_match_cost_function_2d.cc:40-66,
+ * bilinear InterpolatedTSDF2D, SM2/interpolated_tsdf_2d.h:42-125), r_i = n s C_i w_i / sum_j w_j
+ * with s = occupied_space_weight / sqrt(n); translation / rotation delta residuals and solver as
+ * in cmx_ceres2d_match.  The planes and ranges are those of cmx_rt2d_match_tsdf.
+ *   - When every interpolated weight is 0 the cost function fails.  A failed initial evaluation
+ *     ends the solve with termination 2 (FAILURE): the pose is the initial estimate and the
+ *     summary keeps ceres::Solver::Summary's initial values (costs -1, both step counts -1).
+ *     A failed candidate evaluation costs DBL_MAX and is an unsuccessful step.
+ *   - num_points == 0 is accepted (point_cloud_xyz may then be NULL): the reference's functor
+ *     fails on an empty cloud, so the solve ends with FAILURE as above.
+ *   cmx_ceres2d_match_tsdf        the planes are uploaded for the call
+ *   cmx_ceres2d_match_tsdf_grid   the planes of a resident grid are read in place:
+ *                                 LocalTrajectoryBuilder2D's pair after cmx_rt2d_match_tsdf_grid
+ *   cmx_ceres2d_refine_batch_tsdf ConstraintBuilder2D's refinement against finished TSDF
+ *                                 submaps, the contract of cmx_fast2d_refine_batch: target =
+ *                                 pose_estimates_in[i].{x,y}, found[i] == 0 passes through
+ *                                 (found may be NULL), one launch per device the grids live on
+ *   cmx_ceres2d_tsdf_residuals    TSDFMatchCostFunction2D::Evaluate at `pose` (x, y, theta) with
+ *                                 `residual_scaling_factor` = s: residuals[n] and the row-major
+ *                                 n x 3 Jacobian, *valid = 0 where the functor returns false
+ *                                 (then residuals / jacobian are not written; n == 0 gives 0),
+ *                                 kept visible for testing like cmx_rt2d_score_candidates. */
+cmx_status cmx_ceres2d_match_tsdf(const cmx_ceres2d_options* options,
+                                  const cmx_grid2d_limits* limits, const uint16_t* tsd_cells,
+                                  const uint16_t* weight_cells, float truncation_distance,
+                                  float max_weight, const double* target_translation_xy,
+                                  const cmx_pose2d* initial_pose_estimate,
+                                  const float* point_cloud_xyz, int32_t num_points, int32_t device,
+                                  cmx_pose2d* pose_estimate, cmx_ceres_summary* summary);
+cmx_status cmx_ceres2d_match_tsdf_grid(const cmx_ceres2d_options* options, const cmx_tsdf2d* grid,
+                                       const double* target_translation_xy,
+                                       const cmx_pose2d* initial_pose_estimate,
+                                       const float* point_cloud_xyz, int32_t num_points,
+                                       cmx_pose2d* pose_estimate, cmx_ceres_summary* summary);
+cmx_status cmx_ceres2d_refine_batch_tsdf(const cmx_ceres2d_options* options,
+                                         const cmx_tsdf2d* const* grids, int32_t num_grids,
+                                         const int32_t* found,
+                                         const cmx_pose2d* pose_estimates_in,
+                                         const float* point_cloud_xyz, int32_t num_points,
+                                         cmx_pose2d* pose_estimates_out,
+                                         cmx_ceres_summary* summaries);
+cmx_status cmx_ceres2d_tsdf_residuals(const cmx_grid2d_limits* limits, const uint16_t* tsd_cells,
+                                      const uint16_t* weight_cells, float truncation_distance,
+                                      float max_weight, double residual_scaling_factor,
+                                      const double* pose, const float* point_cloud_xyz,
+                                      int32_t num_points, int32_t device, double* residuals,
+                                      double* jacobian, int32_t* valid);
 
 /* ---- CeresScanMatcher3D ------------------------------------------- */
 /* proto::CeresScanMatcherOptions3D (mapping/proto/scan_matching/ceres_scan_matcher_options_3d.proto)

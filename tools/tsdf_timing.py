@@ -12,6 +12,16 @@ in a synchronise):
                                          cmx_rt2d_match_tsdf_grid against cmx_rt2d_match_tsdf
                                          (planes uploaded per call) on a 200x200 grid
   cells_changed_per_insert_*             cells whose (tsd, weight) the insert changed (median)
+  ceres_tsdf_resident_ms / ceres_tsdf_host_planes_ms
+                                         CeresScanMatcher2D::Match on the same TSDF (lua local
+                                         options 1 / 10 / 40, 20 iterations) of one ~1000-point
+                                         room scan: cmx_ceres2d_match_tsdf_grid against
+                                         cmx_ceres2d_match_tsdf (planes uploaded per call)
+  refine_batch_tsdf_64_ms                cmx_ceres2d_refine_batch_tsdf of 64 (pose, grid) pairs
+                                         (pose_graph.lua's constraint-builder options)
+  standin_cpu_ceres_tsdf_ms              the same solve by the reference's cost function over the
+                                         STAND-IN solver of oracle/ref_shims/ceres (not Ceres), on
+                                         this host; null where the reference tree is absent
 Usage: python tools/tsdf_timing.py [--calls 60]
 """
 import argparse
@@ -36,6 +46,38 @@ def _median_ms(fn, calls, warmup=5):
         fn(k)
         times.append((time.perf_counter() - t0) * 1e3)
     return float(np.median(times))
+
+
+def _ceres_legs(out, dev, host, cloud, calls):
+    from cartographer_amd import scan_matching as sm
+    local = sm.CeresScanMatcher2D(1.0, 10.0, 40.0, False, 20)
+    init = sm.Rigid2d(0.03, -0.02, 0.015)
+    target = [init.x, init.y]
+    out["ceres_tsdf_points"] = int(cloud.shape[0])
+    out["ceres_tsdf_resident_ms"] = _median_ms(lambda k: local.match(target, init, cloud, dev),
+                                               calls)
+    out["ceres_tsdf_host_planes_ms"] = _median_ms(lambda k: local.match(target, init, cloud, host),
+                                                  calls)
+    a, b = local.match(target, init, cloud, dev), local.match(target, init, cloud, host)
+    out["ceres_tsdf_equal"] = bool(a == b)
+    out["ceres_tsdf_summary"] = a[1]
+    constraint = sm.CeresScanMatcher2D(20.0, 10.0, 1.0, True, 10)
+    rng = np.random.default_rng(3)
+    poses = [sm.Rigid2d(*rng.uniform(-0.04, 0.04, 3)) for _ in range(64)]
+    out["refine_batch_tsdf_64_ms"] = _median_ms(
+        lambda k: constraint.refine_batch_tsdf([dev] * 64, None, poses, cloud), calls)
+    # The driver compiles against the reference's headers: without the tree the leg is null
+    # (not measured); with it, any failure of the leg is an error.
+    out["standin_cpu_ceres_tsdf_ms"] = None
+    if os.path.isdir("/root/reference"):
+        import make_ceres2d_tsdf_golden as mc
+        L = mc._driver()
+        grid = (host.cells, host.weight_cells, host.resolution, host.max_x, host.max_y,
+                host.truncation_distance, host.max_weight)
+        opts = (1.0, 10.0, 40.0, 0.0, 20.0)
+        out["standin_cpu_ceres_tsdf_ms"] = _median_ms(
+            lambda k: mc.ref_match(L, grid, opts, target, [init.x, init.y, init.theta], cloud),
+            calls)
 
 
 def main():
@@ -96,6 +138,7 @@ def main():
             a, b = rt.match(init, scan, dev), rt.match(init, scan, host)
             out["rt_match_equal"] = bool(a[0] == b[0] and a[1].x == b[1].x and a[1].y == b[1].y
                                          and a[1].theta == b[1].theta)
+            _ceres_legs(out, dev, host, r, args.calls)
     out["calls"] = args.calls
     print(json.dumps(out, sort_keys=True))
 
