@@ -171,7 +171,7 @@ EXPORTED_SYMBOLS = [
     "cmx_fast2d_level_cells", "cmx_fast2d_debug_prepare", "cmx_rt3d_match", "cmx_fast3d_create",
     "cmx_fast3d_destroy", "cmx_fast3d_match", "cmx_fast3d_match_full_submap",
     "cmx_fast3d_match_batch",
-    "cmx_fast3d_level_info", "cmx_fast3d_level_cells",
+    "cmx_fast3d_level_info", "cmx_fast3d_level_cells", "cmx_fast3d_create_from_grids",
     "cmx_ceres2d_match", "cmx_ceres2d_match_grid", "cmx_fast2d_refine_batch", "cmx_ceres3d_match",
     "cmx_ceres2d_match_tsdf", "cmx_ceres2d_match_tsdf_grid", "cmx_ceres2d_refine_batch_tsdf",
     "cmx_ceres2d_tsdf_residuals",
@@ -375,6 +375,8 @@ def lib():
     L.cmx_fast3d_create.argtypes = [P(Fast3DOptions), C.c_float, C.c_int32, C.c_void_p, C.c_int64,
                                     C.c_float, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32,
                                     C.c_int32, P(C.c_void_p)]
+    L.cmx_fast3d_create_from_grids.argtypes = [P(Fast3DOptions), C.c_void_p, C.c_void_p,
+                                               C.c_void_p, C.c_int32, P(C.c_void_p)]
     L.cmx_fast3d_destroy.argtypes = [C.c_void_p]
     L.cmx_fast3d_destroy.restype = None
     L.cmx_fast3d_match.argtypes = [C.c_void_p, P(Pose3d), P(Pose3d), P(NodeData3D), C.c_float,

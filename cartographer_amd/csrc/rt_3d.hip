@@ -35,12 +35,7 @@ __global__ void ScatterVoxelsKernel(const cmx_voxel* __restrict__ voxels, long l
   if (bytes_per_cell == 2) {
     static_cast<uint16_t*>(const_cast<void*>(b.cells))[off] = v.value;
   } else {
-    // ConvertToPrecomputationGrid (SM3/precomputation_grid_3d.cc:49-62).
-    const float kMinP = 0.1f;
-    const float kMaxP = 1.f - kMinP;
-    int value = LRoundF32((ValueToProbabilityDev(v.value) - kMinP) * (255.f / (kMaxP - kMinP)));
-    value = min(max(value, 0), 255);
-    static_cast<uint8_t*>(const_cast<void*>(b.cells))[off] = static_cast<uint8_t>(value);
+    static_cast<uint8_t*>(const_cast<void*>(b.cells))[off] = PrecomputationValueDev(v.value);
   }
 }
 
@@ -1634,13 +1629,7 @@ int GridSizeOf(const cmx_voxel* voxels, int64_t n) {
   return gs;
 }
 
-void BuildBrickFromVoxels(Workspace& ws, const cmx_voxel* voxels, int64_t n, int bytes_per_cell,
-                          DeviceBrick* out) {
-  int lo[3], hi[3];
-  if (!VoxelBounds(voxels, n, lo, hi)) {
-    lo[0] = lo[1] = lo[2] = 0;
-    hi[0] = hi[1] = hi[2] = 0;
-  }
+void AllocateDenseBrick(const int lo[3], const int hi[3], int bytes_per_cell, DeviceBrick* out) {
   for (int k = 0; k < 3; ++k) {
     CMX_REQUIRE(lo[k] > -(1 << 20) && hi[k] < (1 << 20), "voxel index out of range");
   }
@@ -1654,6 +1643,17 @@ void BuildBrickFromVoxels(Workspace& ws, const cmx_voxel* voxels, int64_t n, int
   CMX_HIP(hipMalloc(&out->mem, out->bytes + 16));   // (+16: aligned 8-byte reads of the last cells)
   b.cells = out->mem;
   out->desc = b;
+}
+
+void BuildBrickFromVoxels(Workspace& ws, const cmx_voxel* voxels, int64_t n, int bytes_per_cell,
+                          DeviceBrick* out) {
+  int lo[3], hi[3];
+  if (!VoxelBounds(voxels, n, lo, hi)) {
+    lo[0] = lo[1] = lo[2] = 0;
+    hi[0] = hi[1] = hi[2] = 0;
+  }
+  AllocateDenseBrick(lo, hi, bytes_per_cell, out);
+  const Brick b = out->desc;
   CMX_HIP(hipMemsetAsync(out->mem, 0, out->bytes, ws.stream));
   if (n > 0) {
     cmx_voxel* d_vox = ws.dev[15].ReserveAs<cmx_voxel>(n);

@@ -59,6 +59,16 @@ __device__ __forceinline__ float ValueToProbabilityDev(unsigned raw) {
   return static_cast<float>(v) * scale + (kMinP - scale);
 }
 
+// ConvertToPrecomputationGrid (SM3/precomputation_grid_3d.cc:49-62): the uint8 value level 0 of
+// the precomputation stack holds for a raw HybridGrid value (0 -> 0).  Shared by the voxel-list
+// scatter (rt_3d.hip) and the crop of a resident grid (fast_3d.hip).
+__device__ __forceinline__ uint8_t PrecomputationValueDev(unsigned raw) {
+  const float kMinP = 0.1f;
+  const float kMaxP = 1.f - kMinP;
+  const int value = LRoundF32((ValueToProbabilityDev(raw) - kMinP) * (255.f / (kMaxP - kMinP)));
+  return static_cast<uint8_t>(min(max(value, 0), 255));
+}
+
 // HybridGrid::GetCellIndex (hybrid_grid.h:428-433): lround(p / resolution), f32.
 __device__ __forceinline__ int3 CellIndex3(const F3& p, float resolution) {
   return make_int3(LRoundF32(p.x / resolution), LRoundF32(p.y / resolution),
@@ -161,6 +171,8 @@ struct DeviceBrick {
 
 // Bounding box of a voxel list; false when the list is empty.
 bool VoxelBounds(const cmx_voxel* voxels, int64_t n, int lo[3], int hi[3]);
+// Allocates `out` as the dense brick over [lo, hi] (inclusive) of `bytes_per_cell`, uninitialised.
+void AllocateDenseBrick(const int lo[3], const int hi[3], int bytes_per_cell, DeviceBrick* out);
 // Uploads `voxels` and scatters them into a zeroed dense brick of `bytes_per_cell`
 // (2: raw uint16 values; 1: ConvertToPrecomputationGrid's uint8 values).
 void BuildBrickFromVoxels(Workspace& ws, const cmx_voxel* voxels, int64_t n, int bytes_per_cell,

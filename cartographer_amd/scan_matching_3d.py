@@ -265,6 +265,29 @@ class FastCorrelativeScanMatcher3D:
                                            nl, hist.ctypes.data if hist.size else None,
                                            hist.shape[0], device, C.byref(self._h)))
 
+    @classmethod
+    def from_device_grids(cls, high_grid, low_grid, rotational_scan_matcher_histogram,
+                          branch_and_bound_depth=8, full_resolution_depth=3,
+                          min_rotational_score=0.77, min_low_resolution_score=0.55,
+                          linear_xy_search_window=5.0, linear_z_search_window=1.0,
+                          angular_search_window=float(np.deg2rad(15.0))):
+        """Matcher of two grids that live in HBM (cartographer_amd.grid_3d.HybridGridOnDevice, on
+        one device): resolutions, grid_size and device come from the grids.  The matcher keeps
+        its own copies, so the grids may change or go away afterwards."""
+        self = cls.__new__(cls)
+        self.options = Fast3DOptions(branch_and_bound_depth, full_resolution_depth,
+                                     min_rotational_score, min_low_resolution_score,
+                                     linear_xy_search_window, linear_z_search_window,
+                                     angular_search_window)
+        hist = np.ascontiguousarray(rotational_scan_matcher_histogram, np.float32)
+        self.depth = branch_and_bound_depth
+        self.last_stats = None
+        self._h = C.c_void_p()
+        check(_lib.lib().cmx_fast3d_create_from_grids(
+            C.byref(self.options), high_grid._h, low_grid._h,
+            hist.ctypes.data if hist.size else None, hist.shape[0], C.byref(self._h)))
+        return self
+
     def __del__(self):
         if getattr(self, "_h", None):
             _lib.lib().cmx_fast3d_destroy(self._h)

@@ -8,6 +8,7 @@
 #include <string>
 
 #include "cartographer/mapping/3d/hybrid_grid.h"
+#include "../device_grids.h"
 
 namespace cartographer {
 namespace mapping {
@@ -27,6 +28,9 @@ void Require(bool condition, const char* what) {
 }
 
 std::vector<cmx_voxel> Flatten(const HybridGrid& grid) {     // the HybridGrid::Iterator walk
+  // (the HybridGrid a resident submap hands out is EMPTY, device_grids.h: never upload it)
+  Require(dropin::DeviceGridOf(&grid) == nullptr,
+          "a hybrid grid resident in HBM reached the host-upload path of the batched builder");
   std::vector<cmx_voxel> out;
   for (auto it = HybridGrid::Iterator(grid); !it.Done(); it.Next()) {
     const Eigen::Array3i index = it.GetCellIndex();
@@ -165,8 +169,19 @@ std::shared_ptr<ConstraintBuilder3D::DeviceMatcher> ConstraintBuilder3D::Matcher
   // Placement: submap k of this builder lives in the HBM of device k mod world (mutex_ held).
   const int world = cmx_comm_num_devices(comm_);
   const int device = cmx_comm_device_of(comm_, num_matchers_created_++ % world, world);
+  // Submaps resident in HBM (device_grids.h) build their matcher from the device grids, on the
+  // device those live on.
+  const cmx_grid3d* const device_high = dropin::DeviceGridOf(high);
+  const cmx_grid3d* const device_low = dropin::DeviceGridOf(low);
   auto task = std::make_unique<common::Task>();
-  task->SetWorkItem([matcher, high, low, histogram, fast, device] {
+  task->SetWorkItem([matcher, high, low, histogram, fast, device, device_high, device_low] {
+    if (device_high != nullptr && device_low != nullptr) {
+      const std::vector<float> h = Flatten(*histogram);
+      CheckOk(cmx_fast3d_create_from_grids(&fast, device_high, device_low, h.data(),
+                                           static_cast<int32_t>(h.size()), &matcher->handle),
+              "cmx_fast3d_create_from_grids");
+      return;
+    }
     const std::vector<cmx_voxel> voxels = Flatten(*high), low_voxels = Flatten(*low);
     const std::vector<float> h = Flatten(*histogram);
     CheckOk(cmx_fast3d_create(&fast, high->resolution(), high->grid_size(), voxels.data(),

@@ -111,11 +111,21 @@ FastCorrelativeScanMatcher3D::FastCorrelativeScanMatcher3D(
                              options.min_rotational_score(), options.min_low_resolution_score(),
                              options.linear_xy_search_window(), options.linear_z_search_window(),
                              options.angular_search_window()};
-  const std::vector<cmx_voxel> voxels = Flatten(hybrid_grid);
-  const std::vector<cmx_voxel> low = Flatten(*low_resolution_hybrid_grid);
   std::vector<float> histogram;
   for (int i = 0; i != rotational_scan_matcher_histogram->size(); ++i)
     histogram.push_back((*rotational_scan_matcher_histogram)[i]);
+  // Submaps resident in HBM (device_grids.h): the matcher is built from the device grids, which
+  // never cross PCIe.
+  const cmx_grid3d* const device_high = dropin::DeviceGridOf(&hybrid_grid);
+  const cmx_grid3d* const device_low = dropin::DeviceGridOf(low_resolution_hybrid_grid);
+  if (device_high != nullptr && device_low != nullptr) {
+    CheckOk(cmx_fast3d_create_from_grids(&o, device_high, device_low, histogram.data(),
+                                         static_cast<int32_t>(histogram.size()), &handle_),
+            "cmx_fast3d_create_from_grids");
+    return;
+  }
+  const std::vector<cmx_voxel> voxels = Flatten(hybrid_grid);
+  const std::vector<cmx_voxel> low = Flatten(*low_resolution_hybrid_grid);
   CheckOk(cmx_fast3d_create(&o, hybrid_grid.resolution(), hybrid_grid.grid_size(), voxels.data(),
                             static_cast<int64_t>(voxels.size()),
                             low_resolution_hybrid_grid->resolution(), low.data(),

@@ -624,6 +624,18 @@ cmx_status cmx_fast3d_create(const cmx_fast3d_options* options, float resolution
                              int64_t num_low_resolution_voxels,
                              const float* rotational_scan_matcher_histogram,
                              int32_t histogram_size, int32_t device, cmx_fast3d** out);
+/* The same matcher built from two resident HybridGrids (cmx_grid3d) without moving them across
+ * PCIe: ConstraintBuilder3D's FastCorrelativeScanMatcher3D(high_resolution_hybrid_grid,
+ * low_resolution_hybrid_grid, histogram, options) over submaps kept in HBM.  The device, both
+ * resolutions and grid_size (cmx_grid3d_info) come from the grids, which must live on one device.
+ * Bit-identical to cmx_fast3d_create on the lists cmx_grid3d_download returns for the two grids
+ * (every precomputation level, its bounds, and the raw grids cmx_fast3d_refine_batch reads).  The
+ * matcher keeps its own copies: the grids may be inserted into or destroyed afterwards. */
+cmx_status cmx_fast3d_create_from_grids(const cmx_fast3d_options* options,
+                                        const cmx_grid3d* high_resolution_grid,
+                                        const cmx_grid3d* low_resolution_grid,
+                                        const float* rotational_scan_matcher_histogram,
+                                        int32_t histogram_size, cmx_fast3d** out);
 void cmx_fast3d_destroy(cmx_fast3d* matcher);
 
 /* TrajectoryNode::Data (mapping/trajectory_node.h:45-63), the fields the
