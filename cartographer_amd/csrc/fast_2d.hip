@@ -1,15 +1,11 @@
-// FastCorrelativeScanMatcher2D on gfx950: precomputation-grid stack
-// construction, scan preparation, lowest-resolution scoring and a batched
-// branch and bound.
+// FastCorrelativeScanMatcher2D on gfx950: the batched branch and bound behind the front end.
 //
 // Reference behaviour being replaced:
-//   SM2/fast_correlative_scan_matcher_2d.cc:91-186   PrecomputationGrid2D / Stack
-//   SM2/correlative_scan_matcher_2d.cc:73-127        ShrinkToFit / GenerateRotatedScans / DiscretizeScans
-//   SM2/fast_correlative_scan_matcher_2d.cc:227-378  MatchWithSearchParameters, ScoreCandidates, BranchAndBound
+//   SM2/fast_correlative_scan_matcher_2d.cc:227-378  MatchWithSearchParameters, BranchAndBound
 // (SM2 = cartographer/mapping/internal/2d/scan_matching).
 //
-// Search schedule (any sound schedule returns the reference's best score):
-//   1. score every lowest-resolution candidate (reference: :264-274);
+// Search schedule (any sound schedule returns the reference's best score), the lowest-resolution
+// candidates having been scored (fast_2d_coarse.hip):
 //   2. "dive": greedy descents from the best few of them give a real leaf
 //      score b0, a valid lower bound;
 //   3. every lowest-resolution node whose upper bound reaches the bound is
@@ -18,1102 +14,31 @@
 //   4. among the leaves with the best score, the one the reference's
 //      depth-first search meets first is returned (see SelectBestKernel).
 //
-// Lowest-resolution scoring ("phase planes").  Lowest-resolution candidates
-// of one rotated scan sit on a lattice of pitch w = 2^(depth-1) cells, so for
-// a given point p all of them read level cells with the same residue
-// (phase) modulo w.  The level is therefore stored a second time as w*w small
-// planes, plane(py,px)[J][I] = cell(I*w+px, J*w+py): ONE 64-byte plane holds
-// everything a point contributes to all ~13x13 candidates of its scan.  Points
-// are bucketed by the lattice block they fall in; within a bucket the lane ->
-// candidate map is fixed, so a wave adds planes into registers (one coalesced
-// 64 B load + one add per point for ALL candidates) and flushes once per
-// bucket.  Out-of-grid lookups (60 % of the reference's reads here) cost
-// nothing.
+// Two strategies walk the tree: a work queue in ONE launch (TreeQueueKernel, RunQueueSearch) and a
+// chain of level-synchronous launches (RunLevelSynchronous), which is also what a queue overflow
+// falls back to.  RunBranchAndBound picks.
+//
+// The other units of the matcher: fast_2d_stack.hip (precomputation stack), fast_2d_coarse.hip
+// (front end), fast_2d_match.hip (MatchBatch, tie resolution, C ABI); fast_2d_internal.h and
+// fast_2d_device.h hold what they share.
 #include <algorithm>
-#include <atomic>
 #include <chrono>
-#include <cmath>
-#include <cstdlib>
+#include <cstring>
+#include <memory>
+#include <type_traits>
+#include <utility>
 
-#include "scan_matching_2d.h"
+#include "fast_2d_device.h"
+#include "fast_2d_internal.h"
 
 namespace cmx {
 namespace {
 
-constexpr int kMaxBuckets = 4096;      // LDS histogram size of the point bucketing
-constexpr int kMaxPlaneCells = 256;    // plane_i * plane_j
-constexpr int kMaxPlaneWidth = 128;    // w; plane index fits 14 bits
-constexpr int kMaxCoarsePerScan = 4096;  // lowest-resolution candidates per scan (plane kernel)
-constexpr int kMaxAccCells = 12288;      // padded LDS accumulators of the plane kernel (48 KB)
 constexpr int kSeedsPerProblem = 64;
-
-// ---------------------------------------------------------------------------
-// Precomputation stack
-// ---------------------------------------------------------------------------
-
-// Level 0: ComputeCellValue(1 - |cost|)  (SM2/fast_...2d.cc:107-108,163-169)
-// with the per-grid cost table of mapping/value_conversion_tables.cc:29-51
-// evaluated arithmetically (same f32 expression the table is built from).
-__global__ void BuildLevel0Kernel(const uint16_t* __restrict__ cells, int count, float min_cc,
-                                  float max_cc, uint8_t* __restrict__ out) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= count) return;
-  const unsigned v = cells[i] & 0x7fffu;
-  float cost;
-  if (v == 0) {
-    cost = max_cc;
-  } else {
-    const float scale = (max_cc - min_cc) / 32766.f;
-    cost = static_cast<float>(v) * scale + (min_cc - scale);
-  }
-  const float probability = 1.f - fabsf(cost);
-  const float min_s = 1.f - max_cc, max_s = 1.f - min_cc;
-  int value = LRoundF32((probability - min_s) * (255.f / (max_s - min_s)));
-  value = min(max(value, 0), 255);
-  out[i] = static_cast<uint8_t>(value);
-}
-
-// Level w from level w/2: a w x w window is the union of four (w/2) x (w/2)
-// windows.  The u8 quantisation is monotone, so max-then-quantise (reference)
-// equals quantise-then-max (here).  Windows entirely outside the grid read 0,
-// which never wins because at least one of the four overlaps the grid.
-__global__ void BuildLevelKernel(const uint8_t* __restrict__ prev, int pwx, int pwy, int half,
-                                 uint8_t* __restrict__ out, int wx, int wy) {
-  const int X = blockIdx.x * blockDim.x + threadIdx.x;
-  const int Y = blockIdx.y;
-  if (X >= wx) return;
-  // (x0, y0) = (X - (w-1), Y - (w-1)); in the previous level's storage the
-  // window at x0 sits at x0 + half - 1 = X - half.
-  const int px0 = X - half, py0 = Y - half;
-  int best = 0;
-#pragma unroll
-  for (int j = 0; j < 2; ++j) {
-    const int py = py0 + j * half;
-    if (static_cast<unsigned>(py) >= static_cast<unsigned>(pwy)) continue;
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      const int px = px0 + i * half;
-      if (static_cast<unsigned>(px) >= static_cast<unsigned>(pwx)) continue;
-      best = max(best, static_cast<int>(prev[px + py * pwx]));
-    }
-  }
-  out[X + Y * wx] = static_cast<uint8_t>(best);
-}
-
-// planes[(py*w + px) * stride + J*PI + I] = level(I*w + px, J*w + py) (0 outside).
-__global__ void BuildPlanesKernel(const uint8_t* __restrict__ level, int wx, int wy, int w, int PI,
-                                  int PJ, int stride, uint8_t* __restrict__ planes) {
-  const int plane = blockIdx.x;             // w*w planes + 1 zero plane
-  const int px = plane % w, py = plane / w;
-  for (int c = threadIdx.x; c < stride; c += blockDim.x) {
-    int v = 0;
-    if (plane < w * w && c < PI * PJ) {
-      const int I = c % PI, J = c / PI;
-      const int x = I * w + px, y = J * w + py;
-      if (x < wx && y < wy) v = level[x + y * wx];
-    }
-    planes[static_cast<size_t>(plane) * stride + c] = static_cast<uint8_t>(v);
-  }
-}
-
-// out(X, Y) = max of level(X - 2 + a, Y - 2 + b), a, b in [0, 4] (cells outside the level read 0), for
-// X in [0, wx + 4), Y in [0, wy + 4): the level dilated by two cells either way, stored two cells
-// up so that the border's dilation has a place (the group bounds of the fused front end).
-constexpr int kGroupDilation = 2;
-__global__ void DilateLevelKernel(const uint8_t* __restrict__ level, int wx, int wy,
-                                  uint8_t* __restrict__ out) {
-  const int X = blockIdx.x * blockDim.x + threadIdx.x;
-  const int Y = blockIdx.y;
-  const int ox = wx + 2 * kGroupDilation;
-  if (X >= ox) return;
-  int best = 0;
-  for (int b = -kGroupDilation; b <= kGroupDilation; ++b) {
-    const int y = Y - kGroupDilation + b;
-    if (static_cast<unsigned>(y) >= static_cast<unsigned>(wy)) continue;
-    for (int a = -kGroupDilation; a <= kGroupDilation; ++a) {
-      const int x = X - kGroupDilation + a;
-      if (static_cast<unsigned>(x) >= static_cast<unsigned>(wx)) continue;
-      best = max(best, static_cast<int>(level[x + y * wx]));
-    }
-  }
-  out[X + Y * ox] = static_cast<uint8_t>(best);
-}
-
-// quads(x + w, y + w) = level(x, y) | level(x, y+w) << 8 | level(x+w, y) << 16 |
-// level(x+w, y+w) << 24 for x in [-w, wx), y in [-w, wy); cells outside the level read 0.
-// Tiled storage: QuadOffset (scan_matching_2d.h).
-__global__ void BuildQuadsKernel(const uint8_t* __restrict__ level, int wx, int wy, int w,
-                                 uint32_t* __restrict__ quads, int qx, int qy, int qtx) {
-  const int X = blockIdx.x * blockDim.x + threadIdx.x;
-  const int Y = blockIdx.y;
-  if (X >= qx) return;
-  const int x = X - w, y = Y - w;
-  auto at = [&](int cx, int cy) -> uint32_t {
-    return (static_cast<unsigned>(cx) < static_cast<unsigned>(wx) &&
-            static_cast<unsigned>(cy) < static_cast<unsigned>(wy))
-               ? level[cx + cy * wx] : 0u;
-  };
-  quads[QuadOffset(X, Y, qtx)] =
-      at(x, y) | (at(x, y + w) << 8) | (at(x + w, y) << 16) | (at(x + w, y + w) << 24);
-}
-
-// ---------------------------------------------------------------------------
-// Scan preparation: rotate, translate, discretise, ShrinkToFit, bucket
-// ---------------------------------------------------------------------------
-__global__ void __launch_bounds__(256)
-PrepScansKernel(const Fast2DProblem* __restrict__ problems, const float* __restrict__ xyz, int n,
-                ProblemState* __restrict__ states, int* __restrict__ counters_words,
-                int num_counter_words) {
-  // First kernel of a call: it also clears the list counters of the search (saves a
-  // memset and its launch gap).
-  // (every workgroup clears a slice: the counters with the work queue's control words are 376 KB)
-  if (counters_words)
-    for (int i = (blockIdx.y * gridDim.x + blockIdx.x) * blockDim.x + threadIdx.x;
-         i < num_counter_words; i += gridDim.x * gridDim.y * blockDim.x)
-      counters_words[i] = 0;
-  const Fast2DProblem& P = problems[blockIdx.y];
-  const int s = blockIdx.x;
-  if (s >= P.num_scans || P.use_fused) return;
-  const Quat q0{P.init_qw, 0.f, 0.f, P.init_qz};
-  const float2 r = P.scan_rot[s];
-  const Quat qs{r.x, 0.f, 0.f, r.y};
-  uint32_t* out = P.discrete + static_cast<size_t>(s) * n;
-  int lo_x = 0, lo_y = 0, hi_x = 0, hi_y = 0, bad = 0;
-  for (int i = threadIdx.x; i < n; i += blockDim.x) {
-    const F3 p{xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2]};
-    F3 a = Rotate(q0, p);                   // rotated_point_cloud (+ zero translation)
-    a.x += 0.f; a.y += 0.f; a.z += 0.f;
-    F3 b = Rotate(qs, a);                   // GenerateRotatedScans
-    b.x += 0.f; b.y += 0.f;
-    const float x = (1.f * b.x + 0.f * b.y) + P.tx;   // Affine2f(translation) * v
-    const float y = (0.f * b.x + 1.f * b.y) + P.ty;
-    // MapLimits::GetCellIndex (mapping/2d/map_limits.h:69-76).
-    const int ix = CellIndexF64(P.max_y - static_cast<double>(y), P.res, P.inv_res);
-    const int iy = CellIndexF64(P.max_x - static_cast<double>(x), P.res, P.inv_res);
-    if (ix < -32768 || ix > 32767 || iy < -32768 || iy > 32767) bad = 1;
-    out[i] = (static_cast<uint32_t>(ix) & 0xffffu) | (static_cast<uint32_t>(iy) << 16);
-    lo_x = min(lo_x, -ix);
-    lo_y = min(lo_y, -iy);
-    hi_x = max(hi_x, P.nx - 1 - ix);
-    hi_y = max(hi_y, P.ny - 1 - iy);
-  }
-  __shared__ int red[4][5];
-  __shared__ int4 s_bounds;
-  __shared__ int2 s_dims;
-  lo_x = WaveMin(lo_x); lo_y = WaveMin(lo_y);
-  hi_x = WaveMax(hi_x); hi_y = WaveMax(hi_y);
-  bad = WaveMax(bad);
-  const int wave = threadIdx.x >> 6;
-  if ((threadIdx.x & 63) == 0) {
-    red[wave][0] = lo_x; red[wave][1] = lo_y; red[wave][2] = hi_x; red[wave][3] = hi_y;
-    red[wave][4] = bad;
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    for (int w = 1; w < 4; ++w) {
-      lo_x = min(lo_x, red[w][0]); lo_y = min(lo_y, red[w][1]);
-      hi_x = max(hi_x, red[w][2]); hi_y = max(hi_y, red[w][3]);
-      bad = max(bad, red[w][4]);
-    }
-    // SearchParameters::ShrinkToFit (SM2/correlative_scan_matcher_2d.cc:73-91).
-    int4 bd;
-    bd.x = max(-P.nl, lo_x);
-    bd.y = min(P.nl, hi_x);
-    bd.z = max(-P.nl, lo_y);
-    bd.w = min(P.nl, hi_y);
-    P.bounds[s] = bd;
-    // GenerateLowestResolutionCandidates counts (SM2/fast_...2d.cc:279-292).
-    const int step = 1 << (P.depth - 1);
-    const int2 dims = make_int2((bd.y - bd.x + step) / step, (bd.w - bd.z + step) / step);
-    P.coarse_dims[s] = dims;
-    s_bounds = bd;
-    s_dims = dims;
-    if (bad) atomicMax(&states[blockIdx.y].error, 1);
-    const int count = dims.x * dims.y;
-    if (count > P.coarse_stride || (P.use_planes && count > kMaxCoarsePerScan))
-      atomicMax(&states[blockIdx.y].error, 2);
-  }
-  if (!P.use_planes) return;
-
-  // ---- bucket the points by the lattice block they fall in ---------------
-  __shared__ int hist[kMaxBuckets];
-  __shared__ int partial[256];
-  __syncthreads();
-  const int4 bd = s_bounds;
-  const int2 dims = s_dims;
-  const int shift = P.depth - 1, w = 1 << shift;
-  const int BW = dims.x + P.plane_i - 1, BH = dims.y + P.plane_j - 1;
-  const int NB = BW * BH;   // <= kMaxBuckets (checked on the host with upper bounds)
-  for (int b = threadIdx.x; b < NB; b += blockDim.x) hist[b] = 0;
-  __syncthreads();
-  auto classify = [&](uint32_t packed, int* bucket, int* plane, uint32_t* block = nullptr) {
-    const int U = static_cast<short>(packed & 0xffffu) + bd.x + w - 1;
-    const int V = static_cast<short>(packed >> 16) + bd.z + w - 1;
-    const int bx = (U >> shift) + dims.x - 1, by = (V >> shift) + dims.y - 1;
-    *plane = (V & (w - 1)) * w + (U & (w - 1));
-    *bucket = (bx >= 0 && bx < BW && by >= 0 && by < BH) ? by * BW + bx : -1;
-    if (block) *block = static_cast<uint32_t>(bx) | (static_cast<uint32_t>(by) << 8);
-  };
-  for (int i = threadIdx.x; i < n; i += blockDim.x) {
-    int bucket, plane;
-    classify(out[i], &bucket, &plane);
-    if (bucket >= 0) atomicAdd(&hist[bucket], 1);
-  }
-  __syncthreads();
-  // exclusive scan of hist[0..NB)
-  const int chunk = (NB + 255) / 256;
-  const int b0 = min(static_cast<int>(threadIdx.x) * chunk, NB), b1 = min(b0 + chunk, NB);
-  int sum = 0;
-  for (int b = b0; b < b1; ++b) sum += hist[b];
-  partial[threadIdx.x] = sum;
-  __syncthreads();
-  if (threadIdx.x < 64) {   // exclusive scan of the 256 partials by one wave, 4 per lane
-    const int l = threadIdx.x;
-    const int a0 = partial[4 * l], a1 = partial[4 * l + 1], a2 = partial[4 * l + 2],
-              a3 = partial[4 * l + 3];
-    const int mine = a0 + a1 + a2 + a3;
-    int incl = mine;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-      const int o = __shfl_up(incl, off, 64);
-      if (l >= off) incl += o;
-    }
-    const int base = incl - mine;
-    partial[4 * l] = base;
-    partial[4 * l + 1] = base + a0;
-    partial[4 * l + 2] = base + a0 + a1;
-    partial[4 * l + 3] = base + a0 + a1 + a2;
-    if (l == 63) P.sorted_count[s] = incl;
-  }
-  __syncthreads();
-  int run = partial[threadIdx.x];
-  for (int b = b0; b < b1; ++b) { const int v = hist[b]; hist[b] = run; run += v; }
-  __syncthreads();
-  // Records carry what the plane scorer would otherwise compute per point: the byte
-  // offset of the point's plane and the constant bx * pitch + by its lattice block
-  // subtracts in the accumulator index (pitch = dims.y + 2 * plane_j - 2).
-  uint2* sorted = P.sorted + static_cast<size_t>(s) * n;
-  const int pitch = dims.y + 2 * P.plane_j - 2;
-  for (int i = threadIdx.x; i < n; i += blockDim.x) {
-    int bucket, plane;
-    uint32_t block;
-    classify(out[i], &bucket, &plane, &block);
-    if (bucket >= 0) {
-      const int pos = atomicAdd(&hist[bucket], 1);
-      sorted[pos] = make_uint2(static_cast<uint32_t>(plane) * P.plane_stride,
-                               (block & 0xffu) * pitch + (block >> 8));
-    }
-  }
-}
-
-// ---------------------------------------------------------------------------
-// Scoring
-// ---------------------------------------------------------------------------
-__device__ __forceinline__ float ToScore(const Fast2DProblem& P, int sum, int n) {
-  // ToScore(sum / float(N))  (SM2/fast_...2d.cc:330-331, .h:74-76)
-  return P.min_s + (static_cast<float>(sum) / static_cast<float>(n)) * P.score_scale;
-}
-
-// An integer >= the sum a node's score was computed from (inverse of ToScore,
-// rounded generously upwards; only used to prune).
-__device__ __forceinline__ int SumUpperBound(const Fast2DProblem& P, float score, int n) {
-  const float s = (score - P.min_s) / P.score_scale * static_cast<float>(n);
-  const float ub = ceilf(s * (1.f + 1e-5f)) + 2.f;
-  return static_cast<int>(fminf(fmaxf(ub, 0.f), 255.f * static_cast<float>(n)));
-}
-
-// Integer sum of one candidate over all points, one wave per candidate
-// (SM2/fast_...2d.cc:320-329 with GetValue of .h:56-71).  Generic fallback of
-// the lowest resolution when the phase-plane layout does not apply.
-__device__ __forceinline__ int ScoreCandidateWave(const LevelDesc& L, int level,
-                                                  const uint32_t* __restrict__ scan, int n, int dx,
-                                                  int dy, int lane) {
-  const int off = (1 << level) - 1;   // -offset_
-  const int ax = dx + off, ay = dy + off;
-  const auto* cells = AsGlobal(L.cells);
-  const auto* gscan = AsGlobal(scan);
-  int sum = 0;
-#pragma unroll 4
-  for (int i = lane; i < n; i += kWave) {
-    const uint32_t p = gscan[i];
-    const int x = static_cast<short>(p & 0xffffu) + ax;
-    const int y = static_cast<short>(p >> 16) + ay;
-    const bool ok = static_cast<unsigned>(x) < static_cast<unsigned>(L.wx) &&
-                    static_cast<unsigned>(y) < static_cast<unsigned>(L.wy);
-    const unsigned v = cells[ok ? x + y * L.wx : 0];   // unconditional load, masked value
-    sum += ok ? v : 0u;
-  }
-  return WaveSum(sum);
-}
-
-// Block-wide (sum, local index) maximum, smallest index on ties; result valid
-// in thread 0.
-__device__ __forceinline__ int2 BlockBest(int sum, int index, int2* scratch /*[4]*/) {
-  // sum >= -1 (idle threads pass -1); bias by one so the key is unsigned.
-  unsigned long long key =
-      (static_cast<unsigned long long>(static_cast<unsigned>(sum + 1)) << 32) |
-      static_cast<unsigned>(0x7fffffff - index);
-  key = WaveMaxU64(key);
-  if ((threadIdx.x & 63) == 0)
-    scratch[threadIdx.x >> 6] = make_int2(static_cast<int>(key >> 32) - 1,
-                                          0x7fffffff - static_cast<int>(key & 0xffffffffu));
-  __syncthreads();
-  int2 best = scratch[0];
-  if (threadIdx.x == 0) {
-    for (int w = 1; w < static_cast<int>(blockDim.x >> 6); ++w) {
-      const int2 o = scratch[w];
-      if (o.x > best.x || (o.x == best.x && o.y < best.y)) best = o;
-    }
-  }
-  return best;
-}
-
-__global__ void __launch_bounds__(256)
-ScoreCoarseGenericKernel(const Fast2DProblem* __restrict__ problems, int n,
-                         const ProblemState* __restrict__ states) {
-  const Fast2DProblem& P = problems[blockIdx.y];
-  const int s = blockIdx.x;
-  if (s >= P.num_scans || states[blockIdx.y].error || P.use_planes) return;
-  const int level = P.depth - 1;
-  const int step = 1 << level;
-  const int2 dims = P.coarse_dims[s];
-  const int4 bd = P.bounds[s];
-  const int base = s * P.coarse_stride;
-  const uint32_t* scan = P.discrete + static_cast<size_t>(s) * n;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int count = dims.x * dims.y;
-  int best_sum = -1, best_index = 0x7ffffff;  // idle threads (sum -1) never win
-  for (int c = wave; c < count; c += 4) {
-    const int ix = c / dims.y, iy = c - ix * dims.y;   // x outer, y inner (:295-307)
-    const int sum = ScoreCandidateWave(P.level[level], level, scan, n, bd.x + ix * step,
-                                       bd.z + iy * step, lane);
-    if (lane == 0) {
-      P.coarse_sum[base + c] = sum;
-      P.coarse_score[base + c] = ToScore(P, sum, n);
-    }
-    if (sum > best_sum) { best_sum = sum; best_index = c; }
-  }
-  __shared__ int2 scratch[4];
-  const int2 best = BlockBest(best_sum, best_index, scratch);
-  if (threadIdx.x == 0) P.scan_best[s] = best;
-}
-
-// Phase-plane scoring of all lowest-resolution candidates of one scan.
-template <int CHUNKS>
-__global__ void __launch_bounds__(256)
-ScoreCoarsePlanesKernel(const Fast2DProblem* __restrict__ problems, int n,
-                        const ProblemState* __restrict__ states) {
-  const Fast2DProblem& P = problems[blockIdx.y];
-  const int s = blockIdx.x;
-  if (s >= P.num_scans || states[blockIdx.y].error || !P.use_planes || P.use_fused) return;
-  if ((P.plane_stride >> 6) != CHUNKS) return;
-  // Candidate accumulators, padded by the plane extent on every side: a lane's cell
-  // (I, J) in lattice block (bx, by) belongs to candidate
-  //   (ix, iy) = (I - bx + dims.x - 1, J - by + dims.y - 1),
-  // which may lie outside [0, dims); with the padding its accumulator index
-  //   (ix + PI - 1) * pitch + (iy + PJ - 1) = lane_const - (bx * pitch + by)
-  // is always inside the array, so a flush is one subtract and one LDS add per lane,
-  // no bounds logic (out-of-range candidates collect in padding nobody reads).
-  extern __shared__ int cand_acc[];
-  __shared__ int2 scratch[4];
-  const int2 dims = P.coarse_dims[s];
-  const int count = dims.x * dims.y;
-  const int PI = P.plane_i, PJ = P.plane_j, PIJ = PI * PJ;
-  const int pitch = dims.y + 2 * PJ - 2;
-  const int acc_cells = (dims.x + 2 * PI - 2) * pitch;
-  for (int i = threadIdx.x; i < acc_cells; i += blockDim.x) cand_acc[i] = 0;
-  __syncthreads();
-
-  const int lane = threadIdx.x & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int M = P.sorted_count[s];
-  // (x = plane byte offset, y = block constant) as one 64-bit word per record
-  const auto* rec = AsGlobal(reinterpret_cast<const unsigned long long*>(P.sorted)) +
-                    static_cast<size_t>(s) * n;
-  const int waves = blockDim.x >> 6;     // 2..4, chosen by the host (see the launch)
-  const int begin = static_cast<int>(static_cast<long long>(M) * wave / waves);
-  const int end = static_cast<int>(static_cast<long long>(M) * (wave + 1) / waves);
-  const int stride = P.plane_stride;
-  const unsigned zero_plane = 1u << (2 * (P.depth - 1));   // index w*w: the all-zero plane
-
-  int acc[CHUNKS], lane_const[CHUNKS];
-#pragma unroll
-  for (int c = 0; c < CHUNKS; ++c) {
-    acc[c] = 0;
-    // Lanes past the plane read its zero padding: let them add 0 to the last cell.
-    const int cell = min(c * 64 + lane, PIJ - 1);
-    lane_const[c] = (cell % PI + dims.x + PI - 2) * pitch + (cell / PI + dims.y + PJ - 2);
-  }
-  int cur = -1;
-  auto flush = [&](int block_const) {
-#pragma unroll
-    for (int c = 0; c < CHUNKS; ++c) {
-      atomicAdd(&cand_acc[lane_const[c] - block_const], acc[c]);
-      acc[c] = 0;
-    }
-  };
-
-  // Records are wave-uniform: 64 of them arrive with one coalesced 8-byte load per lane
-  // (the next 64 prefetched meanwhile) and are broadcast with v_readlane (immediate lane
-  // index: the batch loops are fully unrolled).  A plane read is a buffer load: lane
-  // offset in a VGPR, the record's plane offset in an SGPR, no address arithmetic at all.
-  // kBatch plane loads are in flight before the first one is consumed.  Lanes past `end`
-  // hold the sentinel (all-zero plane, block -1): adding zeros changes nothing.
-  constexpr int kBatch = CHUNKS == 1 ? 32 : (CHUNKS == 2 ? 16 : 8);
-  const int kSentinelBlock = -1;
-  const unsigned long long sentinel =
-      (static_cast<unsigned long long>(static_cast<uint32_t>(kSentinelBlock)) << 32) |
-      static_cast<uint32_t>(zero_plane * stride);
-  const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<uint8_t*>(P.planes), 0, static_cast<int>((zero_plane + 1) * stride), 0x00020000);
-  unsigned long long mine = sentinel;
-  if (begin + lane < end) mine = rec[begin + lane];
-  for (int base_i = begin; base_i < end; base_i += 64) {
-    unsigned long long next = sentinel;
-#pragma unroll
-    for (int j0 = 0; j0 < 64; j0 += kBatch) {
-      if (base_i + j0 >= end) break;          // wave-uniform
-      int block[kBatch];
-      int v[kBatch][CHUNKS];
-#pragma unroll
-      for (int k = 0; k < kBatch; ++k) {
-        const int plane_offset =
-            __builtin_amdgcn_readlane(static_cast<int>(mine & 0xffffffffu), j0 + k);
-        block[k] = __builtin_amdgcn_readlane(static_cast<int>(mine >> 32), j0 + k);
-#pragma unroll
-        for (int c = 0; c < CHUNKS; ++c)
-          v[k][c] = __builtin_amdgcn_raw_buffer_load_b8(rsrc, lane + c * 64, plane_offset, 0);
-      }
-      if (j0 == 0) {   // prefetch the next 64 records behind this batch's plane loads
-        const int nidx = base_i + 64 + lane;
-        next = rec[min(nidx, end - 1)];
-        if (nidx >= end) next = sentinel;
-      }
-#pragma unroll
-      for (int k = 0; k < kBatch; ++k) {
-        if (block[k] != cur) {
-          if (cur >= 0) flush(cur);
-          cur = block[k];     // the sentinel block (-1) only ever follows real ones
-        }
-#pragma unroll
-        for (int c = 0; c < CHUNKS; ++c) acc[c] += v[k][c];
-      }
-    }
-    mine = next;
-  }
-  if (cur >= 0) flush(cur);
-  __syncthreads();
-
-  const int base = s * P.coarse_stride;
-  auto* coarse_sum = AsGlobal(P.coarse_sum) + base;
-  auto* coarse_score = AsGlobal(P.coarse_score) + base;
-  int best_sum = -1, best_index = 0x7ffffff;  // idle threads (sum -1) never win
-  for (int i = threadIdx.x; i < count; i += blockDim.x) {
-    const int ix = i / dims.y, iy = i - ix * dims.y;
-    const int sum = cand_acc[(ix + PI - 1) * pitch + (iy + PJ - 1)];
-    coarse_sum[i] = sum;
-    coarse_score[i] = ToScore(P, sum, n);
-    if (sum > best_sum) { best_sum = sum; best_index = i; }
-  }
-  const int2 best = BlockBest(best_sum, best_index, scratch);
-  if (threadIdx.x == 0) P.scan_best[s] = best;
-}
-
-// The same scoring for 64-byte planes (plane_i * plane_j <= 64, the usual case) with DWORD
-// gathers.  A wave-wide `buffer_load_ubyte` costs the texture-address path ~12 cycles
-// however few cache lines it touches (2.3 M of them were the 45 us of the byte variant:
-// SQ/TA counters in profiles/HISTORY.md); here a lane fetches four plane cells at once, sixteen lanes
-// cover a plane, and one instruction serves FOUR records (lane group g = lane / 16 takes
-// records 4t + g).  Groups sit in different lattice blocks, so the block bookkeeping is
-// per lane: packed 16-bit partial sums (cells 0|2 and 1|3), flushed to the LDS
-// accumulators when the lane's block changes or after 256 records.
-__global__ void __launch_bounds__(256)
-ScoreCoarsePlanesDwordKernel(const Fast2DProblem* __restrict__ problems, int n,
-                             const ProblemState* __restrict__ states) {
-  const Fast2DProblem& P = problems[blockIdx.y];
-  const int s = blockIdx.x;
-  if (s >= P.num_scans || states[blockIdx.y].error || !P.use_planes || P.use_fused) return;
-  if (P.plane_stride != 64) return;
-  extern __shared__ int cand_acc[];
-  __shared__ int2 scratch[4];
-  const int2 dims = P.coarse_dims[s];
-  const int count = dims.x * dims.y;
-  const int PI = P.plane_i, PJ = P.plane_j, PIJ = PI * PJ;
-  const int pitch = dims.y + 2 * PJ - 2;
-  const int acc_cells = (dims.x + 2 * PI - 2) * pitch;
-  for (int i = threadIdx.x; i < acc_cells; i += blockDim.x) cand_acc[i] = 0;
-  __syncthreads();
-
-  const int lane = threadIdx.x & 63;
-  const int group = lane >> 4, sub = lane & 15;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int M = P.sorted_count[s];
-  const auto* rec = AsGlobal(reinterpret_cast<const unsigned long long*>(P.sorted)) +
-                    static_cast<size_t>(s) * n;
-  const int waves = blockDim.x >> 6;
-  const int begin = static_cast<int>(static_cast<long long>(M) * wave / waves);
-  const int end = static_cast<int>(static_cast<long long>(M) * (wave + 1) / waves);
-  const unsigned zero_plane = 1u << (2 * (P.depth - 1));   // index w*w: the all-zero plane
-
-  int lane_const[4];
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    // Cells past the plane are zero padding: they add 0 to the last cell.
-    const int cell = min(4 * sub + j, PIJ - 1);
-    lane_const[j] = (cell % PI + dims.x + PI - 2) * pitch + (cell / PI + dims.y + PJ - 2);
-  }
-  int cur = -1, pending = 0;
-  uint32_t even = 0, odd = 0;               // cells 0 | 2 << 16 and 1 | 3 << 16
-  const auto flush = [&]() {
-    const int a0 = even & 0xffffu, a2 = even >> 16, a1 = odd & 0xffffu, a3 = odd >> 16;
-    if (a0) atomicAdd(&cand_acc[lane_const[0] - cur], a0);
-    if (a1) atomicAdd(&cand_acc[lane_const[1] - cur], a1);
-    if (a2) atomicAdd(&cand_acc[lane_const[2] - cur], a2);
-    if (a3) atomicAdd(&cand_acc[lane_const[3] - cur], a3);
-    even = odd = 0;
-    pending = 0;
-  };
-
-  constexpr int kSteps = 8;                 // gathers (of four records each) in flight
-  const unsigned long long sentinel = (0xffffffffull << 32) | (zero_plane * 64u);
-  const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<uint8_t*>(P.planes), 0, static_cast<int>((zero_plane + 1) * 64), 0x00020000);
-  unsigned long long mine = sentinel;
-  if (begin + lane < end) mine = rec[begin + lane];
-  for (int base_i = begin; base_i < end; base_i += 64) {
-    unsigned long long next = sentinel;
-#pragma unroll
-    for (int t0 = 0; t0 < 16; t0 += kSteps) {
-      if (base_i + 4 * t0 >= end) break;      // wave-uniform
-      int block[kSteps];
-      uint32_t q[kSteps];
-#pragma unroll
-      for (int k = 0; k < kSteps; ++k) {
-        const int src = 4 * (t0 + k) + group;                 // this lane group's record
-        const int plane_offset = __shfl(static_cast<int>(mine & 0xffffffffu), src, 64);
-        block[k] = __shfl(static_cast<int>(mine >> 32), src, 64);
-        q[k] = __builtin_amdgcn_raw_buffer_load_b32(rsrc, plane_offset + 4 * sub, 0, 0);
-      }
-      if (t0 == 0) {   // prefetch the next 64 records behind the first gathers
-        const int nidx = base_i + 64 + lane;
-        next = rec[min(nidx, end - 1)];
-        if (nidx >= end) next = sentinel;
-      }
-#pragma unroll
-      for (int k = 0; k < kSteps; ++k) {
-        if (block[k] != cur) {                // per lane group
-          if (cur >= 0) flush();
-          cur = block[k];                     // -1 (sentinel) only ever follows real blocks
-        }
-        even += q[k] & 0x00ff00ffu;
-        odd += (q[k] >> 8) & 0x00ff00ffu;
-        if (++pending == 256) flush();        // 16-bit partial sums: 256 x 255 fits
-      }
-    }
-    mine = next;
-  }
-  if (cur >= 0) flush();
-  __syncthreads();
-
-  const int base = s * P.coarse_stride;
-  auto* coarse_sum = AsGlobal(P.coarse_sum) + base;
-  auto* coarse_score = AsGlobal(P.coarse_score) + base;
-  int best_sum = -1, best_index = 0x7ffffff;  // idle threads (sum -1) never win
-  for (int i = threadIdx.x; i < count; i += blockDim.x) {
-    const int ix = i / dims.y, iy = i - ix * dims.y;
-    const int sum = cand_acc[(ix + PI - 1) * pitch + (iy + PJ - 1)];
-    coarse_sum[i] = sum;
-    coarse_score[i] = ToScore(P, sum, n);
-    if (sum > best_sum) { best_sum = sum; best_index = i; }
-  }
-  const int2 best = BlockBest(best_sum, best_index, scratch);
-  if (threadIdx.x == 0) P.scan_best[s] = best;
-}
-
-// ---------------------------------------------------------------------------
-// Fused front end (the usual case: 64-byte phase planes, the scan fits in LDS)
-// ---------------------------------------------------------------------------
-// One block per rotated scan does everything the reference does for that scan before
-// branch and bound -- GenerateRotatedScans + DiscretizeScans + ShrinkToFit
-// (SM2/correlative_scan_matcher_2d.cc:73-127), GenerateLowestResolutionCandidates and
-// their ScoreCandidates (SM2/fast_correlative_scan_matcher_2d.cc:264-333) -- with the
-// discretised scan staged in LDS only.  As separate launches the same work wrote 27 MB per
-// match (discrete scans + 64-bit bucketed records) and the scorer fetched 20 MB of it back;
-// here only the candidates' scores (1.7 MB) leave the chip -- the tree search re-derives the
-// cells of the scans it descends into (ScanCell) -- and the per-scan candidate layout needs
-// no prefix sum: scan s owns [s * coarse_stride, (s + 1) * coarse_stride).
-//
-// Unlike the separate launches this kernel does NOT sort the points by lattice block.  The
-// sort (histogram, scan, scatter: seven barriers) was a third of a block's latency, and it
-// buys little: a range scan is spatially coherent -- consecutive returns fall into the same
-// 2^(depth-1)-cell lattice block for dozens of points -- so scoring in point order flushes
-// the register accumulators only when a lane group's block really changes.  (An unordered
-// cloud stays correct: it flushes more often.)  Every lane classifies its own point of a
-// 64-point chunk (plane, lattice block); lane group g = lane / 16 takes points 4 t + g, so
-// one buffer_load_dword still serves four points, sixteen of them in flight per wave.
-// (Wider gathers do not help: the plane reads run at ~8 B/clk per CU whatever the
-// instruction width -- buffer_load_dwordx4, sixteen points per instruction, was slower --
-// because every point touches its own 64-byte half of a 128-byte L2 line.)
-// The integer sums are order-free: results are bit-identical to the sorted variant
-// (ScoreCoarsePlanesDwordKernel, kept for CMX_FUSED=0 and for problems this kernel does not
-// take).
-// Dynamic LDS: pts[group][n_pad] u32 | misc[kFusedMisc] | cand_acc[acc_cap] | point words[waves][64].
-constexpr int kFusedMaxPoints = 4096;    // = kPointCache of the tree search
-constexpr int kFusedGroup = 3;           // rotations per workgroup under group bounds (see the kernel)
-constexpr int kFusedMisc = 128;          // ints of bookkeeping between the cells and the accumulators
-
-// Points kFirst .. kFirst + 7 of a lane group (LDS words at a stride of 16 bytes from `base`): the
-// low halves into lo[0..7], the high halves into hi[0..7], zero-extended; returns when they landed.
-template <int kFirst>
-__device__ __forceinline__ void ReadHalves8(unsigned base, uint32_t* lo, uint32_t* hi) {
-  constexpr int o = 16 * kFirst;
-  asm volatile(
-      "ds_read_u16 %0, %16 offset:%17\n\tds_read_u16 %8, %16 offset:%18\n\t"
-      "ds_read_u16 %1, %16 offset:%19\n\tds_read_u16 %9, %16 offset:%20\n\t"
-      "ds_read_u16 %2, %16 offset:%21\n\tds_read_u16 %10, %16 offset:%22\n\t"
-      "ds_read_u16 %3, %16 offset:%23\n\tds_read_u16 %11, %16 offset:%24\n\t"
-      "ds_read_u16 %4, %16 offset:%25\n\tds_read_u16 %12, %16 offset:%26\n\t"
-      "ds_read_u16 %5, %16 offset:%27\n\tds_read_u16 %13, %16 offset:%28\n\t"
-      "ds_read_u16 %6, %16 offset:%29\n\tds_read_u16 %14, %16 offset:%30\n\t"
-      "ds_read_u16 %7, %16 offset:%31\n\tds_read_u16 %15, %16 offset:%32\n\t"
-      "s_waitcnt lgkmcnt(0)"
-      : "=&v"(lo[0]), "=&v"(lo[1]), "=&v"(lo[2]), "=&v"(lo[3]), "=&v"(lo[4]), "=&v"(lo[5]),
-        "=&v"(lo[6]), "=&v"(lo[7]), "=&v"(hi[0]), "=&v"(hi[1]), "=&v"(hi[2]), "=&v"(hi[3]),
-        "=&v"(hi[4]), "=&v"(hi[5]), "=&v"(hi[6]), "=&v"(hi[7])
-      : "v"(base), "n"(o), "n"(o + 2), "n"(o + 16), "n"(o + 18), "n"(o + 32), "n"(o + 34),
-        "n"(o + 48), "n"(o + 50), "n"(o + 64), "n"(o + 66), "n"(o + 80), "n"(o + 82),
-        "n"(o + 96), "n"(o + 98), "n"(o + 112), "n"(o + 114)
-      : "memory");
-}
-
-// The sums of a unit of PrepScoreFusedKernel (below, where the terms are explained): the cells of ONE
-// rotation of the unit summed over the phase planes -- the dilated level's under group bounds, the
-// level's own otherwise -- and the sums handed to the rotations they stand for.  Everything it needs
-// comes out of the block's bookkeeping words in LDS, so that nothing but those is live across the
-// gather loop (which fills the 64 VGPRs of eight wavefronts per SIMD on its own: no scratch).
-template <bool kTimeline>
-__device__ __forceinline__ void FusedPass(const Fast2DProblem& P, ProblemState* state, int n,
-                                          int acc_cap, int s0, int timeline_block) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char fused_smem[];
-  const auto uni = [](int v) { return __builtin_amdgcn_readfirstlane(v); };
-  const int n_pad = (n + 63) & ~63;
-  const int G = P.group > 1 ? kFusedGroup : 1;
-  auto* pts_all = reinterpret_cast<uint32_t*>(fused_smem);        // [G][n_pad]
-  int* misc = reinterpret_cast<int*>(pts_all + G * n_pad);
-  int* cand_acc = misc + kFusedMisc;
-  const int T = blockDim.x;
-  const int waves = T >> 6;
-  const int lane = threadIdx.x & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const auto stamp = [&](int k) {
-    if constexpr (kTimeline) Stamp(P.timeline, timeline_block, k);
-  };
-  const int gcount = uni(misc[1]), gm = uni(misc[2]);
-  const bool far = uni(misc[7]) != 0;       // the premise of the group bound failed for this unit
-  const int2 dims_all = make_int2(uni(misc[4]), uni(misc[5]));
-  const int PI = P.plane_i, PJ = P.plane_j, PIJ = PI * PJ;
-  const int shift = P.depth - 1, w = 1 << shift;
-  const unsigned zero_plane = 1u << (2 * (P.depth - 1));
-  const int group = lane >> 4, sub = lane & 15;
-  const int begin = static_cast<int>(static_cast<long long>(n) * wave / waves);
-  const int end = static_cast<int>(static_cast<long long>(n) * (wave + 1) / waves);
-  constexpr int kSteps = 16;                // all gathers of a 64-point chunk in flight
-  uint32_t* const wave_words = reinterpret_cast<uint32_t*>(cand_acc + acc_cap) + 64 * wave;
-  const unsigned group_base = static_cast<unsigned>(reinterpret_cast<uintptr_t>(
-      (__attribute__((address_space(3))) uint32_t*)(wave_words + group)));
-  int2* const scratch = reinterpret_cast<int2*>(misc + 8);      // [4]
-  const bool verify = (P.group_verify & 1) != 0;
-    const bool group_pass = G > 1;
-    const int gp = group_pass ? gm : 0;                  // whose cells are summed
-    const uint32_t* const pts = pts_all + gp * n_pad;
-    const int* const mine = misc + 16 + 8 * gp;
-    const int4 bd = make_int4(uni(mine[0]), uni(mine[1]), uni(mine[2]), uni(mine[3]));
-    const int2 dims = group_pass ? dims_all : make_int2(uni(mine[4]), uni(mine[5]));
-    const int lift = group_pass ? kGroupDilation : 0;    // (the dilated level is stored two cells up)
-    const int pitch = dims.y + 2 * PJ - 2;
-    const int BW = dims.x + PI - 1, BH = dims.y + PJ - 1;
-
-  // ---- score in point order (cf. ScoreCoarsePlanesDwordKernel) ------------------------
-  int lane_const[4];
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    const int cell = min(4 * sub + j, PIJ - 1);
-    lane_const[j] = (cell % PI + dims.x + PI - 2) * pitch + (cell / PI + dims.y + PJ - 2);
-  }
-  // Four 32-bit running sums, one per plane cell of the lane's dword (round 4's per-chunk stamps:
-  // a step of this loop is ~15 issued instructions on a SIMD shared by 4.5 wavefronts -- 1.9 of a
-  // chunk's 2.1 us, the gathers themselves land in 0.16 -- so the packed 16-bit pairs, whose
-  // overflow guard cost a counter, a compare and a branch per step, are gone: byte k of the dword
-  // is added with one (SDWA) instruction each).
-  uint32_t cur = 0;                         // lattice block + 1 of the running sums; 0: none yet
-  uint32_t a0 = 0, a1 = 0, a2 = 0, a3 = 0;
-  const auto flush = [&]() {
-    const int at = static_cast<int>(cur) - 1;
-    if (a0) atomicAdd(&cand_acc[lane_const[0] - at], static_cast<int>(a0));
-    if (a1) atomicAdd(&cand_acc[lane_const[1] - at], static_cast<int>(a1));
-    if (a2) atomicAdd(&cand_acc[lane_const[2] - at], static_cast<int>(a2));
-    if (a3) atomicAdd(&cand_acc[lane_const[3] - at], static_cast<int>(a3));
-    a0 = a1 = a2 = a3 = 0;
-  };
-  // (the selected pointer made uniform by hand: the compiler turns the selection into ONE vector
-  // load from a selected address, and a resource out of vector registers costs a waterfall loop
-  // around every gather)
-  const unsigned long long planes_bits =
-      reinterpret_cast<unsigned long long>(group_pass ? P.planes_group : P.planes);
-  // (readfirstlane returns an int: through `unsigned`, or the low half sign-extends over the high one)
-  const unsigned planes_lo = static_cast<unsigned>(
-      __builtin_amdgcn_readfirstlane(static_cast<int>(static_cast<unsigned>(planes_bits))));
-  const unsigned planes_hi = static_cast<unsigned>(
-      __builtin_amdgcn_readfirstlane(static_cast<int>(static_cast<unsigned>(planes_bits >> 32))));
-  const uint8_t* const planes_uniform = reinterpret_cast<const uint8_t*>(
-      (static_cast<unsigned long long>(planes_hi) << 32) | planes_lo);
-  const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<uint8_t*>(planes_uniform), 0, static_cast<int>((zero_plane + 1) * 64), 0x00020000);
-  for (int base_i = begin; base_i < end; base_i += 64) {
-    // (instrumented instantiation only -- wavefront 0's first chunk step by step: [8] chunk
-    // begins, [9] its sixteen gathers issued, [10] all of them landed, [11] consumed; [12..15]:
-    // the next four chunks begin.  profiles/HISTORY.md 5.1: which part of a chunk takes its 2.25 us)
-    const int chunk_index = (base_i - begin) >> 6;
-    if constexpr (kTimeline) {
-      if (chunk_index == 0) stamp(8);
-      else if (chunk_index <= 4) stamp(11 + chunk_index);
-    }
-    // This lane's point of the chunk: byte offset of its phase plane and the constant
-    // bx * pitch + by of its lattice block (-1: no candidate of this scan can reach it).
-    // ONE word per point: plane index (low half; the zero plane for a point no candidate
-    // reaches) and lattice block + 1 (high half; BW, BH <= 255 and the host keeps the pitch so
-    // that it fits).  The wavefront parks its 64 words in LDS and a lane group reads point
-    // 4 k + group of the chunk at the IMMEDIATE offset 16 k from its own base, as two 16-bit
-    // halves: the plane index needs one shift-or to become the gather's offset and the block goes
-    // straight into the compare.  (Before: two ds_bpermute and an address add per step; as ONE
-    // packed word a shift, a mask and a decrement more -- on the unit the loop is bound by.)
-    uint32_t my_word = zero_plane;
-    if (base_i + lane < end) {
-      const uint32_t packed = pts[base_i + lane];
-      const int U = static_cast<short>(packed & 0xffffu) + bd.x + w - 1 + lift;
-      const int V = static_cast<short>(packed >> 16) + bd.z + w - 1 + lift;
-      const int bx = (U >> shift) + dims.x - 1, by = (V >> shift) + dims.y - 1;
-      if (bx >= 0 && bx < BW && by >= 0 && by < BH)
-        my_word = static_cast<uint32_t>((V & (w - 1)) * w + (U & (w - 1))) |
-                  (static_cast<uint32_t>(bx * pitch + by + 1) << 16);
-    }
-    wave_words[lane] = my_word;
-    __builtin_amdgcn_wave_barrier();
-    uint32_t block[kSteps];                            // lattice block + 1; 0: a skipped point
-    uint32_t plane[kSteps];
-    uint32_t q[kSteps];
-    // (inline assembly: written as 16-bit loads in C++, the compiler merges the two halves of a
-    // word into one ds_read_b32 and takes them apart again with a mask and a shift per step)
-    ReadHalves8<0>(group_base, plane, block);
-    ReadHalves8<8>(group_base, plane + 8, block + 8);
-#pragma unroll
-    for (int k = 0; k < kSteps; ++k)
-      q[k] = __builtin_amdgcn_raw_buffer_load_b32(rsrc, (plane[k] << 6) | (4 * sub), 0, 0);
-    __builtin_amdgcn_wave_barrier();                   // (the next chunk overwrites the words)
-    if constexpr (kTimeline) {
-      if (chunk_index == 0) {
-        stamp(9);
-        __builtin_amdgcn_s_waitcnt(0x0f70);      // vmcnt(0): the gathers' latency on its own
-        stamp(10);
-      }
-    }
-#pragma unroll
-    for (int k = 0; k < kSteps; ++k) {
-      if (block[k] != cur) {                // per lane group; 0 = skipped point (adds zeros)
-        // (cur == 0: nothing has been added but bytes of the zero plane, every sum is 0 and
-        // flush() issues no addition -- no second test per step)
-        flush();
-        cur = block[k];
-      }
-      a0 += q[k] & 0xffu;
-      a1 += (q[k] >> 8) & 0xffu;
-      a2 += (q[k] >> 16) & 0xffu;
-      a3 += q[k] >> 24;
-    }
-    if constexpr (kTimeline) {
-      if (chunk_index == 0) stamp(11);
-    }
-  }
-  if (cur != 0) flush();
-  stamp(4);      // wave 0 done gathering
-  __syncthreads();
-  stamp(5);      // all waves done
-
-    // ---- the sums of this pass to the rotations they stand for ------------------------------
-    // (a unit whose premise failed -- a point's cell, or a bound, further than one from the middle
-    // rotation's: not seen so far, the angular step excludes it up to rounding -- keeps the middle
-    // rotation's bound, which holds whatever the others do, and gives every candidate of the other
-    // rotations the largest sum there is: nothing of them is excluded up here)
-    for (int t = 0; t < gcount; ++t) {
-      const int s = s0 + t;
-      const int2 tdims = make_int2(misc[16 + 8 * t + 4], misc[16 + 8 * t + 5]);
-      const int count = tdims.x * tdims.y;
-      const int base = s * P.coarse_stride;
-      auto* coarse_sum = AsGlobal(P.coarse_sum) + base;
-      auto* coarse_score = AsGlobal(P.coarse_score) + base;
-      const bool unbounded = far && t != gm;
-      int best_sum = -1, best_index = 0x7ffffff;
-      for (int i = threadIdx.x; i < count; i += T) {
-        const int ix = i / tdims.y, iy = i - ix * tdims.y;
-        const int csum = unbounded ? 255 * n : cand_acc[(ix + PI - 1) * pitch + (iy + PJ - 1)];
-        if (group_pass) {
-          // fast2d_group_verify: the exact sums of an earlier launch (group = 1) are in place
-          if (verify && coarse_sum[i] > csum) atomicMax(&state->error, 3);
-        } else if (P.write_all_discrete || verify) {
-          coarse_sum[i] = csum;     // introspection only
-        }
-        coarse_score[i] = ToScore(P, csum, n);
-        if (csum > best_sum) { best_sum = csum; best_index = i; }
-      }
-      const int2 best = BlockBest(best_sum, best_index, scratch);
-      if (threadIdx.x == 0) P.scan_best[s] = best;
-      stamp(6);      // scores written
-      // The discretised scan stays on chip: the tree search re-derives the cells of the few scans
-      // it descends into (ScanCell).  Only the introspection entry point asks for the array.
-      // Batches (store_scans): a scan whose best candidate reaches the initial bound may enter the
-      // tree search, where several nodes per scan are expanded by independent wavefronts; its
-      // cells are written for them (a superset of what the coarse filter keeps: the bound only
-      // rises).  Re-deriving the cells per node made that expansion VALU-bound.
-      bool keep_cells = P.write_all_discrete != 0;
-      if (!keep_cells && P.store_scans) {
-        int top_sum = scratch[0].x;
-        for (int k = 1; k < T >> 6; ++k) top_sum = max(top_sum, scratch[k].x);
-        keep_cells = !(ToScore(P, top_sum, n) < fmaxf(P.min_score, 0.f));
-      }
-      if (keep_cells) {
-        auto* out = AsGlobal(P.discrete) + static_cast<size_t>(s) * n;
-        const uint32_t* const cells = pts_all + t * n_pad;
-        for (int i = threadIdx.x; i < n; i += T) out[i] = cells[i];
-      }
-      __syncthreads();                       // (the next rotation's BlockBest reuses the scratch)
-    }
-}
-
-template <bool kTimeline>    // (true: the debug switch `timeline`; the shipped instantiation has no stamps)
-__global__ void __launch_bounds__(256, 8)   // (eight wavefronts per SIMD: at most 64 VGPRs)
-PrepScoreFusedKernel(const Fast2DProblem* __restrict__ problems, const float* __restrict__ xyz,
-                     int n, ProblemState* __restrict__ states, int acc_cap,
-                     int* __restrict__ counters_words, int num_counter_words) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char fused_smem[];
-  // First kernel of a fully fused batch: it also clears the list counters of the search.
-  // (every workgroup clears a slice: the counters with the work queue's control words are 376 KB)
-  if (counters_words)
-    for (int i = (blockIdx.y * gridDim.x + blockIdx.x) * blockDim.x + threadIdx.x;
-         i < num_counter_words; i += gridDim.x * gridDim.y * blockDim.x)
-      counters_words[i] = 0;
-  const Fast2DProblem& P = problems[blockIdx.y];
-  // GROUP BOUNDS (round 6).  Neighbouring rotations move a point by at most one cell (the angular
-  // step is chosen so, SM2/correlative_scan_matcher_2d.cc:31-44), and their search bounds -- the
-  // minimum over the points -- by at most one with it.  So for the G = 3 rotations g of a unit and
-  // the middle one m, the cell a lowest-resolution candidate (kx, ky) of rotation g reads for point
-  // p lies within two cells (per axis) of the cell candidate (kx, ky) of rotation m reads for p,
-  // and ONE sum of m's cells over the level DILATED by two cells bounds the score of (kx, ky) of
-  // all three from above.  Everything behind the front end (dive, filter, tree search) takes a
-  // lowest-resolution score as the upper bound of the subtree below it and nothing else, so the
-  // bound takes the score's place: a third of the gathers.  What needs the exact scores -- the
-  // replay of the reference's std::sort when leaves tie (ResolveTies), depth 1, the introspection
-  // entry point -- runs this kernel (again) with group = 1.  The premise is CHECKED per unit (every
-  // point's cells, every bound): in a unit that fails it the outer rotations get the largest sum
-  // there is, i.e. no bound (FusedPass).  fast2d_group_verify: every bound against the exact sums
-  // of a launch with group = 1, on the device.
-  const int G = P.group > 1 ? kFusedGroup : 1;
-  // Units u, u + 256, u + 512, ... tend to share a CU (u % 8 picks the XCD, round-robin
-  // within it): give them ADJACENT rotations.  Neighbouring rotations move a point by less
-  // than a cell, so co-resident blocks gather the same or the neighbouring phase plane at
-  // about the same time and meet in the CU's L1 instead of each going to L2.  (Any bijection
-  // is correct; only speed depends on the dispatch order.)
-  const int slots = (gridDim.x + 255) >> 8;
-  const int unit = (blockIdx.x & 255) * slots + (blockIdx.x >> 8);
-  const int s0 = unit * G;
-  if (!P.use_fused || s0 >= P.num_scans) return;
-  const int gcount = min(G, P.num_scans - s0);
-  const int gm = gcount == 3 ? 1 : 0;       // the rotation of the unit whose cells are summed
-  const int n_pad = (n + 63) & ~63;
-  auto* pts_all = reinterpret_cast<uint32_t*>(fused_smem);        // [G][n_pad]
-  int* misc = reinterpret_cast<int*>(pts_all + G * n_pad);
-  int* cand_acc = misc + kFusedMisc;
-  // misc: [0, 8) the pass (bounds, dims, ok, grouped) | [8, 16) BlockBest | [16 + 8 g, ...) bounds
-  // and dims of rotation g | [40 + 20 g + 5 wave, ...) partials | [100 + wave] cell deltas
-  const int T = blockDim.x;              // 128, 192 or 256
-  const int waves = T >> 6;
-  const int lane = threadIdx.x & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const auto stamp = [&](int k) {
-    if constexpr (kTimeline) Stamp(P.timeline, blockIdx.y * gridDim.x + blockIdx.x, k);
-  };
-  stamp(0);
-
-  // ---- rotate, translate, discretise (PrepScansKernel's arithmetic) ----------
-  const bool identity_q0 = P.init_qw == 1.f && P.init_qz == 0.f;
-  // The cell of a point from an f32 ESTIMATE of the value the reference rounds,
-  //     t = (max - translation) / res - 0.5 - (rotated coordinate) / res,
-  // in two FMAs per coordinate (the real-time matcher's discretisation, rt_2d_tiles.hip, where
-  // the error bound is derived: the estimate differs from GetCellIndex over RotateZ's f32 chain
-  // by less than 2^-24 [((k_z + 4) (|ax| + |ay|) + |translation|) / res + 3 |K|], k_z =
-  // max(2 + 4 z^2, 1 + 6 |z|) for this scan's rotation (w, z)); when it lies further than
-  // 1.25 x that from every half-integer its rounding IS the reference's cell.  Otherwise -- three
-  // points in a thousand at 60 m (20 M random points over the full circle: 0 wrong cells among
-  // the decided ones) -- the exact expressions below run for that lane.  ~30 instead of ~110
-  // vector instructions per point (a third of this kernel's instructions) -- and no measurable
-  // change of its duration (same-box A/B: 132.4 -> 130.4 - 132.5 us per search): the kernel is
-  // not bound by instruction issue but by the plane gathers below.
-  const double inv_res_d = P.inv_res;
-  const double Kyd = (P.max_y - static_cast<double>(P.ty)) * inv_res_d - 0.5;
-  const double Kxd = (P.max_x - static_cast<double>(P.tx)) * inv_res_d - 0.5;
-  const float Ky = static_cast<float>(Kyd), Kx = static_cast<float>(Kxd);
-  const float bound_fixed = static_cast<float>(
-      1.25 * 0x1p-24 * (inv_res_d * fmax(fabs(static_cast<double>(P.tx)), fabs(static_cast<double>(P.ty))) +
-                        3.0 * fmax(fabs(Kxd), fabs(Kyd)) + 1.0));
-  for (int g = 0; g < gcount; ++g) {
-    const float2 r = P.scan_rot[s0 + g];
-    const double zd = r.y;
-    const float Ci = static_cast<float>((1.0 - 2.0 * zd * zd) * inv_res_d);
-    const float Si = static_cast<float>(2.0 * static_cast<double>(r.x) * zd * inv_res_d);
-    const float bound_per_m = static_cast<float>(
-        1.25 * 0x1p-24 * inv_res_d * (4.0 + fmax(2.0 + 4.0 * zd * zd, 1.0 + 6.0 * fabs(zd))));
-    uint32_t* const pts = pts_all + g * n_pad;
-    int lo_x = 0, lo_y = 0, hi_x = 0, hi_y = 0, bad = 0;
-    for (int i0 = threadIdx.x; i0 < n; i0 += 4 * T) {
-      // Four points' loads in flight before the first is used.
-      F3 p[4];
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        const int j = min(i0 + k * T, n - 1);
-        p[k] = F3{xyz[3 * j], xyz[3 * j + 1], xyz[3 * j + 2]};
-      }
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        const int i = i0 + k * T;
-        if (i >= n) break;
-        // Two yaw rotations (initial estimate, then this scan's perturbation), then the
-        // translation: Rotate / `+ 0.f` / `1.f * x + 0.f * y` of PrepScansKernel without the
-        // terms that are exactly zero (RotateZ, cmx_device.h).  A full-submap search starts
-        // from yaw 0: its first rotation is the identity.
-        float ax = p[k].x, ay = p[k].y;
-        if (!identity_q0) RotateZ(P.init_qw, P.init_qz, p[k].x, p[k].y, &ax, &ay);
-        const float tY = fmaf(-Ci, ay, fmaf(-Si, ax, Ky));    // cell x index from the map's y
-        const float tX = fmaf(-Ci, ax, fmaf(Si, ay, Kx));
-        const float nY = rintf(tY), nX = rintf(tX);
-        const float margin = fminf(0.5f - fabsf(tY - nY), 0.5f - fabsf(tX - nX));
-        const float bound = fmaf(fabsf(ax) + fabsf(ay), bound_per_m, bound_fixed);
-        int ix, iy;
-        if (margin > bound && fabsf(tY) < 1e6f && fabsf(tX) < 1e6f) {     // (NaN: not greater)
-          ix = static_cast<int>(nY);
-          iy = static_cast<int>(nX);
-        } else {
-          float bx, by;
-          RotateZ(r.x, r.y, ax, ay, &bx, &by);
-          const float x = bx + P.tx;
-          const float y = by + P.ty;
-          // lround((max - v) / res - 0.5), exact (cmx_device.h)
-          ix = CellIndexFast(P.max_y, y, P.res, P.inv_res);
-          iy = CellIndexFast(P.max_x, x, P.res, P.inv_res);
-        }
-        if (ix < -32768 || ix > 32767 || iy < -32768 || iy > 32767) bad = 1;
-        pts[i] = (static_cast<uint32_t>(ix) & 0xffffu) | (static_cast<uint32_t>(iy) << 16);
-        lo_x = min(lo_x, -ix);
-        lo_y = min(lo_y, -iy);
-        hi_x = max(hi_x, P.nx - 1 - ix);
-        hi_y = max(hi_y, P.ny - 1 - iy);
-      }
-    }
-    lo_x = WaveMinDpp(lo_x); lo_y = WaveMinDpp(lo_y);
-    hi_x = WaveMaxDpp(hi_x); hi_y = WaveMaxDpp(hi_y);
-    bad = WaveMaxDpp(bad);
-    if (lane == 0) {
-      int* red = misc + 40 + 20 * g + wave * 5;      // [G][4][5]
-      red[0] = lo_x; red[1] = lo_y; red[2] = hi_x; red[3] = hi_y; red[4] = bad;
-    }
-  }
-  for (int i = threadIdx.x; i < acc_cap; i += T) cand_acc[i] = 0;
-  stamp(1);      // points discretised
-  __syncthreads();
-  if (gcount > 1) {            // (uniform)
-    // the premise of the group bound: no point's cell further than one from the middle rotation's
-    int far = 0;
-    const uint32_t* const mid = pts_all + gm * n_pad;
-    for (int g = 0; g < gcount; ++g) {
-      if (g == gm) continue;
-      const uint32_t* const other = pts_all + g * n_pad;
-      for (int i = threadIdx.x; i < n; i += T) {
-        const uint32_t a = mid[i], b = other[i];
-        const int dx = static_cast<short>(a & 0xffffu) - static_cast<short>(b & 0xffffu);
-        const int dy = static_cast<short>(a >> 16) - static_cast<short>(b >> 16);
-        far |= (dx < -1 || dx > 1 || dy < -1 || dy > 1) ? 1 : 0;
-      }
-    }
-    far = WaveMaxDpp(far);
-    if (lane == 0) misc[100 + wave] = far;
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) {
-    const int step = 1 << (P.depth - 1);
-    int bad = 0, far = 0;
-    int2 dims_all = make_int2(0, 0);
-    for (int g = 0; g < gcount; ++g) {
-      const int* red = misc + 40 + 20 * g;
-      int lo_x = red[0], lo_y = red[1], hi_x = red[2], hi_y = red[3];
-      bad = max(bad, red[4]);
-      for (int w = 1; w < waves; ++w) {
-        red += 5;
-        lo_x = min(lo_x, red[0]); lo_y = min(lo_y, red[1]);
-        hi_x = max(hi_x, red[2]); hi_y = max(hi_y, red[3]);
-        bad = max(bad, red[4]);
-      }
-      int4 bd;   // ShrinkToFit
-      bd.x = max(-P.nl, lo_x);
-      bd.y = min(P.nl, hi_x);
-      bd.z = max(-P.nl, lo_y);
-      bd.w = min(P.nl, hi_y);
-      P.bounds[s0 + g] = bd;
-      const int2 dims = make_int2((bd.y - bd.x + step) / step, (bd.w - bd.z + step) / step);
-      P.coarse_dims[s0 + g] = dims;
-      int* mine = misc + 16 + 8 * g;
-      mine[0] = bd.x; mine[1] = bd.y; mine[2] = bd.z; mine[3] = bd.w;
-      mine[4] = dims.x; mine[5] = dims.y;
-      dims_all.x = max(dims_all.x, dims.x);
-      dims_all.y = max(dims_all.y, dims.y);
-    }
-    if (gcount > 1) {
-      far = (P.group_verify & 2) ? 1 : 0;       // (tests: every unit as if its premise had failed)
-      for (int w = 0; w < waves; ++w) far |= misc[100 + w];
-      for (int g = 0; g < gcount; ++g)
-        far |= (abs(misc[16 + 8 * g] - misc[16 + 8 * gm]) > 1 ||
-                abs(misc[16 + 8 * g + 2] - misc[16 + 8 * gm + 2]) > 1) ? 1 : 0;
-    }
-    if (bad) atomicMax(&states[blockIdx.y].error, 1);
-    // (checked on the largest candidate grid of the unit: the accumulators of a group pass hold it)
-    const int count = dims_all.x * dims_all.y;
-    const int BW = dims_all.x + P.plane_i - 1, BH = dims_all.y + P.plane_j - 1;
-    // (block + 1 = bx * pitch + by + 1 travels in 16 bits, see the scoring loop)
-    const int ok = count <= P.coarse_stride && count <= kMaxCoarsePerScan && BW <= 255 &&
-                   BH <= 255 && (BW - 1) * (dims_all.y + 2 * P.plane_j - 2) + BH <= 65535 &&
-                   (dims_all.x + 2 * P.plane_i - 2) * (dims_all.y + 2 * P.plane_j - 2) <= acc_cap;
-    misc[1] = gcount; misc[2] = gm;
-    misc[4] = dims_all.x; misc[5] = dims_all.y;
-    misc[6] = ok;
-    misc[7] = far;
-    if (far) atomicAdd(&states[blockIdx.y].done_top, 1);      // (statistics: units without a group bound)
-    if (!ok) {
-      atomicMax(&states[blockIdx.y].error, 2);
-      for (int g = 0; g < gcount; ++g) P.scan_best[s0 + g] = make_int2(0, 0);
-    }
-  }
-  __syncthreads();
-  if (!misc[6]) return;
-  stamp(2);      // bounds known
-  FusedPass<kTimeline>(P, &states[blockIdx.y], n, acc_cap, s0, blockIdx.y * gridDim.x + blockIdx.x);
-  stamp(7);
-}
 
 // ---------------------------------------------------------------------------
 // Branch and bound
 // ---------------------------------------------------------------------------
-// Node lists (frontiers, leaves) are split into kSubLists sub-lists, each with
-// its own counter, so that thousands of blocks appending at once do not
-// serialise on one atomic word (one word sustains only ~90 atomics/us).
-constexpr int kSubLists = 64;
-
 constexpr int kMaxStages = kMaxDepth + 2;   // one frontier counter array per search stage
 
 // Sub-list counters sit one per 128-byte line: returning atomics on words of the same line
@@ -1326,23 +251,6 @@ __device__ __forceinline__ bool PickSeed(const Fast2DProblem& P, int n, int want
   __syncthreads();
   *scan_out = sh->found_scan;
   return sh->found_scan >= 0;
-}
-
-// Cell of point i of rotated scan `rot` = P.scan_rot[scan], packed (x | y << 16): the fused
-// front end's arithmetic (RotateZ twice, translation, CellIndexFast), so bit-identical to what
-// it scored -- and to PrepScansKernel's `discrete` array.
-__device__ __forceinline__ uint32_t ScanCell(const Fast2DProblem& P, float2 rot, int i) {
-  const float* __restrict__ xyz = P.xyz;
-  const float px = xyz[3 * i], py = xyz[3 * i + 1];
-  float ax = px, ay = py;
-  if (!(P.init_qw == 1.f && P.init_qz == 0.f)) RotateZ(P.init_qw, P.init_qz, px, py, &ax, &ay);
-  float bx, by;
-  RotateZ(rot.x, rot.y, ax, ay, &bx, &by);
-  const float x = bx + P.tx;
-  const float y = by + P.ty;
-  const int ix = CellIndexFast(P.max_y, y, P.res, P.inv_res);
-  const int iy = CellIndexFast(P.max_x, x, P.res, P.inv_res);
-  return (static_cast<uint32_t>(ix) & 0xffffu) | (static_cast<uint32_t>(iy) << 16);
 }
 
 // Problem- and scan-invariant data a block keeps on chip while it works on
@@ -2759,249 +1667,308 @@ SelectDepthOneKernel(const Fast2DProblem* __restrict__ problems,
   }
 }
 
+// ---------------------------------------------------------------------------
+// Host: the scratch block of a search
+// ---------------------------------------------------------------------------
+// d_misc: Counters | CountersSummary | SelectState[num] | BestLeaf[num] | ProblemState[num].
+// Everything behind the Counters -- the tail -- is what the host reads after a search: it travels
+// back in one D2H, or the selecting workgroup stores it into the caller's pinned buffer itself.
+// The one description of that layout, for the device block and for its pinned host copy.
+struct SearchTail {
+  static_assert(sizeof(Counters) % 16 == 0 && sizeof(CountersSummary) % 8 == 0, "alignment");
+  static size_t Bytes(int num) {
+    return sizeof(CountersSummary) +
+           num * (sizeof(SelectState) + sizeof(BestLeaf) + sizeof(ProblemState));
+  }
+  SearchTail() = default;
+  SearchTail(char* base, int num)
+      : base(base), bytes(Bytes(num)),
+        summary(reinterpret_cast<CountersSummary*>(base)),
+        sel(reinterpret_cast<SelectState*>(summary + 1)),
+        best(reinterpret_cast<BestLeaf*>(sel + num)),
+        states(reinterpret_cast<ProblemState*>(best + num)) {}
+  unsigned* words() const { return reinterpret_cast<unsigned*>(base); }
+  int num_words() const { return static_cast<int>(bytes / sizeof(unsigned)); }
+  char* base = nullptr;
+  size_t bytes = 0;
+  CountersSummary* summary = nullptr;
+  SelectState* sel = nullptr;
+  BestLeaf* best = nullptr;
+  ProblemState* states = nullptr;
+};
+size_t SearchMiscBytes(int num) { return sizeof(Counters) + SearchTail::Bytes(num); }
+
+// ---------------------------------------------------------------------------
+// Host: one search of a prepared batch
+// ---------------------------------------------------------------------------
+// What the strategies below share and hand to each other: the lists and the scratch block of the
+// call, and the state of the overflow fall-back (`strict`, `num_chunks`).
+struct SearchRun {
+  SearchRun(Workspace& ws, const PreparedBatch& batch, BatchResult* result);
+  // Stage k reads list k and appends to list k+1 (buffers ping-pong, counters
+  // do not: they are all zeroed by the first kernel of the call).
+  NodeList Front(int stage) const {
+    return NodeList{d_front[stage & 1], d_counters->frontier[stage], frontier_sub};
+  }
+  void Mark(const char* name) const { if (batch.trace) batch.trace->Mark(name); }
+  // Where the selecting workgroup stores the tail itself (null: the host fetches it).
+  unsigned* PublishTo() const { return direct ? h_tail.words() : nullptr; }
+  void FetchResults(bool published);
+  void PrepareStrictRetry();
+
+  Workspace& ws;
+  const PreparedBatch& batch;
+  BatchResult* result;
+  const int num, n, depth;
+  int frontier_capacity, frontier_sub;    // nodes per frontier buffer / per sub-list of one
+  // (the two frontier buffers: reserved by the strategy that runs)
+  Node2D* d_front[2] = {nullptr, nullptr};
+  NodeList leaf_list;
+  Counters* d_counters;
+  SearchTail d_tail, h_tail;
+  bool direct;                            // the last kernel stores the tail into h_tail itself
+  int strict = 0;                         // 1: prune ties, record only improving leaves
+  int num_chunks = 1;                     // the scans go through the level-synchronous path in chunks
+};
+
+SearchRun::SearchRun(Workspace& ws, const PreparedBatch& batch, BatchResult* result)
+    : ws(ws), batch(batch), result(result), num(batch.num_problems), n(batch.n),
+      depth(batch.h_problems[0].depth) {
+  // Nodes per frontier / leaf buffer.  The debug switch frontier_capacity shrinks the frontiers
+  // (tests only) so that the overflow -> strict, chunked retry is exercised.
+  const auto capacity = [](int v, int fallback) {
+    return v >= kSubLists ? std::min(v, fallback) / kSubLists * kSubLists : fallback;
+  };
+  // 64 K nodes per problem (a weak match keeps ~30 k lowest-resolution nodes alive), at
+  // least 2 M, at most 32 M (1 GB per buffer): HBM is not the scarce resource here, and
+  // an overflow costs a whole second, chunked pass (64 submaps: 34 -> 20 ms per scan).
+  const int frontier_default = static_cast<int>(
+      std::min<long long>(1ll << 25, std::max<long long>(1ll << 21, 65536ll * num)));
+  frontier_capacity = capacity(Debug().frontier_capacity, frontier_default);
+  frontier_sub = frontier_capacity / kSubLists;
+  const int leaf_capacity = capacity(0, 1 << 20);
+  Node2D* d_leaves = ws.dev[12].ReserveAs<Node2D>(leaf_capacity);
+  // Carved by ReserveSearchScratch before the first kernel of the call, which clears the
+  // counters.
+  d_counters = reinterpret_cast<Counters*>(batch.d_misc);
+  d_tail = SearchTail(batch.d_misc + sizeof(Counters), num);
+  leaf_list = NodeList{d_leaves, d_counters->leaves, leaf_capacity / kSubLists};
+  // One D2H for the counters' summary + selection state + best leaves.
+  h_tail = SearchTail(static_cast<char*>(ws.pinned[3].Reserve(SearchTail::Bytes(num))), num);
+  // (depth > 1: the selecting workgroup stores the tail into h_tail itself)
+  direct = Debug().no_direct_results == 0 && h_tail.bytes % sizeof(unsigned) == 0;
+}
+
+void SearchRun::FetchResults(bool published) {
+  if (!published)
+    SmallCopyAsync(h_tail.base, d_tail.base, h_tail.bytes, /*to_device=*/false, ws.stream);
+  const auto t0 = std::chrono::steady_clock::now();
+  CMX_HIP(hipStreamSynchronize(ws.stream));
+  g_host_wait_ns += std::chrono::duration_cast<std::chrono::nanoseconds>(
+                        std::chrono::steady_clock::now() - t0).count();
+}
+
+// Something was dropped (a full frontier / queue / leaf list).  Bounds found so far are real
+// leaf scores and stay valid; the search is repeated in strict mode (prunes ties, records
+// only improving leaves) over more, smaller chunks of scans.  The best leaf found so far is
+// re-found by lowering the bound one ulp.
+void SearchRun::PrepareStrictRetry() {
+  CMX_REQUIRE(num_chunks < (1 << 12), "branch-and-bound overflow not resolvable");
+  if (h_tail.summary->frontier_overflow) num_chunks *= 4;
+  strict = 1;
+  for (int p = 0; p < num; ++p) {
+    const float floor_score = std::max(batch.h_problems[p].min_score, 0.f);
+    unsigned floor_bits;
+    std::memcpy(&floor_bits, &floor_score, sizeof(float));
+    if (h_tail.states[p].best_bits > floor_bits) h_tail.states[p].best_bits -= 1;
+  }
+  CMX_HIP(hipMemcpyAsync(batch.d_states, h_tail.states, num * sizeof(ProblemState),
+                         hipMemcpyHostToDevice, ws.stream));
+  CMX_HIP(hipMemsetAsync(d_counters, 0, sizeof(Counters), ws.stream));
+}
+
+// depth == 1: the lowest-resolution candidates are the leaves, no tree.
+void RunDepthOne(SearchRun& run) {
+  Workspace& ws = run.ws;
+  SelectDepthOneKernel<<<run.num, 1024, 0, ws.stream>>>(
+      run.batch.d_problems, run.batch.d_states, run.n, run.d_tail.best, run.d_tail.states);
+  CMX_HIP(hipGetLastError());
+  RecordEvent(ws.ev_end, ws.stream);
+  run.FetchResults(false);
+}
+
+// Whether the work queue can take this batch: it holds a scan in registers (QueueSearchWanted), it
+// reads stored cells, and it gathers quads through buffer resources (2 GB per level).
+bool QueueSearchPossible(const SearchRun& run) {
+  bool queue_ok = QueueSearchWanted(run.n, run.num);
+  for (const Fast2DProblem& P : run.batch.h_problems) {
+    queue_ok = queue_ok && (P.recompute_scans == 0 || P.store_scans != 0);
+    for (int l = 0; l + 1 < run.depth; ++l)
+      queue_ok = queue_ok && static_cast<unsigned long long>((P.level[l].qy + 3) >> 2) *
+                                     static_cast<unsigned>(P.level[l].qtx) * 128ull < (1ull << 31);
+  }
+  return queue_ok;
+}
+
+// ---- the work queue: filter + ONE launch for the whole tree and the selection ---------
+// Takes over the caller's turn at the launch path (held since the dive) and gives it up behind
+// the tree launch, before it waits for the results.
+enum class QueueOutcome { kDone, kLeafOverflow, kQueueOverflow };
+
+QueueOutcome RunQueueSearch(SearchRun& run, std::unique_ptr<LaunchTurn> turn) {
+  Workspace& ws = run.ws;
+  const PreparedBatch& batch = run.batch;
+  BatchResult* result = run.result;
+  const int num = run.num, n = run.n;
+  // 16 K nodes per sub-queue (1 M nodes, 64 MB) for up to 16 problems, 64 K per problem
+  // beyond; slots are not reused within a call.
+  const long long wanted = std::max<long long>(1ll << 20, 65536ll * num);
+  int sub_capacity = static_cast<int>(std::min<long long>(wanted, 1ll << 23) / kQueues);
+  if (Debug().fast2d_queue_capacity > 0) sub_capacity = Debug().fast2d_queue_capacity;
+  TreeQueue queue;
+  queue.capacity = sub_capacity;
+  queue.slots = static_cast<unsigned long long*>(ws.tagged[0].Acquire(
+      static_cast<size_t>(kQueues) * sub_capacity * 8 * sizeof(unsigned long long), ws.stream,
+      &queue.epoch));
+  run.d_front[0] = ws.dev[10].ReserveAs<Node2D>(run.frontier_capacity);
+  FilterCoarseKernel<<<dim3(DivUp(batch.max_scans, 4), num), 256, 0, ws.stream>>>(
+      batch.d_problems, batch.d_states, n, 0, 1, /*strict=*/0, /*affinity=*/0, run.Front(0),
+      run.d_counters);
+  run.Mark("filter");
+  // (events only under the debug switch `timing`: RecordEvent is a no-op otherwise)
+  RecordEvent(ws.ev_x0, ws.stream);
+  // One workgroup per CU: 1024 wavefronts.  More of them shorten a single hard search (512
+  // workgroups: 240 against 290 us on the hardest of the bench's eight scans) and cost the
+  // eight-thread line more than that (17 200 against 19 300 matches/s): wavefronts that find
+  // nothing to steal are pure overhead for the searches that share the chip.
+  const int blocks = Debug().fast2d_queue_blocks > 0
+                         ? Debug().fast2d_queue_blocks
+                         : std::min(2048, 256 * std::max(1, (num + 3) / 4));
+  TreeQueueKernel<<<blocks, 256, 0, ws.stream>>>(
+      batch.d_problems, batch.d_states, n, run.Front(0), queue, run.leaf_list, run.d_counters,
+      run.d_tail.sel, run.d_tail.best, num, run.d_tail.states, run.d_tail.summary,
+      run.d_tail.words(), run.PublishTo(), run.h_tail.num_words(),
+      batch.trace && batch.trace->enabled() ? 1 : 0,
+      Debug().fast2d_queue_lost > 0 ? Debug().fast2d_queue_lost : 3);
+  run.Mark("queue");
+  CMX_HIP(hipGetLastError());
+  RecordEvent(ws.ev_x1, ws.stream);
+  result->expansion_launches = 1;
+  RecordEvent(ws.ev_end, ws.stream);
+  turn.reset();
+  run.FetchResults(run.direct);
+  const CountersSummary& h_counters = *run.h_tail.summary;
+  result->expansion_lookups = 64ll * h_counters.wave_gathers;
+  for (int p = 0; p < num; ++p)
+    for (int k = 0; k < kStatShards; ++k)
+      result->expansion_nodes += run.h_tail.states[p].expanded_shard[k];
+  if (h_counters.leaf_overflow) return QueueOutcome::kLeafOverflow;
+  if (h_counters.frontier_overflow) return QueueOutcome::kQueueOverflow;
+  return QueueOutcome::kDone;
+}
+
+// ---- the level-synchronous chain: filter, wave stages, subtree stages, selection ---------
+// Top of the tree per scan, then the subtrees of the survivors down to the leaves on many
+// blocks; over `run.num_chunks` chunks of scans, and once more in strict mode for as long as a
+// list overflows.
+void RunLevelSynchronous(SearchRun& run) {
+  Workspace& ws = run.ws;
+  const PreparedBatch& batch = run.batch;
+  BatchResult* result = run.result;
+  const int num = run.num, n = run.n;
+  const CountersSummary& h_counters = *run.h_tail.summary;
+  // Stage shape (tunable for experiments through the environment).
+  const int kLevelsPerStage = std::max(0, Debug().fast2d_levels_per_stage);
+  const int kWaveLevels = Debug().fast2d_wave_levels > 0 ? Debug().fast2d_wave_levels - 1 : -1;
+  // Single searches are latency-bound: one wave stage, then one depth-first
+  // kernel down to the leaves.  Batches are throughput-bound: two wave stages,
+  // then depth-first stages of two levels.
+  const int levels_per_stage = kLevelsPerStage > 0 ? kLevelsPerStage : (num < 4 ? kMaxDepth : 2);
+  const int wave_levels = kWaveLevels >= 0 ? kWaveLevels : (num < 4 ? 1 : 2);
+  // Frontier sizes are only known on the device; grids are sized for the
+  // typical case (a few thousand nodes at the top, tens below) and every
+  // kernel grid-strides, so larger frontiers (big batches) still fill the chip.
+  // Batches: one problem's nodes stay on one XCD (debug switch fast2d_xcd_affinity overrides).
+  const int affinity_override = Debug().fast2d_xcd_affinity;
+  const int affinity = affinity_override ? affinity_override - 1 : (num >= 16 ? 1 : 0);
+  const int wide_blocks = std::min(4096, 1024 * std::max(1, (num + 3) / 4));
+  const int narrow_blocks = std::min(4096, 512 * std::max(1, (num + 3) / 4));
+  run.d_front[0] = ws.dev[10].ReserveAs<Node2D>(run.frontier_capacity);
+  run.d_front[1] = ws.dev[11].ReserveAs<Node2D>(run.frontier_capacity);
+  for (;;) {
+    const int strict = run.strict;
+    for (int chunk = 0; chunk < run.num_chunks; ++chunk) {
+      if (chunk > 0 || strict)
+        CMX_HIP(hipMemsetAsync(run.d_counters->frontier, 0, sizeof(run.d_counters->frontier),
+                               ws.stream));
+      FilterCoarseKernel<<<dim3(DivUp(batch.max_scans, 4), num), 256, 0, ws.stream>>>(
+          batch.d_problems, batch.d_states, n, chunk, run.num_chunks, strict, affinity,
+          run.Front(0), run.d_counters);
+      run.Mark("filter");
+      int stage = 0;
+      int top = run.depth - 1;
+      // Wave-per-node level-synchronous expansion of the (wide, shallow-lived)
+      // top levels.  (Timed for the statistics in the first pass of a batch: there the
+      // expansion is the dominant kernel; a single search's chain of launches is not given
+      // two more event packets to wait behind.)
+      const bool timed = !strict && chunk == 0 && num >= 4;
+      if (timed) RecordEvent(ws.ev_x0, ws.stream);
+      for (int used = 0; used < wave_levels && top - 1 >= 1; ++used, --top, ++stage) {
+        ExpandWaveKernel<<<used == 0 ? wide_blocks : narrow_blocks, 256, 0, ws.stream>>>(
+            batch.d_problems, batch.d_states, n, run.Front(stage), strict, affinity,
+            run.Front(stage + 1), run.d_counters);
+        run.Mark("wave");
+      }
+      if (timed) {
+        RecordEvent(ws.ev_x1, ws.stream);
+        result->expansion_launches = stage;
+      }
+      // Block-per-node depth-first stages of kLevelsPerStage levels: the bushy
+      // part of the tree near the optimum spreads over many blocks instead of
+      // being walked serially by one.
+      for (; top > 0; top -= levels_per_stage, ++stage) {
+        const int stop = std::max(0, top - levels_per_stage);
+        SubtreeKernel<<<narrow_blocks, 256, 0, ws.stream>>>(
+            batch.d_problems, batch.d_states, n, run.Front(stage), stop, strict,
+            run.Front(stage + 1), run.leaf_list, run.d_counters);
+        run.Mark("subtree");
+      }
+    }
+    SelectBestKernel<<<1, 1024, 0, ws.stream>>>(
+        run.leaf_list, batch.d_states, run.d_tail.sel, run.d_tail.best, num, run.d_tail.states,
+        run.d_counters, run.d_tail.summary, run.d_tail.words(), run.PublishTo(),
+        run.h_tail.num_words());
+    run.Mark("select");
+    CMX_HIP(hipGetLastError());
+    RecordEvent(ws.ev_end, ws.stream);
+    run.FetchResults(run.direct);
+    if (!strict) {
+      for (int st = 0; st < result->expansion_launches; ++st)
+        result->expansion_nodes += h_counters.frontier_total[st];
+      result->expansion_lookups = 64ll * h_counters.wave_gathers;
+    }
+    if (!h_counters.frontier_overflow && !h_counters.leaf_overflow) break;
+    run.PrepareStrictRetry();
+  }
+}
+
+// (debug switch trace)
+void TraceListSizes(const CountersSummary& h_counters) {
+  fprintf(stderr, "[cmx trace] list sizes:");
+  for (int st = 0; st < kMaxStages; ++st)
+    if (h_counters.frontier_total[st])
+      fprintf(stderr, " frontier[%d]=%d", st, h_counters.frontier_total[st]);
+  long long leaves = 0;
+  for (int k = 0; k < kSubLists; ++k) leaves += h_counters.leaves[k];
+  fprintf(stderr, " leaves=%lld\n", leaves);
+  const unsigned* q = h_counters.queue_stats;
+  if (q[5])
+    fprintf(stderr, "[cmx trace] work queue: %u chains (%u nodes from the list, %u popped), %u "
+            "pushed, %u lost races, %u slot re-reads\n", q[5], q[4], q[0], q[3], q[1], q[2]);
+}
+
 }  // namespace
 
-// ---------------------------------------------------------------------------
-// Fast2DMatcher (host)
-// ---------------------------------------------------------------------------
-Fast2DMatcher::Fast2DMatcher(const cmx_fast2d_options& options, const cmx_grid2d_limits& limits,
-                             const uint16_t* cells, int device)
-    : options_(options), limits_(limits), device_(device) {
-  // CHECKs of the reference: SM2/fast_...2d.cc:100-102,174; map_limits.h:45-47;
-  // grid_2d.cc:73.
-  CMX_REQUIRE(cells != nullptr, "cells is null");
-  CMX_REQUIRE(options.branch_and_bound_depth >= 1 && options.branch_and_bound_depth <= kMaxDepth,
-              "branch_and_bound_depth %d outside [1,%d]", options.branch_and_bound_depth,
-              kMaxDepth);
-  CMX_REQUIRE(limits.resolution > 0., "resolution must be > 0");
-  CMX_REQUIRE(limits.num_x_cells >= 1 && limits.num_y_cells >= 1, "empty cell limits");
-  CMX_REQUIRE(limits.num_x_cells <= 16384 && limits.num_y_cells <= 16384,
-              "grid larger than 16384 cells per side is unsupported");
-  CMX_REQUIRE(limits.min_correspondence_cost < limits.max_correspondence_cost,
-              "min_correspondence_cost must be < max_correspondence_cost");
-  WorkspaceLease ws(device);
-  const int nx = limits.num_x_cells, ny = limits.num_y_cells;
-  const int depth = options.branch_and_bound_depth;
-  size_t total = 0;
-  level_offsets_.resize(depth);
-  levels_.resize(depth);
-  for (int i = 0; i < depth; ++i) {
-    const int w = 1 << i;
-    level_offsets_[i] = total;
-    levels_[i].wx = nx + w - 1;
-    levels_[i].wy = ny + w - 1;
-    total += (static_cast<size_t>(levels_[i].wx) * levels_[i].wy + 255) & ~size_t(255);
-  }
-  CMX_HIP(hipMalloc(&stack_mem_, total));
-  for (int i = 0; i < depth; ++i)
-    levels_[i].cells = static_cast<uint8_t*>(stack_mem_) + level_offsets_[i];
-  min_s_ = 1.f - limits.max_correspondence_cost;
-  const float max_s = 1.f - limits.min_correspondence_cost;
-  score_scale_ = (max_s - min_s_) / 255.f;
-
-  const size_t count = static_cast<size_t>(nx) * ny;
-  CMX_HIP(hipMalloc(reinterpret_cast<void**>(&grid_cells_), count * sizeof(uint16_t)));
-  uint16_t* d_cells = grid_cells_;
-  CMX_HIP(hipMemcpyAsync(d_cells, cells, count * sizeof(uint16_t), hipMemcpyHostToDevice,
-                         ws->stream));
-  BuildLevel0Kernel<<<DivUp(count, 256), 256, 0, ws->stream>>>(
-      d_cells, static_cast<int>(count), limits.min_correspondence_cost,
-      limits.max_correspondence_cost, const_cast<uint8_t*>(levels_[0].cells));
-  for (int i = 1; i < depth; ++i) {
-    const LevelDesc& prev = levels_[i - 1];
-    const LevelDesc& cur = levels_[i];
-    BuildLevelKernel<<<dim3(DivUp(cur.wx, 256), cur.wy), 256, 0, ws->stream>>>(
-        prev.cells, prev.wx, prev.wy, 1 << (i - 1), const_cast<uint8_t*>(cur.cells), cur.wx,
-        cur.wy);
-  }
-  // Quad layouts of every level that can be a child level (0 .. depth-2).
-  {
-    size_t quad_total = 0;
-    std::vector<size_t> quad_off(depth, 0);
-    for (int i = 0; i + 1 < depth; ++i) {
-      const int w = 1 << i;
-      levels_[i].qx = levels_[i].wx + w;
-      levels_[i].qy = levels_[i].wy + w;
-      levels_[i].qtx = (levels_[i].qx + 7) / 8;
-      quad_off[i] = quad_total;
-      // whole tiles of 32 dwords (128 bytes)
-      quad_total += static_cast<size_t>(levels_[i].qtx) * ((levels_[i].qy + 3) / 4) * 128;
-    }
-    levels_[depth - 1].quads = nullptr;
-    levels_[depth - 1].qx = levels_[depth - 1].qy = levels_[depth - 1].qtx = 0;
-    if (quad_total) {
-      CMX_HIP(hipMalloc(&quads_mem_, quad_total));
-      for (int i = 0; i + 1 < depth; ++i) {
-        LevelDesc& L = levels_[i];
-        uint32_t* q = reinterpret_cast<uint32_t*>(static_cast<char*>(quads_mem_) + quad_off[i]);
-        L.quads = q;
-        BuildQuadsKernel<<<dim3(DivUp(L.qx, 256), L.qy), 256, 0, ws->stream>>>(
-            L.cells, L.wx, L.wy, 1 << i, q, L.qx, L.qy, L.qtx);
-      }
-    }
-  }
-  // Phase planes of the lowest-resolution level.
-  {
-    const int w = 1 << (depth - 1);
-    const LevelDesc& top = levels_[depth - 1];
-    const int PI = (top.wx + w - 1) / w, PJ = (top.wy + w - 1) / w;
-    if (w <= kMaxPlaneWidth && PI * PJ <= kMaxPlaneCells) {
-      plane_i_ = PI;
-      plane_j_ = PJ;
-      plane_stride_ = (PI * PJ + 63) & ~63;
-      const size_t bytes = static_cast<size_t>(w * w + 1) * plane_stride_;
-      CMX_HIP(hipMalloc(reinterpret_cast<void**>(&planes_), bytes));
-      BuildPlanesKernel<<<w * w + 1, 64, 0, ws->stream>>>(top.cells, top.wx, top.wy, w, PI, PJ,
-                                                          plane_stride_, planes_);
-      // The same planes of the level dilated by two cells (group bounds of the fused front end),
-      // where the dilated image still fits the planes' PI x PJ lattice cells.
-      const int dwx = top.wx + 2 * kGroupDilation, dwy = top.wy + 2 * kGroupDilation;
-      if (plane_stride_ == 64 && depth > 1 && dwx <= PI * w && dwy <= PJ * w) {
-        uint8_t* dilated = ws->dev[0].ReserveAs<uint8_t>(static_cast<size_t>(dwx) * dwy);
-        DilateLevelKernel<<<dim3(DivUp(dwx, 256), dwy), 256, 0, ws->stream>>>(top.cells, top.wx,
-                                                                             top.wy, dilated);
-        CMX_HIP(hipMalloc(reinterpret_cast<void**>(&planes_group_), bytes));
-        BuildPlanesKernel<<<w * w + 1, 64, 0, ws->stream>>>(dilated, dwx, dwy, w, PI, PJ,
-                                                            plane_stride_, planes_group_);
-      }
-    }
-  }
-  CMX_HIP(hipGetLastError());
-  CMX_HIP(hipStreamSynchronize(ws->stream));
-}
-
-Fast2DMatcher::~Fast2DMatcher() {
-  (void)hipSetDevice(device_);
-  if (stack_mem_) (void)hipFree(stack_mem_);
-  if (quads_mem_) (void)hipFree(quads_mem_);
-  if (planes_) (void)hipFree(planes_);
-  if (planes_group_) (void)hipFree(planes_group_);
-  if (grid_cells_) (void)hipFree(grid_cells_);
-}
-
-void FillRotationTable(double step, int num_angular, float2* out) {
-  // delta_theta accumulates in f64, each angle is narrowed to f32 for AngleAxisf.
-  const int num_scans = 2 * num_angular + 1;
-  double delta_theta = -num_angular * step;
-  for (int s = 0; s < num_scans; ++s, delta_theta += step) {
-    const float ha = 0.5f * static_cast<float>(delta_theta);
-    out[s] = make_float2(std::cos(ha), std::sin(ha) * 1.f);
-  }
-}
-
-std::shared_ptr<const std::vector<float2>> HostRotationTable(double step, int num_angular) {
-  struct Entry {
-    double step;
-    int num_angular;
-    std::shared_ptr<const std::vector<float2>> table;
-  };
-  static std::mutex mu;
-  static std::vector<Entry>* cache = new std::vector<Entry>;   // most recent last
-  {
-    std::lock_guard<std::mutex> lock(mu);
-    for (size_t i = cache->size(); i-- > 0;) {
-      if ((*cache)[i].step == step && (*cache)[i].num_angular == num_angular)
-        return (*cache)[i].table;
-    }
-  }
-  const int num_scans = 2 * num_angular + 1;
-  auto table = std::make_shared<std::vector<float2>>(num_scans);
-  FillRotationTable(step, num_angular, table->data());
-  std::lock_guard<std::mutex> lock(mu);
-  if (cache->size() >= 64) cache->erase(cache->begin());      // bound the cache
-  cache->push_back(Entry{step, num_angular, table});
-  return table;
-}
-
-namespace {
-
-// SearchParameters ctor (SM2/correlative_scan_matcher_2d.cc:27-55), host side.
-struct HostSearch {
-  int num_angular;
-  double step;
-  int num_scans;
-  int nl;
-};
-HostSearch MakeSearch(double linear_window, double angular_window, float max_range_xy,
-                      double resolution) {
-  float max_scan_range = 3.f * resolution;
-  max_scan_range = std::max(max_range_xy, max_scan_range);
-  const double kSafetyMargin = 1. - 1e-3;
-  const float range_sq = max_scan_range * (max_scan_range * 1.f);
-  const double res_sq = resolution * (resolution * 1.);
-  HostSearch h;
-  h.step = kSafetyMargin * std::acos(1. - res_sq / (2. * range_sq));
-  h.num_angular = std::ceil(angular_window / h.step);
-  h.num_scans = 2 * h.num_angular + 1;
-  h.nl = std::ceil(linear_window / resolution);
-  return h;
-}
-
-float MaxRangeXY(const float* xyz, int n) {
-  float m = 0.f;
-  for (int i = 0; i < n; ++i) {
-    const float x = xyz[3 * i], y = xyz[3 * i + 1];
-    m = std::max(m, std::sqrt(x * x + y * y));
-  }
-  return m;
-}
-
-struct PreparedBatch {
-  StageTrace* trace = nullptr;
-  int num_problems = 0;
-  int n = 0;
-  int max_scans = 0;
-  long long plane_acc_cells = 0;   // LDS accumulators the plane kernel needs (upper bound)
-  std::vector<HostSearch> search;
-  std::vector<cmx_pose2d> initial;
-  Fast2DProblem* d_problems = nullptr;
-  ProblemState* d_states = nullptr;
-  std::vector<Fast2DProblem> h_problems;
-  // Search scratch carved before the first kernel so that it can clear the counters.
-  char* d_misc = nullptr;          // Counters | SelectState[num] | BestLeaf[num] | ProblemState[num]
-  bool write_all_discrete = false; // debug entry point: keep every discretised scan
-  unsigned long long* d_timeline = nullptr;   // CMX_TIMELINE=1
-  int timeline_blocks = 0;
-  // The fused front end's launch, kept for the exact re-run of a problem whose leaves tie
-  // (RescoreExact): under group bounds the lowest-resolution scores are bounds.
-  bool any_group = false;
-  size_t fused_lds = 0;
-  int fused_acc = 0, fused_threads = 0;
-  const float* d_xyz = nullptr;
-};
-
-// The debug switch fast2d_unfused routes every problem through the separate prep / score
-// launches (the fallback of problems the fused kernel does not take); parity tests run both.
-bool FusedEnabled() { return Debug().fast2d_unfused == 0; }
-
-// Blocks of PrepScoreFusedKernel the whole chip holds at once (occupancy query, cached).
-long long FusedResidentBlocks(int device, int threads, size_t lds_bytes) {
-  struct Key { int device, threads; size_t lds; long long blocks; };
-  static std::mutex mu;
-  static std::vector<Key>* cache = new std::vector<Key>;
-  const size_t lds = (lds_bytes + 1023) & ~size_t(1023);
-  {
-    std::lock_guard<std::mutex> lock(mu);
-    for (const Key& k : *cache)
-      if (k.device == device && k.threads == threads && k.lds == lds) return k.blocks;
-  }
-  int per_cu = 0, cus = 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, PrepScoreFusedKernel<false>, threads, lds) !=
-          hipSuccess ||
-      hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess) {
-    (void)hipGetLastError();
-    return 0;
-  }
-  // (one fewer per CU than the API says: it over-reports by one for some SGPR counts,
-  // MI355X_MICROARCH.md "Residency and cooperative launch")
-  const long long blocks = static_cast<long long>(std::max(per_cu - 1, 0)) * cus;
-  std::lock_guard<std::mutex> lock(mu);
-  if (cache->size() < 256) cache->push_back(Key{device, threads, lds, blocks});
-  return blocks;
-}
-
-// Uploads problem descriptors, carves scratch and runs the preparation +
-// lowest-resolution scoring kernels.  `d_xyz` is the device point cloud.
 // The work-queue tree search (TreeQueueKernel) holds a scan in registers, 16 cells per lane.
 // Debug switch fast2d_queue: 2 = the chain of level-synchronous launches of rounds 2 - 5 (the
 // parity partner, and the path a queue overflow falls back to).
@@ -3011,1128 +1978,64 @@ bool QueueSearchWanted(int n, int num) {
   return Debug().fast2d_queue != 2 && n <= kChainCells * kWave && (num < 4 || Debug().fast2d_queue == 1);
 }
 
-void PrepareAndScoreCoarse(Workspace& ws, const Fast2DMatcher* const* matchers, int num,
-                           const cmx_pose2d* initial_or_null, bool full_submap,
-                           const float* d_xyz, int n, float max_range_xy, float min_score,
-                           PreparedBatch* out, const int32_t* full_flags = nullptr,
-                           const float* min_scores = nullptr) {
-  // Mixed batches (the ConstraintBuilder front): per-problem full-submap flag and
-  // acceptance threshold override the uniform ones.
-  const auto is_full = [&](int p) { return full_flags ? full_flags[p] != 0 : full_submap; };
-  const auto min_of = [&](int p) { return min_scores ? min_scores[p] : min_score; };
-  out->num_problems = num;
-  out->n = n;
-  out->search.resize(num);
-  out->initial.resize(num);
-  out->h_problems.resize(num);
-
-  // Per-problem search parameters and scratch sizes.
-  size_t discrete_total = 0, scans_total = 0, coarse_total = 0;
-  // Rotation tables (host libm values, cached process-wide) of the distinct
-  // (step, num_angular) pairs of this batch; they travel in the problem upload.
-  struct Rotation { double step; int num_angular; std::shared_ptr<const std::vector<float2>> table; size_t offset; };
-  std::vector<Rotation> rotations;
-  std::vector<int> rotation_of(num);
-  size_t rotation_floats = 0;
-  const bool fused_enabled = FusedEnabled();
-  const int n_pad = (n + 63) & ~63;
-  long long fused_acc = 0;
-  bool any_fused = false, any_unfused = false;
-  for (int p = 0; p < num; ++p) {
-    const Fast2DMatcher& m = *matchers[p];
-    const cmx_grid2d_limits& lim = m.limits();
-    HostSearch h;
-    cmx_pose2d init;
-    if (is_full(p)) {
-      // SM2/fast_...2d.cc:213-222.
-      h = MakeSearch(1e6 * lim.resolution, M_PI, max_range_xy, lim.resolution);
-      init.x = lim.max_x - 0.5 * lim.resolution * lim.num_y_cells;
-      init.y = lim.max_y - 0.5 * lim.resolution * lim.num_x_cells;
-      init.theta = 0.;
-    } else {
-      h = MakeSearch(m.options().linear_search_window, m.options().angular_search_window,
-                     max_range_xy, lim.resolution);
-      init = initial_or_null[p];
-    }
-    CMX_REQUIRE(h.num_scans >= 1 && h.num_scans < (1 << 20), "unsupported number of scans %d",
-                h.num_scans);
-    out->search[p] = h;
-    out->initial[p] = init;
-    int r = -1;
-    for (size_t k = 0; k < rotations.size(); ++k)
-      if (rotations[k].step == h.step && rotations[k].num_angular == h.num_angular) r = static_cast<int>(k);
-    if (r < 0) {
-      r = static_cast<int>(rotations.size());
-      rotations.push_back(Rotation{h.step, h.num_angular, HostRotationTable(h.step, h.num_angular),
-                                   rotation_floats});
-      rotation_floats += 2 * static_cast<size_t>(h.num_scans);
-    }
-    rotation_of[p] = r;
-    discrete_total += static_cast<size_t>(h.num_scans) * n;
-    scans_total += h.num_scans + 1;
-    // Upper bound of lowest-resolution candidates per scan: the shrunk window
-    // never exceeds nx-1 plus the cell spread of the scan, nor 2*nl.
-    const int step = 1 << (m.depth() - 1);
-    const double spread_cells = 2.0 * (std::max(max_range_xy, 0.f) / lim.resolution + 2.0);
-    auto per_axis = [&](int cells) {
-      const double width = std::min(2.0 * h.nl, cells - 1 + spread_cells);
-      return static_cast<long long>(width / step) + 2;
-    };
-    const long long ax = per_axis(lim.num_x_cells), ay = per_axis(lim.num_y_cells);
-    const long long cap = ax * ay * h.num_scans;
-    CMX_REQUIRE(cap < (1ll << 30), "search too large: %lld lowest-resolution candidates", cap);
-    Fast2DProblem& P = out->h_problems[p];
-    P.coarse_capacity = static_cast<int>(cap);
-    P.coarse_stride = static_cast<int>(ax * ay);
-    P.use_planes = m.planes() != nullptr && ax * ay <= kMaxCoarsePerScan &&
-                   (ax + m.plane_i() - 1) * (ay + m.plane_j() - 1) <= kMaxBuckets &&
-                   ax + m.plane_i() - 1 <= 255 && ay + m.plane_j() - 1 <= 255 &&   // 8-bit bx, by
-                   (ax + 2 * m.plane_i() - 2) * (ay + 2 * m.plane_j() - 2) <= kMaxAccCells &&
-                   m.depth() > 1;
-    const long long acc = (ax + 2 * m.plane_i() - 2) * (ay + 2 * m.plane_j() - 2);
-    if (P.use_planes)
-      out->plane_acc_cells = std::max<long long>(out->plane_acc_cells, acc);
-    // Fused front end: 64-byte planes, the scan + the accumulators within the 64 KB of
-    // dynamic LDS a launch gets without opting in to more.
-    // (... and the lattice block of a point + 1 within 16 bits: the fused kernel's point words)
-    P.use_fused = fused_enabled && P.use_planes && m.plane_stride() == 64 &&
-                  n <= kFusedMaxPoints && 4ll * n_pad + 4 * (kFusedMisc + acc) + 1024 <= 64 * 1024 &&
-                  (ax + m.plane_i() - 2) * (ay + 2 * m.plane_j() - 2) + (ay + m.plane_j() - 1) <= 65535;
-    if (P.use_fused) {
-      any_fused = true;
-      fused_acc = std::max(fused_acc, acc);
-    } else {
-      any_unfused = true;
-    }
-    P.write_all_discrete = out->write_all_discrete ? 1 : 0;
-    // Group bounds: three rotations per workgroup, one sum over the dilated level (the kernel's
-    // long comment).  Not for the callers that need every exact lowest-resolution score
-    // (introspection, depth 1), not where two cells of dilation are a large part of the
-    // lowest-resolution window (below 16 cells the bounds stop excluding anything).
-    // fast2d_group: 1 never, 2 whenever the planes exist.
-    {
-      const int sw = Debug().fast2d_group;
-      const bool wanted = sw == 1 ? false : sw == 2 ? true : m.depth() >= 5;
-      P.group = (wanted && P.use_fused && m.planes_group() != nullptr && m.depth() > 1 &&
-                 !out->write_all_discrete && h.num_scans >= kFusedGroup &&
-                 4ll * kFusedGroup * n_pad + 4 * (kFusedMisc + acc) + 1024 <= 64 * 1024)
-                    ? kFusedGroup : 1;
-      P.group_verify = Debug().fast2d_group_verify;
-      if (P.group > 1) out->any_group = true;
-    }
-    P.timeline = nullptr;
-    coarse_total += cap;
-  }
-
-  // Scratch carving.  The bucketed records exist in HBM only for unfused problems.
-  uint32_t* d_discrete =
-      ws.dev[2].ReserveAs<uint32_t>(discrete_total + (any_unfused ? 2 * discrete_total + 2 : 0));
-  uint2* d_sorted = reinterpret_cast<uint2*>(d_discrete + discrete_total + (discrete_total & 1));
-  int4* d_bounds = ws.dev[3].ReserveAs<int4>(scans_total);
-  int2* d_dims = ws.dev[4].ReserveAs<int2>(2 * scans_total);
-  int2* d_scan_best = d_dims + scans_total;
-  int* d_sorted_count = ws.dev[5].ReserveAs<int>(scans_total);
-  float* d_cscore = ws.dev[6].ReserveAs<float>(coarse_total);
-  int* d_csum = ws.dev[7].ReserveAs<int>(coarse_total);
-  const size_t problems_bytes = (num * sizeof(Fast2DProblem) + 255) & ~size_t(255);
-  const size_t states_bytes = (num * sizeof(ProblemState) + 255) & ~size_t(255);
-  const size_t upload_bytes = problems_bytes + states_bytes + rotation_floats * sizeof(float);
-  char* d_upload = static_cast<char*>(ws.dev[8].Reserve(upload_bytes));
-  out->d_problems = reinterpret_cast<Fast2DProblem*>(d_upload);
-  out->d_states = reinterpret_cast<ProblemState*>(d_upload + problems_bytes);
-  const float* d_rotations = reinterpret_cast<const float*>(d_upload + problems_bytes + states_bytes);
-  char* h_upload = static_cast<char*>(ws.pinned[1].Reserve(upload_bytes));
-  Fast2DProblem* h_prob = reinterpret_cast<Fast2DProblem*>(h_upload);
-  ProblemState* h_state = reinterpret_cast<ProblemState*>(h_upload + problems_bytes);
-  float* h_rotations = reinterpret_cast<float*>(h_upload + problems_bytes + states_bytes);
-  for (const Rotation& r : rotations)
-    std::memcpy(h_rotations + r.offset, r.table->data(), r.table->size() * sizeof(float2));
-
-  if (TimelineEnabled() && any_fused) {
-    int max_scans = 0;
-    for (const HostSearch& h : out->search) max_scans = std::max(max_scans, h.num_scans);
-    out->timeline_blocks = (max_scans + 255) / 256 * 256 * num;
-    const size_t bytes = static_cast<size_t>(out->timeline_blocks) * kTimelineStamps * 8;
-    out->d_timeline = static_cast<unsigned long long*>(ws.dev[15].Reserve(bytes));
-    CMX_HIP(hipMemsetAsync(out->d_timeline, 0, bytes, ws.stream));
-  }
-  // Batches and the work-queue search keep the cells of surviving scans (debug switch
-  // fast2d_store_scans overrides).
-  const int store_override = Debug().fast2d_store_scans;
-  const int store_scans =
-      store_override ? store_override - 1 : ((num >= 4 || QueueSearchWanted(n, num)) ? 1 : 0);
-  size_t disc_off = 0, scan_off = 0, coarse_off = 0;
-  for (int p = 0; p < num; ++p) {
-    const Fast2DMatcher& m = *matchers[p];
-    const cmx_grid2d_limits& lim = m.limits();
-    const HostSearch& h = out->search[p];
-    Fast2DProblem& P = out->h_problems[p];
-    P.timeline = out->d_timeline;
-    P.xyz = d_xyz;
-    P.recompute_scans = (P.use_fused && !P.write_all_discrete) ? 1 : 0;
-    P.store_scans = store_scans;
-    for (int i = 0; i < m.depth(); ++i) P.level[i] = m.level(i);
-    P.depth = m.depth();
-    P.nx = lim.num_x_cells; P.ny = lim.num_y_cells;
-    P.nl = h.nl;
-    P.res = lim.resolution; P.max_x = lim.max_x; P.max_y = lim.max_y;
-    P.tx = static_cast<float>(out->initial[p].x);
-    P.ty = static_cast<float>(out->initial[p].y);
-    {  // Quaternion(AngleAxisf(initial_rotation.cast<float>().angle(), Z))
-      const float ha = 0.5f * static_cast<float>(out->initial[p].theta);
-      P.init_qw = std::cos(ha);
-      P.init_qz = std::sin(ha) * 1.f;
-    }
-    P.num_scans = h.num_scans;
-    P.inv_res = 1.0 / P.res;
-    P.scan_rot = reinterpret_cast<const float2*>(d_rotations + rotations[rotation_of[p]].offset);
-    P.min_s = m.min_s();
-    P.score_scale = m.score_scale();
-    P.min_score = min_of(p);
-    P.planes = m.planes();
-    P.planes_group = m.planes_group();
-    P.plane_i = m.plane_i();
-    P.plane_j = m.plane_j();
-    P.plane_stride = m.plane_stride();
-    P.discrete = d_discrete + disc_off;
-    P.sorted = d_sorted + disc_off;
-    P.bounds = d_bounds + scan_off;
-    P.coarse_dims = d_dims + scan_off;
-    P.scan_best = d_scan_best + scan_off;
-    P.sorted_count = d_sorted_count + scan_off;
-    P.coarse_score = d_cscore + coarse_off;
-    P.coarse_sum = d_csum + coarse_off;
-    h_prob[p] = P;
-    std::memset(&h_state[p], 0, sizeof(ProblemState));
-    const float bound = std::max(min_of(p), 0.f);
-    std::memcpy(&h_state[p].best_bits, &bound, sizeof(float));
-    disc_off += static_cast<size_t>(h.num_scans) * n;
-    scan_off += h.num_scans + 1;
-    coarse_off += P.coarse_capacity;
-    out->max_scans = std::max(out->max_scans, h.num_scans);
-  }
-  // (from here to the end of this function: the call's turn at the runtime's launch path)
-  LaunchTurn turn;
-  // One H2D for the problem descriptors, their initial states and the rotation tables.
-  SmallCopyAsync(d_upload, h_upload, upload_bytes, /*to_device=*/true, ws.stream);
-
-  const dim3 per_scan(out->max_scans, num);
-  auto mark = [&](const char* name) { if (out->trace) out->trace->Mark(name); };
-  mark("upload");
-  // Whichever kernel runs first clears the search's list counters.
-  int* clear_words = reinterpret_cast<int*>(out->d_misc);
-  const int clear_count = out->d_misc ? static_cast<int>(sizeof(Counters) / sizeof(int)) : 0;
-  RecordEvent(ws.ev_k0, ws.stream);
-  if (any_fused) {
-    // Threads per block: with 192 (three waves) ten blocks fit a CU, i.e. a single search's
-    // ~2300 rotations are all resident at once and the launch takes one block's latency;
-    // batches run several rounds anyway and use full 256-thread blocks.
-    // (units of a launch: rotations, or groups of three; a batch that mixes both is sized for
-    // single rotations -- surplus workgroups of a grouped problem return at once)
-    bool all_group = true;
-    for (const Fast2DProblem& P : out->h_problems) all_group = all_group && (!P.use_fused || P.group > 1);
-    const int per_unit = all_group ? kFusedGroup : 1;
-    const int units = (out->max_scans + per_unit - 1) / per_unit;
-    const long long blocks = static_cast<long long>(units) * num;
-    // pts | misc | candidate sums | 64 point words per wavefront (at most four)
-    const size_t lds = 4 * static_cast<size_t>(n_pad) * (out->any_group ? kFusedGroup : 1) +
-                       4 * static_cast<size_t>(kFusedMisc + fused_acc) + 4 * 256;
-    out->fused_lds = lds;
-    out->fused_acc = static_cast<int>(fused_acc);
-    out->d_xyz = d_xyz;
-    int threads = 256;
-    for (int t : {256, 192, 128}) {
-      if (blocks <= FusedResidentBlocks(ws.device, t, lds)) { threads = t; break; }
-    }
-    if (Debug().fast2d_fused_threads > 0) threads = Debug().fast2d_fused_threads;   // experiments
-    if (out->trace && out->trace->enabled())
-      fprintf(stderr, "[cmx trace] fused front end: %lld blocks x %d threads, %zu B LDS\n", blocks,
-              threads, lds);
-    // (grid.x rounded up to a multiple of 256 for the rotation -> block map of the kernel)
-    const dim3 fused_grid((units + 255) / 256 * 256, num);
-    out->fused_threads = threads;
-    if (out->any_group && (Debug().fast2d_group_verify & 1)) {
-      // Verification of the group bounds: first every rotation on the level itself (the same
-      // descriptors with group = 1; the exact sums stay in coarse_sum), then the launch proper,
-      // which compares every bound with them (error 3).
-      std::vector<Fast2DProblem> exact(out->h_problems);
-      for (Fast2DProblem& P : exact) { P.group = 1; P.store_scans = 0; }
-      Fast2DProblem* d_exact = ws.dev[16].ReserveAs<Fast2DProblem>(num);
-      CMX_HIP(hipMemcpyAsync(d_exact, exact.data(), num * sizeof(Fast2DProblem), hipMemcpyHostToDevice,
-                             ws.stream));
-      CMX_HIP(hipStreamSynchronize(ws.stream));        // (`exact` is a local)
-      const dim3 exact_grid((out->max_scans + 255) / 256 * 256, num);
-      PrepScoreFusedKernel<false><<<exact_grid, threads, lds, ws.stream>>>(
-          d_exact, d_xyz, n, out->d_states, static_cast<int>(fused_acc), clear_words, clear_count);
-      clear_words = nullptr;
-    }
-    (out->d_timeline ? PrepScoreFusedKernel<true> : PrepScoreFusedKernel<false>)
-        <<<fused_grid, threads, lds, ws.stream>>>(out->d_problems, d_xyz, n, out->d_states,
-                                                  static_cast<int>(fused_acc), clear_words,
-                                                  clear_count);
-    clear_words = nullptr;
-    mark("fused");
-  }
-  if (any_unfused) {
-    PrepScansKernel<<<per_scan, 256, 0, ws.stream>>>(out->d_problems, d_xyz, n, out->d_states,
-                                                     clear_words, clear_count);
-    mark("prep");
-    bool any_generic = false;
-    int chunk_mask = 0;
-    for (const Fast2DProblem& P : out->h_problems) {
-      if (P.use_fused) continue;
-      if (P.use_planes) chunk_mask |= 1 << (P.plane_stride >> 6);
-      else any_generic = true;
-    }
-    const size_t acc_bytes = static_cast<size_t>(out->plane_acc_cells) * sizeof(int);
-    const int plane_threads = 256;
-    if (chunk_mask & (1 << 1))
-      ScoreCoarsePlanesDwordKernel<<<per_scan, plane_threads, acc_bytes, ws.stream>>>(
-          out->d_problems, n, out->d_states);
-    if (chunk_mask & (1 << 2))
-      ScoreCoarsePlanesKernel<2><<<per_scan, plane_threads, acc_bytes, ws.stream>>>(
-          out->d_problems, n, out->d_states);
-    if (chunk_mask & (1 << 3))
-      ScoreCoarsePlanesKernel<3><<<per_scan, plane_threads, acc_bytes, ws.stream>>>(
-          out->d_problems, n, out->d_states);
-    if (chunk_mask & (1 << 4))
-      ScoreCoarsePlanesKernel<4><<<per_scan, plane_threads, acc_bytes, ws.stream>>>(
-          out->d_problems, n, out->d_states);
-    if (any_generic)
-      ScoreCoarseGenericKernel<<<per_scan, 256, 0, ws.stream>>>(out->d_problems, n, out->d_states);
-    mark("coarse");
-  }
-  RecordEvent(ws.ev_k1, ws.stream);
-  CMX_HIP(hipGetLastError());
-}
-
-struct BatchResult {
-  std::vector<BestLeaf> best;
-  std::vector<ProblemState> states;
-  double device_ms = 0., dominant_ms = 0.;
-  double expansion_ms = 0.;          // wave-per-node stages of the first pass
-  int expansion_launches = 0;
-  long long expansion_nodes = 0, expansion_lookups = 0;
-};
-
-struct ScoreIndex;
-void ResolveDepthOne(const PreparedBatch& batch, std::vector<BestLeaf>* best,
-                     const std::vector<ProblemState>& states);
-void ResolveTies(Workspace& ws, const PreparedBatch& batch, const NodeList& leaves_dev,
-                 const CountersSummary& h_counters, std::vector<BestLeaf>* best,
-                 const std::vector<ProblemState>& states);
-
-// d_misc: Counters | CountersSummary | SelectState[num] | BestLeaf[num] | ProblemState[num];
-// everything after the Counters travels back in one D2H.
-size_t SearchTailBytes(int num) {
-  return sizeof(CountersSummary) +
-         num * (sizeof(SelectState) + sizeof(BestLeaf) + sizeof(ProblemState));
-}
-size_t SearchMiscBytes(int num) { return sizeof(Counters) + SearchTailBytes(num); }
+// Carved before the first kernel of a call so that it can clear the counters.
 void ReserveSearchScratch(Workspace& ws, int num, PreparedBatch* batch) {
   batch->d_misc = static_cast<char*>(ws.dev[14].Reserve(SearchMiscBytes(num)));
+  batch->num_counter_words = static_cast<int>(sizeof(Counters) / sizeof(int));
 }
 
-// Full search of a prepared batch.
 // (debug switch host_trace: where a caller's wall clock goes -- tools only)
 thread_local long long g_host_wait_ns = 0;
-std::atomic<long long> g_host_calls{0}, g_host_total_ns{0}, g_host_waited_ns{0};
 
+// Full search of a prepared batch: picks the strategy and performs the fall-backs.
 void RunBranchAndBound(Workspace& ws, const PreparedBatch& batch, BatchResult* result) {
-  const int num = batch.num_problems, n = batch.n;
+  const int num = batch.num_problems;
   const int depth = batch.h_problems[0].depth;
   for (const Fast2DProblem& P : batch.h_problems)
     CMX_REQUIRE(P.depth == depth, "all matchers of a batch must share branch_and_bound_depth");
-
-  // Nodes per frontier / leaf buffer.  The debug switch frontier_capacity shrinks the frontiers
-  // (tests only) so that the overflow -> strict, chunked retry below is exercised.
-  const auto capacity = [](int v, int fallback) {
-    return v >= kSubLists ? std::min(v, fallback) / kSubLists * kSubLists : fallback;
-  };
-  // 64 K nodes per problem (a weak match keeps ~30 k lowest-resolution nodes alive), at
-  // least 2 M, at most 32 M (1 GB per buffer): HBM is not the scarce resource here, and
-  // an overflow costs a whole second, chunked pass (64 submaps: 34 -> 20 ms per scan).
-  const int frontier_default = static_cast<int>(
-      std::min<long long>(1ll << 25, std::max<long long>(1ll << 21, 65536ll * num)));
-  const int kFrontierCapacity = capacity(Debug().frontier_capacity, frontier_default);
-  const int kLeafCapacity = capacity(0, 1 << 20);
-  const int kFrontierSub = kFrontierCapacity / kSubLists, kLeafSub = kLeafCapacity / kSubLists;
-  // (the two frontier buffers of the level-synchronous path: reserved when that path runs)
-  Node2D* d_front[2] = {nullptr, nullptr};
-  Node2D* d_leaves = ws.dev[12].ReserveAs<Node2D>(kLeafCapacity);
-  // Carved by ReserveSearchScratch before the first kernel of the call, which clears the
-  // counters.
-  static_assert(sizeof(Counters) % 16 == 0 && sizeof(CountersSummary) % 8 == 0, "alignment");
-  char* d_misc = batch.d_misc;
-  Counters* d_counters = reinterpret_cast<Counters*>(d_misc);
-  char* d_tail = d_misc + sizeof(Counters);
-  CountersSummary* d_summary = reinterpret_cast<CountersSummary*>(d_tail);
-  SelectState* d_sel = reinterpret_cast<SelectState*>(d_tail + sizeof(CountersSummary));
-  BestLeaf* d_best = reinterpret_cast<BestLeaf*>(d_tail + sizeof(CountersSummary) +
-                                                 num * sizeof(SelectState));
-  ProblemState* d_states_out = reinterpret_cast<ProblemState*>(
-      d_tail + sizeof(CountersSummary) + num * (sizeof(SelectState) + sizeof(BestLeaf)));
-  auto mark = [&](const char* name) { if (batch.trace) batch.trace->Mark(name); };
-  // Stage k reads list k and appends to list k+1 (buffers ping-pong, counters
-  // do not: they are all zeroed by the one memset above).
-  auto front = [&](int stage) {
-    return NodeList{d_front[stage & 1], d_counters->frontier[stage], kFrontierSub};
-  };
-  const NodeList leaf_list = {d_leaves, d_counters->leaves, kLeafSub};
-
-  // One D2H for the counters' summary + selection state + best leaves.
-  const size_t misc_bytes = SearchTailBytes(num);
-  char* h_misc = static_cast<char*>(ws.pinned[3].Reserve(misc_bytes));
-  CountersSummary* h_counters = reinterpret_cast<CountersSummary*>(h_misc);
-  BestLeaf* h_best = reinterpret_cast<BestLeaf*>(h_misc + sizeof(CountersSummary) +
-                                                 num * sizeof(SelectState));
-  ProblemState* h_states = reinterpret_cast<ProblemState*>(
-      h_misc + sizeof(CountersSummary) + num * (sizeof(SelectState) + sizeof(BestLeaf)));
-  // (depth > 1: SelectBestKernel stores the tail into h_misc itself)
-  const bool direct = Debug().no_direct_results == 0 && misc_bytes % sizeof(unsigned) == 0;
-  auto fetch_results = [&](bool published) {
-    if (!published) SmallCopyAsync(h_misc, d_tail, misc_bytes, /*to_device=*/false, ws.stream);
-    const auto t0 = std::chrono::steady_clock::now();
-    CMX_HIP(hipStreamSynchronize(ws.stream));
-    g_host_wait_ns += std::chrono::duration_cast<std::chrono::nanoseconds>(
-                          std::chrono::steady_clock::now() - t0).count();
-  };
-
+  SearchRun run(ws, batch, result);
   if (depth == 1) {
-    SelectDepthOneKernel<<<num, 1024, 0, ws.stream>>>(batch.d_problems, batch.d_states, n, d_best,
-                                                      d_states_out);
-    CMX_HIP(hipGetLastError());
-    RecordEvent(ws.ev_end, ws.stream);
-    fetch_results(false);
+    RunDepthOne(run);
   } else {
-    // ---- dive -------------------------------------------------------------
     // (the launches of the search proper: one turn from the dive to the tree launch)
     std::unique_ptr<LaunchTurn> turn(new LaunchTurn);
     DiveKernel<<<dim3(kSeedsPerProblem * (batch.any_group ? kFusedGroup : 1), num), 256, 0, ws.stream>>>(
-        batch.d_problems, batch.d_states, n, leaf_list, d_counters);
-    mark("seed+dive");
-
-    // ---- search -------------------------------------------------------------
-    // Top of the tree (two levels) per scan, then the subtrees of the
-    // survivors down to the leaves on many blocks.
-    // Stage shape (tunable for experiments through the environment).
-    const int kLevelsPerStage = std::max(0, Debug().fast2d_levels_per_stage);
-    const int kWaveLevels = Debug().fast2d_wave_levels > 0 ? Debug().fast2d_wave_levels - 1 : -1;
-    // Single searches are latency-bound: one wave stage, then one depth-first
-    // kernel down to the leaves.  Batches are throughput-bound: two wave stages,
-    // then depth-first stages of two levels.
-    const int levels_per_stage = kLevelsPerStage > 0 ? kLevelsPerStage : (num < 4 ? kMaxDepth : 2);
-    const int wave_levels = kWaveLevels >= 0 ? kWaveLevels : (num < 4 ? 1 : 2);
-    // Frontier sizes are only known on the device; grids are sized for the
-    // typical case (a few thousand nodes at the top, tens below) and every
-    // kernel grid-strides, so larger frontiers (big batches) still fill the chip.
-    // Batches: one problem's nodes stay on one XCD (debug switch fast2d_xcd_affinity overrides).
-    const int affinity_override = Debug().fast2d_xcd_affinity;
-    const int affinity = affinity_override ? affinity_override - 1 : (num >= 16 ? 1 : 0);
-    const int wide_blocks = std::min(4096, 1024 * std::max(1, (num + 3) / 4));
-    const int narrow_blocks = std::min(4096, 512 * std::max(1, (num + 3) / 4));
-    int num_chunks = 1;
-    int strict = 0;
-    // Something was dropped (a full frontier / queue / leaf list).  Bounds found so far are real
-    // leaf scores and stay valid; the search is repeated in strict mode (prunes ties, records
-    // only improving leaves) over more, smaller chunks of scans.  The best leaf found so far is
-    // re-found by lowering the bound one ulp.
-    const auto prepare_strict_retry = [&]() {
-      CMX_REQUIRE(num_chunks < (1 << 12), "branch-and-bound overflow not resolvable");
-      if (h_counters->frontier_overflow) num_chunks *= 4;
-      strict = 1;
-      for (int p = 0; p < num; ++p) {
-        const float floor_score = std::max(batch.h_problems[p].min_score, 0.f);
-        unsigned floor_bits;
-        std::memcpy(&floor_bits, &floor_score, sizeof(float));
-        if (h_states[p].best_bits > floor_bits) h_states[p].best_bits -= 1;
-      }
-      CMX_HIP(hipMemcpyAsync(batch.d_states, h_states, num * sizeof(ProblemState),
-                             hipMemcpyHostToDevice, ws.stream));
-      CMX_HIP(hipMemsetAsync(d_counters, 0, sizeof(Counters), ws.stream));
-    };
-    // ---- the work queue: filter + ONE launch for the whole tree and the selection ---------
-    bool queue_ok = QueueSearchWanted(n, num);
-    for (const Fast2DProblem& P : batch.h_problems) {
-      queue_ok = queue_ok && (P.recompute_scans == 0 || P.store_scans != 0);
-      for (int l = 0; l + 1 < depth; ++l)
-        queue_ok = queue_ok && static_cast<unsigned long long>((P.level[l].qy + 3) >> 2) *
-                                       static_cast<unsigned>(P.level[l].qtx) * 128ull < (1ull << 31);
-    }
+        batch.d_problems, batch.d_states, run.n, run.leaf_list, run.d_counters);
+    run.Mark("seed+dive");
     bool searched = false;
-    if (queue_ok) {
-      // 16 K nodes per sub-queue (1 M nodes, 64 MB) for up to 16 problems, 64 K per problem
-      // beyond; slots are not reused within a call.
-      const long long wanted = std::max<long long>(1ll << 20, 65536ll * num);
-      int sub_capacity = static_cast<int>(std::min<long long>(wanted, 1ll << 23) / kQueues);
-      if (Debug().fast2d_queue_capacity > 0) sub_capacity = Debug().fast2d_queue_capacity;
-      TreeQueue queue;
-      queue.capacity = sub_capacity;
-      queue.slots = static_cast<unsigned long long*>(ws.tagged[0].Acquire(
-          static_cast<size_t>(kQueues) * sub_capacity * 8 * sizeof(unsigned long long), ws.stream,
-          &queue.epoch));
-      d_front[0] = ws.dev[10].ReserveAs<Node2D>(kFrontierCapacity);
-      FilterCoarseKernel<<<dim3(DivUp(batch.max_scans, 4), num), 256, 0, ws.stream>>>(
-          batch.d_problems, batch.d_states, n, 0, 1, /*strict=*/0, /*affinity=*/0, front(0),
-          d_counters);
-      mark("filter");
-      // (events only under the debug switch `timing`: RecordEvent is a no-op otherwise)
-      const bool timed = true;
-      if (timed) RecordEvent(ws.ev_x0, ws.stream);
-      // One workgroup per CU: 1024 wavefronts.  More of them shorten a single hard search (512
-      // workgroups: 240 against 290 us on the hardest of the bench's eight scans) and cost the
-      // eight-thread line more than that (17 200 against 19 300 matches/s): wavefronts that find
-      // nothing to steal are pure overhead for the searches that share the chip.
-      const int blocks = Debug().fast2d_queue_blocks > 0
-                             ? Debug().fast2d_queue_blocks
-                             : std::min(2048, 256 * std::max(1, (num + 3) / 4));
-      TreeQueueKernel<<<blocks, 256, 0, ws.stream>>>(
-          batch.d_problems, batch.d_states, n, front(0), queue, leaf_list, d_counters, d_sel,
-          d_best, num, d_states_out, d_summary, reinterpret_cast<const unsigned*>(d_tail),
-          direct ? reinterpret_cast<unsigned*>(h_misc) : nullptr,
-          static_cast<int>(misc_bytes / sizeof(unsigned)),
-          batch.trace && batch.trace->enabled() ? 1 : 0,
-          Debug().fast2d_queue_lost > 0 ? Debug().fast2d_queue_lost : 3);
-      mark("queue");
-      CMX_HIP(hipGetLastError());
-      if (timed) {
-        RecordEvent(ws.ev_x1, ws.stream);
-        result->expansion_launches = 1;
-      }
-      RecordEvent(ws.ev_end, ws.stream);
-      turn.reset();
-      fetch_results(direct);
-      result->expansion_lookups = 64ll * h_counters->wave_gathers;
-      for (int p = 0; p < num; ++p)
-        for (int k = 0; k < kStatShards; ++k) result->expansion_nodes += h_states[p].expanded_shard[k];
-      if (!h_counters->frontier_overflow && !h_counters->leaf_overflow) {
-        searched = true;
-      } else if (h_counters->leaf_overflow) {
-        prepare_strict_retry();
-      } else {
-        // A sub-queue filled up (it holds 1 K nodes: one wavefront's siblings -- landscapes where
-        // nearly everything ties fill it).  The level-synchronous path has room for millions of
-        // nodes and reproduces the reference's order among ANY number of tied leaves, which the
-        // strict retry cannot: it runs first, from the bounds found so far (real leaf scores),
-        // with the lists cleared.
-        CMX_HIP(hipMemsetAsync(d_counters, 0, sizeof(Counters), ws.stream));
+    if (QueueSearchPossible(run)) {
+      switch (RunQueueSearch(run, std::move(turn))) {
+        case QueueOutcome::kDone:
+          searched = true;
+          break;
+        case QueueOutcome::kLeafOverflow:
+          run.PrepareStrictRetry();
+          break;
+        case QueueOutcome::kQueueOverflow:
+          // A sub-queue filled up (it holds 1 K nodes: one wavefront's siblings -- landscapes where
+          // nearly everything ties fill it).  The level-synchronous path has room for millions of
+          // nodes and reproduces the reference's order among ANY number of tied leaves, which the
+          // strict retry cannot: it runs first, from the bounds found so far (real leaf scores),
+          // with the lists cleared.
+          CMX_HIP(hipMemsetAsync(run.d_counters, 0, sizeof(Counters), ws.stream));
+          break;
       }
     }
-    turn.reset();      // (the level-synchronous launches below issue as they come)
-    if (!searched) {
-      d_front[0] = ws.dev[10].ReserveAs<Node2D>(kFrontierCapacity);
-      d_front[1] = ws.dev[11].ReserveAs<Node2D>(kFrontierCapacity);
-    }
-    while (!searched) {
-      for (int chunk = 0; chunk < num_chunks; ++chunk) {
-        if (chunk > 0 || strict)
-          CMX_HIP(hipMemsetAsync(d_counters->frontier, 0, sizeof(d_counters->frontier),
-                                 ws.stream));
-        FilterCoarseKernel<<<dim3(DivUp(batch.max_scans, 4), num), 256, 0, ws.stream>>>(
-            batch.d_problems, batch.d_states, n, chunk, num_chunks, strict, affinity, front(0),
-            d_counters);
-        mark("filter");
-        int stage = 0;
-        int top = depth - 1;
-        // Wave-per-node level-synchronous expansion of the (wide, shallow-lived)
-        // top levels.  (Timed for the statistics in the first pass of a batch: there the
-        // expansion is the dominant kernel; a single search's chain of launches is not given
-        // two more event packets to wait behind.)
-        const bool timed = !strict && chunk == 0 && num >= 4;
-        if (timed) RecordEvent(ws.ev_x0, ws.stream);
-        for (int used = 0; used < wave_levels && top - 1 >= 1; ++used, --top, ++stage) {
-          ExpandWaveKernel<<<used == 0 ? wide_blocks : narrow_blocks, 256, 0, ws.stream>>>(
-              batch.d_problems, batch.d_states, n, front(stage), strict, affinity,
-              front(stage + 1), d_counters);
-          mark("wave");
-        }
-        if (timed) {
-          RecordEvent(ws.ev_x1, ws.stream);
-          result->expansion_launches = stage;
-        }
-        // Block-per-node depth-first stages of kLevelsPerStage levels: the bushy
-        // part of the tree near the optimum spreads over many blocks instead of
-        // being walked serially by one.
-        for (; top > 0; top -= levels_per_stage, ++stage) {
-          const int stop = std::max(0, top - levels_per_stage);
-          SubtreeKernel<<<narrow_blocks, 256, 0, ws.stream>>>(
-              batch.d_problems, batch.d_states, n, front(stage), stop, strict, front(stage + 1),
-              leaf_list, d_counters);
-          mark("subtree");
-        }
-      }
-      SelectBestKernel<<<1, 1024, 0, ws.stream>>>(
-          leaf_list, batch.d_states, d_sel, d_best, num, d_states_out, d_counters, d_summary,
-          reinterpret_cast<const unsigned*>(d_tail),
-          direct ? reinterpret_cast<unsigned*>(h_misc) : nullptr,
-          static_cast<int>(misc_bytes / sizeof(unsigned)));
-      mark("select");
-      CMX_HIP(hipGetLastError());
-      RecordEvent(ws.ev_end, ws.stream);
-      fetch_results(direct);
-      if (!strict) {
-        for (int st = 0; st < result->expansion_launches; ++st)
-          result->expansion_nodes += h_counters->frontier_total[st];
-        result->expansion_lookups = 64ll * h_counters->wave_gathers;
-      }
-      if (!h_counters->frontier_overflow && !h_counters->leaf_overflow) break;
-      prepare_strict_retry();
-    }
+    turn.reset();      // (the level-synchronous launches issue as they come)
+    if (!searched) RunLevelSynchronous(run);
   }
 
-  result->best.assign(h_best, h_best + num);
-  result->states.assign(h_states, h_states + num);
-  if (batch.trace && batch.trace->enabled() && depth > 1) {
-    fprintf(stderr, "[cmx trace] list sizes:");
-    for (int st = 0; st < kMaxStages; ++st)
-      if (h_counters->frontier_total[st])
-        fprintf(stderr, " frontier[%d]=%d", st, h_counters->frontier_total[st]);
-    long long leaves = 0;
-    for (int k = 0; k < kSubLists; ++k) leaves += h_counters->leaves[k];
-    fprintf(stderr, " leaves=%lld\n", leaves);
-    const unsigned* q = h_counters->queue_stats;
-    if (q[5])
-      fprintf(stderr, "[cmx trace] work queue: %u chains (%u nodes from the list, %u popped), %u "
-              "pushed, %u lost races, %u slot re-reads\n", q[5], q[4], q[0], q[3], q[1], q[2]);
-  }
+  result->best.assign(run.h_tail.best, run.h_tail.best + num);
+  result->states.assign(run.h_tail.states, run.h_tail.states + num);
   if (depth > 1) {
-    ResolveTies(ws, batch, leaf_list, *h_counters, &result->best, result->states);
-  } else {
-    ResolveDepthOne(batch, &result->best, result->states);
+    if (batch.trace && batch.trace->enabled()) TraceListSizes(*run.h_tail.summary);
+    result->d_leaves = run.leaf_list.nodes;
+    result->leaf_sub_capacity = run.leaf_list.sub_capacity;
+    result->leaf_counts.assign(run.h_tail.summary->leaves, run.h_tail.summary->leaves + kSubLists);
   }
-  float ms = 0.f;
-  ms = ElapsedMs(ws.ev_begin, ws.ev_end);
-  result->device_ms = ms;
-  ms = ElapsedMs(ws.ev_k0, ws.ev_k1);
-  result->dominant_ms = ms;
-  if (result->expansion_launches > 0) {
-    ms = ElapsedMs(ws.ev_x0, ws.ev_x1);
-    result->expansion_ms = ms;
-  }
+  result->device_ms = ElapsedMs(ws.ev_begin, ws.ev_end);
+  result->dominant_ms = ElapsedMs(ws.ev_k0, ws.ev_k1);
+  if (result->expansion_launches > 0) result->expansion_ms = ElapsedMs(ws.ev_x0, ws.ev_x1);
 }
 
-
-// Exact tie resolution.  When several leaves share the best score the
-// reference returns the one its depth-first search meets first, and at the top
-// level that order is whatever std::sort (libstdc++ introsort, unstable) makes
-// of equal-score candidates (SM2/fast_...2d.cc:331-332).  The host repeats that
-// very sort on the lowest-resolution scores (same initial order, same
-// comparator) and ranks the tied leaves by (sorted position of their
-// lowest-resolution ancestor, sibling ranks down the tree).  Only runs when the
-// device reported a tie.
-struct ScoreIndex {
-  float score;
-  int index;
-  bool operator>(const ScoreIndex& other) const { return score > other.score; }
-};
-
-// The device keeps the lowest-resolution candidates of scan s at [s * coarse_stride, ...);
-// the reference's generation order (scan, x, y) is the dense concatenation.  Host-side
-// views for the rare paths that need that order (tie replay, depth 1, introspection).
-struct CoarseLayout {
-  std::vector<int2> dims;   // [S]
-  std::vector<int> off;     // [S + 1] dense prefix
-  int Dense(const Fast2DProblem& P, int strided) const {
-    return off[strided / P.coarse_stride] + strided % P.coarse_stride;
-  }
-};
-CoarseLayout DownloadLayout(const Fast2DProblem& P) {
-  CoarseLayout L;
-  const int S = P.num_scans;
-  L.dims.resize(S);
-  L.off.resize(S + 1);
-  CMX_HIP(hipMemcpy(L.dims.data(), P.coarse_dims, S * sizeof(int2), hipMemcpyDeviceToHost));
-  L.off[0] = 0;
-  for (int s = 0; s < S; ++s) L.off[s + 1] = L.off[s] + L.dims[s].x * L.dims[s].y;
-  return L;
-}
-template <typename T>
-std::vector<T> DownloadDense(const Fast2DProblem& P, const CoarseLayout& L, const T* device) {
-  const int S = P.num_scans;
-  std::vector<T> strided(static_cast<size_t>(S) * P.coarse_stride);
-  CMX_HIP(hipMemcpy(strided.data(), device, strided.size() * sizeof(T), hipMemcpyDeviceToHost));
-  std::vector<T> dense(L.off[S]);
-  for (int s = 0; s < S; ++s)
-    std::copy_n(strided.begin() + static_cast<size_t>(s) * P.coarse_stride,
-                L.off[s + 1] - L.off[s], dense.begin() + L.off[s]);
-  return dense;
-}
-
-// Under group bounds the lowest-resolution scores of a problem are upper bounds shared by three
-// rotations.  The replay of the reference's order needs the scores themselves: the fused front
-// end once more for THIS problem, every rotation summed on the level itself (group = 1; same
-// buffers, the search is over).  Rare: leaves that tie for the best score.
-void RescoreExact(Workspace& ws, const PreparedBatch& batch, int p) {
-  Fast2DProblem P = batch.h_problems[p];
-  if (P.group <= 1) return;
-  P.group = 1;
-  P.group_verify = 0;
-  P.store_scans = 0;
-  P.timeline = nullptr;
-  CMX_HIP(hipMemcpyAsync(batch.d_problems + p, &P, sizeof(P), hipMemcpyHostToDevice, ws.stream));
-  CMX_HIP(hipStreamSynchronize(ws.stream));          // (`P` is a local)
-  const dim3 grid((P.num_scans + 255) / 256 * 256, 1);
-  PrepScoreFusedKernel<false><<<grid, batch.fused_threads, batch.fused_lds, ws.stream>>>(
-      batch.d_problems + p, batch.d_xyz, batch.n, batch.d_states + p, batch.fused_acc, nullptr, 0);
-  CMX_HIP(hipGetLastError());
-  CMX_HIP(hipStreamSynchronize(ws.stream));
-}
-
-void ResolveTies(Workspace& ws, const PreparedBatch& batch, const NodeList& leaves_dev,
-                 const CountersSummary& h_counters, std::vector<BestLeaf>* best,
-                 const std::vector<ProblemState>& states) {
-  bool any = false;
-  for (const BestLeaf& b : *best) any |= (b.found && b.ties > 1);
-  if (!any) return;
-  // All recorded leaves.
-  std::vector<Node2D> leaves;
-  for (int sub = 0; sub < kSubLists; ++sub) {
-    const int count = std::min(h_counters.leaves[sub], leaves_dev.sub_capacity);
-    if (count <= 0) continue;
-    const size_t old = leaves.size();
-    leaves.resize(old + count);
-    CMX_HIP(hipMemcpy(leaves.data() + old,
-                      leaves_dev.nodes + static_cast<size_t>(sub) * leaves_dev.sub_capacity,
-                      count * sizeof(Node2D), hipMemcpyDeviceToHost));
-  }
-  for (int p = 0; p < batch.num_problems; ++p) {
-    BestLeaf& b = (*best)[p];
-    if (!b.found || b.ties <= 1) continue;
-    unsigned best_bits;
-    std::memcpy(&best_bits, &b.score, sizeof(float));
-    // The dive and the search record the same leaf twice; only distinct leaves tie.
-    std::vector<const Node2D*> tied;
-    for (const Node2D& nd : leaves) {
-      unsigned bits;
-      std::memcpy(&bits, &nd.score, sizeof(float));
-      if ((nd.problem & 0xffffff) != p || bits != best_bits) continue;
-      bool duplicate = false;
-      for (const Node2D* t : tied)
-        duplicate |= (t->scan == nd.scan && t->dx == nd.dx && t->dy == nd.dy);
-      if (!duplicate) tied.push_back(&nd);
-      if (tied.size() > 4096) break;   // degenerate input: plenty of ties, stop deduplicating
-    }
-    if (tied.size() <= 1) continue;
-    const Fast2DProblem& P = batch.h_problems[p];
-    RescoreExact(ws, batch, p);
-    const CoarseLayout layout = DownloadLayout(P);
-    const std::vector<float> scores = DownloadDense(P, layout, P.coarse_score);
-    const int total = static_cast<int>(scores.size());
-    CMX_REQUIRE(total == states[p].coarse_total, "internal error: candidate layout mismatch");
-    std::vector<ScoreIndex> sorted(total);
-    for (int c = 0; c < total; ++c) sorted[c] = {scores[c], c};
-    std::sort(sorted.begin(), sorted.end(), std::greater<ScoreIndex>());
-    std::vector<int> position(total);
-    for (int i = 0; i < total; ++i) position[sorted[i].index] = i;
-    bool have = false;
-    unsigned long long best_key = 0;
-    for (const Node2D& nd : leaves) {
-      unsigned bits;
-      std::memcpy(&bits, &nd.score, sizeof(float));
-      if ((nd.problem & 0xffffff) != p || bits != best_bits) continue;
-      const unsigned long long key =
-          (static_cast<unsigned long long>(position[layout.Dense(P, nd.coarse_index)]) << 32) |
-          nd.path;
-      if (!have || key < best_key) {
-        have = true;
-        best_key = key;
-        b.scan = nd.scan; b.dx = nd.dx; b.dy = nd.dy;
-      }
-    }
-  }
-}
-
-// depth == 1: BranchAndBound returns candidates[0] of the std::sort-ed
-// lowest-resolution candidates (SM2/fast_...2d.cc:340-343); replay that sort.
-void ResolveDepthOne(const PreparedBatch& batch, std::vector<BestLeaf>* best,
-                     const std::vector<ProblemState>& states) {
-  for (int p = 0; p < batch.num_problems; ++p) {
-    BestLeaf& b = (*best)[p];
-    const Fast2DProblem& P = batch.h_problems[p];
-    if (states[p].error || states[p].coarse_total <= 0) continue;
-    const CoarseLayout layout = DownloadLayout(P);
-    const std::vector<float> scores = DownloadDense(P, layout, P.coarse_score);
-    const int total = static_cast<int>(scores.size());
-    std::vector<ScoreIndex> sorted(total);
-    for (int c = 0; c < total; ++c) sorted[c] = {scores[c], c};
-    std::sort(sorted.begin(), sorted.end(), std::greater<ScoreIndex>());
-    const int S = P.num_scans;
-    const std::vector<int>& off = layout.off;
-    const std::vector<int2>& dims = layout.dims;
-    std::vector<int4> bounds(S);
-    CMX_HIP(hipMemcpy(bounds.data(), P.bounds, S * sizeof(int4), hipMemcpyDeviceToHost));
-    const int c = sorted[0].index;
-    const int s = static_cast<int>(std::upper_bound(off.begin(), off.end(), c) - off.begin()) - 1;
-    const int local = c - off[s];
-    b = BestLeaf{};
-    b.score = sorted[0].score;
-    b.found = b.score > P.min_score;
-    b.scan = s;
-    b.dx = bounds[s].x + local / dims[s].y;    // depth 1: step 1, x outer / y inner
-    b.dy = bounds[s].z + local % dims[s].y;
-    b.ties = 1;
-  }
-}
-
-void CheckProblemErrors(const BatchResult& r) {
-  for (const ProblemState& st : r.states) {
-    CMX_REQUIRE(st.error != 1, "scan cell indices exceed the int16 range supported on device");
-    CMX_REQUIRE(st.error != 2, "internal error: lowest-resolution candidate capacity exceeded");
-    CMX_REQUIRE(st.error != 3, "internal error: a group bound of the fused front end lies below one of its rotations' sums");
-  }
-}
-
-void MatchBatch(const cmx_fast2d* const* handles, int num, const cmx_pose2d* initial,
-                bool full_submap, const float* host_xyz, const cmx_cloud* cloud, int n,
-                float min_score, int32_t* found, float* scores, cmx_pose2d* poses,
-                cmx_match_stats* stats, const int32_t* full_flags = nullptr,
-                const float* min_scores = nullptr) {
-  CMX_REQUIRE(handles != nullptr && num >= 1, "no matchers given");
-  CMX_REQUIRE(num < (1 << 24), "too many matchers in one batch");
-  CMX_REQUIRE(found != nullptr && scores != nullptr && poses != nullptr,
-              "score / pose_estimate outputs must not be null");   // CHECK at :232-233
-  CMX_REQUIRE(n >= 1, "empty point cloud");
-  CMX_REQUIRE(n <= (1 << 24), "point cloud too large");
-  std::vector<const Fast2DMatcher*> matchers(num);
-  for (int p = 0; p < num; ++p) {
-    CMX_REQUIRE(handles[p] != nullptr && handles[p]->impl, "null matcher handle");
-    matchers[p] = handles[p]->impl.get();
-    CMX_REQUIRE(matchers[p]->device() == matchers[0]->device(),
-                "all matchers of a batch must live on the same device");
-  }
-  const int device = matchers[0]->device();
-  // Large batches (from 32 problems on; debug switch fast2d_fanout: 1 never, N > 1 from N on) as
-  // INDEPENDENT searches over the host pool: every problem the single-search chain (front end, dive,
-  // filter, work-queue tree) on a workspace and stream of its own, sixteen in flight on sixteen
-  // hardware queues, instead of the level-synchronous launches over the whole batch -- 64 submaps
-  // 6.6 against 9.8 ms, 128: 11.8 against 17.9, 16: the same (profiles/r06g_fanout.txt; with the
-  // runtime's four queues of until round 6 it lost: 1.69 against 1.42 ms for 16).  Same results: a
-  // problem's search does not depend on its neighbours in the batch.  A caller that finds the
-  // pool busy (another batch of the process) runs its problems one after the other itself.
-  const int fanout_from = Debug().fast2d_fanout == 0 ? 32 : Debug().fast2d_fanout == 1 ? (1 << 30)
-                                                                                       : Debug().fast2d_fanout;
-  // (full-submap searches only: a windowed search is a few launches' worth of work, and a batch of
-  // them is cheaper in the batch's few launches than in five launches each)
-  bool all_full = true;
-  for (int p = 0; p < num && all_full; ++p) all_full = full_flags ? full_flags[p] != 0 : full_submap;
-  if (num >= fanout_from && all_full && OverrideStream(device) == nullptr) {
-    std::vector<cmx_match_stats> part(num);
-    ParallelFor(num, 2, [&](int p) {
-      MatchBatch(handles + p, 1, initial ? initial + p : nullptr, full_submap, host_xyz, cloud, n,
-                 min_scores ? min_scores[p] : min_score, found + p, scores + p, poses + p, &part[p],
-                 full_flags ? full_flags + p : nullptr, nullptr);
-    });
-    cmx_match_stats total{};
-    for (const cmx_match_stats& st : part) {
-      total.candidates_scored += st.candidates_scored;
-      total.coarse_candidates += st.coarse_candidates;
-      total.nodes_expanded += st.nodes_expanded;
-      total.num_scans += st.num_scans;
-      total.device_ms += st.device_ms;                      // (sums over concurrent searches)
-      total.dominant_kernel_ms += st.dominant_kernel_ms;
-      total.expansion_ms += st.expansion_ms;
-      total.expansion_launches += st.expansion_launches;
-      total.expansion_nodes += st.expansion_nodes;
-      total.expansion_lookups += st.expansion_lookups;
-    }
-    if (stats) *stats = total;
-    return;
-  }
-  const auto t_call = std::chrono::steady_clock::now();
-  g_host_wait_ns = 0;
-  WorkspaceLease ws(device);
-  const float* d_xyz;
-  float max_range;
-  if (cloud) {
-    CMX_REQUIRE(cloud->device == device, "cloud and matcher are on different devices");
-    d_xyz = cloud->xyz;
-    max_range = cloud->max_range_xy;
-  } else {
-    CMX_REQUIRE(host_xyz != nullptr, "point cloud is null");
-    float* buf = ws->dev[0].ReserveAs<float>(3 * static_cast<size_t>(n));
-    CMX_HIP(hipMemcpyAsync(buf, host_xyz, 3 * sizeof(float) * n, hipMemcpyHostToDevice,
-                           ws->stream));
-    d_xyz = buf;
-    max_range = MaxRangeXY(host_xyz, n);
-  }
-  RecordEvent(ws->ev_begin, ws->stream);
-  PreparedBatch batch;
-  StageTrace trace(ws->stream);
-  batch.trace = &trace;
-  ReserveSearchScratch(*ws, num, &batch);
-  PrepareAndScoreCoarse(*ws, matchers.data(), num, initial, full_submap, d_xyz, n, max_range,
-                        min_score, &batch, full_flags, min_scores);
-  BatchResult result;
-  RunBranchAndBound(*ws, batch, &result);
-  if (Debug().host_trace) {
-    g_host_total_ns += std::chrono::duration_cast<std::chrono::nanoseconds>(
-                           std::chrono::steady_clock::now() - t_call).count();
-    g_host_waited_ns += g_host_wait_ns;
-    const long long calls = ++g_host_calls;
-    if (calls % 2000 == 0)
-      fprintf(stderr, "[cmx host] fast2d: %lld calls, mean %.1f us per call, of which %.1f us in the final synchronisation\n",
-              calls, g_host_total_ns.load() * 1e-3 / calls, g_host_waited_ns.load() * 1e-3 / calls);
-  }
-  trace.Report();
-  if (batch.d_timeline)
-    ReportTimeline("PrepScoreFusedKernel", batch.d_timeline, batch.timeline_blocks, ws->stream);
-  if (trace.enabled()) {
-    for (int p = 0; p < std::min(num, 4); ++p) {
-      unsigned long long ex = 0;
-      for (int k = 0; k < kStatShards; ++k) ex += result.states[p].expanded_shard[k];
-      fprintf(stderr, "[cmx trace] problem %d: coarse %d expanded %llu found %d ties %d\n", p,
-              result.states[p].coarse_total, ex, result.best[p].found, result.best[p].ties);
-    }
-  }
-  CheckProblemErrors(result);
-  cmx_match_stats total{};
-  for (int p = 0; p < num; ++p) {
-    const BestLeaf& b = result.best[p];
-    const HostSearch& h = batch.search[p];
-    const bool ok = b.found && b.score > (min_scores ? min_scores[p] : min_score);
-    found[p] = ok ? 1 : 0;
-    if (ok) {
-      // Candidate2D (SM2/correlative_scan_matcher_2d.h:74-84) and the pose
-      // composition of :254-259.
-      const double res = matchers[p]->limits().resolution;
-      const double cx = -b.dy * res, cy = -b.dx * res;
-      const double orientation = (b.scan - h.num_angular) * h.step;
-      scores[p] = b.score;
-      poses[p].x = batch.initial[p].x + cx;
-      poses[p].y = batch.initial[p].y + cy;
-      poses[p].theta = batch.initial[p].theta + orientation;
-    }
-    total.candidates_scored += result.states[p].coarse_total;
-    total.coarse_candidates += result.states[p].coarse_total;
-    for (int k = 0; k < kStatShards; ++k) {
-      total.candidates_scored += result.states[p].scored_shard[k];
-      total.nodes_expanded += result.states[p].expanded_shard[k];
-    }
-    total.num_scans += h.num_scans;
-  }
-  total.device_ms = result.device_ms;
-  total.dominant_kernel_ms = result.dominant_ms;
-  total.expansion_ms = result.expansion_ms;
-  total.expansion_launches = result.expansion_launches;
-  total.expansion_nodes = result.expansion_nodes;
-  total.expansion_lookups = result.expansion_lookups;
-  if (stats) *stats = total;
-}
-
-}  // namespace
 }  // namespace cmx
-
-// ---------------------------------------------------------------------------
-// C ABI
-// ---------------------------------------------------------------------------
-using cmx::Guard;
-
-extern "C" {
-
-cmx_status cmx_fast2d_create(const cmx_fast2d_options* options, const cmx_grid2d_limits* limits,
-                             const uint16_t* cells, int32_t device, cmx_fast2d** out) {
-  return Guard([&] {
-    CMX_REQUIRE(options && limits && out, "null argument");
-    *out = nullptr;
-    std::unique_ptr<cmx_fast2d> h(new cmx_fast2d);
-    h->impl.reset(new cmx::Fast2DMatcher(*options, *limits, cells, device));
-    *out = h.release();
-  });
-}
-
-void cmx_fast2d_destroy(cmx_fast2d* matcher) { delete matcher; }
-
-cmx_status cmx_fast2d_match(const cmx_fast2d* matcher, const cmx_pose2d* initial_pose_estimate,
-                            const float* point_cloud_xyz, int32_t num_points, float min_score,
-                            int32_t* found, float* score, cmx_pose2d* pose_estimate,
-                            cmx_match_stats* stats) {
-  return Guard([&] {
-    CMX_REQUIRE(matcher && initial_pose_estimate, "null argument");
-    cmx::MatchBatch(&matcher, 1, initial_pose_estimate, false, point_cloud_xyz, nullptr,
-                    num_points, min_score, found, score, pose_estimate, stats);
-  });
-}
-
-cmx_status cmx_fast2d_match_full_submap(const cmx_fast2d* matcher, const float* point_cloud_xyz,
-                                        int32_t num_points, float min_score, int32_t* found,
-                                        float* score, cmx_pose2d* pose_estimate,
-                                        cmx_match_stats* stats) {
-  return Guard([&] {
-    CMX_REQUIRE(matcher, "null argument");
-    cmx::MatchBatch(&matcher, 1, nullptr, true, point_cloud_xyz, nullptr, num_points, min_score,
-                    found, score, pose_estimate, stats);
-  });
-}
-
-cmx_status cmx_fast2d_match_full_submap_batch(const cmx_fast2d* const* matchers,
-                                              int32_t num_matchers, const float* point_cloud_xyz,
-                                              int32_t num_points, float min_score,
-                                              int32_t* found, float* scores,
-                                              cmx_pose2d* pose_estimates, cmx_match_stats* stats) {
-  return Guard([&] {
-    cmx::MatchBatch(matchers, num_matchers, nullptr, true, point_cloud_xyz, nullptr, num_points,
-                    min_score, found, scores, pose_estimates, stats);
-  });
-}
-
-cmx_status cmx_cloud_upload(const float* point_cloud_xyz, int32_t num_points, int32_t device,
-                            cmx_cloud** out) {
-  return Guard([&] {
-    CMX_REQUIRE(point_cloud_xyz && out && num_points >= 1, "invalid point cloud");
-    *out = nullptr;
-    cmx::UseDevice(device);
-    std::unique_ptr<cmx_cloud> c(new cmx_cloud);
-    c->device = device;
-    c->num_points = num_points;
-    c->host_xyz.assign(point_cloud_xyz, point_cloud_xyz + 3 * static_cast<size_t>(num_points));
-    c->max_range_xy = cmx::MaxRangeXY(point_cloud_xyz, num_points);
-    float m = 0.f;
-    for (int i = 0; i < num_points; ++i) {
-      const float x = point_cloud_xyz[3 * i], y = point_cloud_xyz[3 * i + 1],
-                  z = point_cloud_xyz[3 * i + 2];
-      m = std::max(m, std::sqrt(x * x + y * y + z * z));
-    }
-    c->max_range_xyz = m;
-    {
-      double best = 0.;
-      for (int i = 0; i < num_points; ++i) {
-        const double x = point_cloud_xyz[3 * i], y = point_cloud_xyz[3 * i + 1];
-        best = std::max(best, x * x + y * y);
-      }
-      for (int i = 0; i < num_points && c->far_points.size() <= 64; ++i) {
-        const double x = point_cloud_xyz[3 * i], y = point_cloud_xyz[3 * i + 1];
-        if (x * x + y * y >= best * (1. - 1e-4)) c->far_points.push_back(i);
-      }
-      if (c->far_points.size() > 64) c->far_points.clear();
-    }
-    CMX_HIP(hipMalloc(&c->xyz, 3 * sizeof(float) * num_points));
-    hipError_t err = hipMemcpy(c->xyz, point_cloud_xyz, 3 * sizeof(float) * num_points,
-                               hipMemcpyHostToDevice);
-    if (err != hipSuccess) {
-      (void)hipFree(c->xyz);
-      c->xyz = nullptr;
-      CMX_HIP(err);
-    }
-    *out = c.release();
-  });
-}
-
-void cmx_cloud_destroy(cmx_cloud* cloud) {
-  if (!cloud) return;
-  if (cloud->xyz) {
-    (void)hipSetDevice(cloud->device);
-    (void)hipFree(cloud->xyz);
-  }
-  delete cloud;
-}
-
-cmx_status cmx_fast2d_match_full_submap_batch_resident(
-    const cmx_fast2d* const* matchers, int32_t num_matchers, const cmx_cloud* cloud,
-    float min_score, int32_t* found, float* scores, cmx_pose2d* pose_estimates,
-    cmx_match_stats* stats) {
-  return Guard([&] {
-    CMX_REQUIRE(cloud != nullptr, "null cloud");
-    cmx::MatchBatch(matchers, num_matchers, nullptr, true, nullptr, cloud, cloud->num_points,
-                    min_score, found, scores, pose_estimates, stats);
-  });
-}
-
-cmx_status cmx_fast2d_match_batch(const cmx_fast2d* const* matchers, int32_t num_matchers,
-                                  const cmx_pose2d* initial_pose_estimates,
-                                  const int32_t* match_full_submap, const float* min_scores,
-                                  const float* point_cloud_xyz, int32_t num_points, int32_t* found,
-                                  float* scores, cmx_pose2d* pose_estimates,
-                                  cmx_match_stats* stats) {
-  return Guard([&] {
-    CMX_REQUIRE(match_full_submap != nullptr && min_scores != nullptr, "null argument");
-    bool any_windowed = false;
-    for (int p = 0; p < num_matchers; ++p) any_windowed |= match_full_submap[p] == 0;
-    CMX_REQUIRE(!any_windowed || initial_pose_estimates != nullptr,
-                "initial_pose_estimates required for windowed searches");
-    cmx::MatchBatch(matchers, num_matchers, initial_pose_estimates, false, point_cloud_xyz, nullptr,
-                    num_points, 0.f, found, scores, pose_estimates, stats, match_full_submap,
-                    min_scores);
-  });
-}
-
-cmx_status cmx_fast2d_level_dims(const cmx_fast2d* matcher, int32_t level, int32_t* wide_x,
-                                 int32_t* wide_y) {
-  return Guard([&] {
-    CMX_REQUIRE(matcher && matcher->impl && wide_x && wide_y, "null argument");
-    CMX_REQUIRE(level >= 0 && level < matcher->impl->depth(), "level out of range");
-    *wide_x = matcher->impl->level(level).wx;
-    *wide_y = matcher->impl->level(level).wy;
-  });
-}
-
-cmx_status cmx_fast2d_level_cells(const cmx_fast2d* matcher, int32_t level, uint8_t* out) {
-  return Guard([&] {
-    CMX_REQUIRE(matcher && matcher->impl && out, "null argument");
-    CMX_REQUIRE(level >= 0 && level < matcher->impl->depth(), "level out of range");
-    cmx::UseDevice(matcher->impl->device());
-    const cmx::LevelDesc& L = matcher->impl->level(level);
-    CMX_HIP(hipMemcpy(out, L.cells, static_cast<size_t>(L.wx) * L.wy, hipMemcpyDeviceToHost));
-  });
-}
-
-cmx_status cmx_fast2d_debug_prepare(const cmx_fast2d* matcher,
-                                    const cmx_pose2d* initial_pose_estimate,
-                                    const float* point_cloud_xyz, int32_t num_points,
-                                    int32_t full_submap, int32_t* num_scans,
-                                    double* angular_step, int32_t* discrete_xy,
-                                    int64_t discrete_capacity, int32_t* bounds,
-                                    int64_t bounds_capacity, int32_t* coarse_sums,
-                                    int64_t sums_capacity, int64_t* num_coarse) {
-  return Guard([&] {
-    CMX_REQUIRE(matcher && matcher->impl && point_cloud_xyz && num_points >= 1, "bad argument");
-    CMX_REQUIRE(full_submap || initial_pose_estimate, "initial pose required");
-    const cmx::Fast2DMatcher* m = matcher->impl.get();
-    cmx::WorkspaceLease ws(m->device());
-    const int n = num_points;
-    float* d_xyz = ws->dev[0].ReserveAs<float>(3 * static_cast<size_t>(n));
-    CMX_HIP(hipMemcpyAsync(d_xyz, point_cloud_xyz, 3 * sizeof(float) * n, hipMemcpyHostToDevice,
-                           ws->stream));
-    cmx::RecordEvent(ws->ev_begin, ws->stream);
-    cmx::PreparedBatch batch;
-    batch.write_all_discrete = true;
-    cmx::PrepareAndScoreCoarse(*ws, &m, 1, initial_pose_estimate, full_submap != 0, d_xyz, n,
-                               cmx::MaxRangeXY(point_cloud_xyz, n), 0.f, &batch);
-    CMX_HIP(hipStreamSynchronize(ws->stream));
-    const cmx::Fast2DProblem& P = batch.h_problems[0];
-    cmx::ProblemState st;
-    CMX_HIP(hipMemcpy(&st, batch.d_states, sizeof(st), hipMemcpyDeviceToHost));
-    CMX_REQUIRE(st.error == 0, "device preparation error %d", st.error);
-    const int S = P.num_scans;
-    const cmx::CoarseLayout layout = cmx::DownloadLayout(P);
-    st.coarse_total = layout.off[S];
-    if (num_scans) *num_scans = S;
-    if (angular_step) *angular_step = batch.search[0].step;
-    if (num_coarse) *num_coarse = st.coarse_total;
-    if (discrete_xy) {
-      CMX_REQUIRE(discrete_capacity >= 2ll * S * n, "discrete_xy capacity too small");
-      std::vector<uint32_t> packed(static_cast<size_t>(S) * n);
-      CMX_HIP(hipMemcpy(packed.data(), P.discrete, packed.size() * sizeof(uint32_t),
-                        hipMemcpyDeviceToHost));
-      for (size_t i = 0; i < packed.size(); ++i) {
-        discrete_xy[2 * i] = static_cast<short>(packed[i] & 0xffffu);
-        discrete_xy[2 * i + 1] = static_cast<short>(packed[i] >> 16);
-      }
-    }
-    if (bounds) {
-      CMX_REQUIRE(bounds_capacity >= 4ll * S, "bounds capacity too small");
-      std::vector<int4> b(S);
-      CMX_HIP(hipMemcpy(b.data(), P.bounds, S * sizeof(int4), hipMemcpyDeviceToHost));
-      for (int s = 0; s < S; ++s) {
-        bounds[4 * s] = b[s].x; bounds[4 * s + 1] = b[s].y;
-        bounds[4 * s + 2] = b[s].z; bounds[4 * s + 3] = b[s].w;
-      }
-    }
-    if (coarse_sums) {
-      CMX_REQUIRE(sums_capacity >= st.coarse_total, "coarse_sums capacity too small");
-      const std::vector<int> dense = cmx::DownloadDense(P, layout, P.coarse_sum);
-      std::copy(dense.begin(), dense.end(), coarse_sums);
-    }
-  });
-}
-
-}  // extern "C"

@@ -1,0 +1,98 @@
+// What the translation units of the fast 2D matcher share on the host:
+//   fast_2d_stack.hip    precomputation stack (Fast2DMatcher)
+//   fast_2d_coarse.hip   scan preparation + lowest-resolution scoring (the front end)
+//   fast_2d.hip          branch and bound
+//   fast_2d_match.hip    MatchBatch, tie resolution, C ABI
+// Every unit owns its kernels and exposes the host functions declared here; no kernel is launched
+// from another file than the one that defines it.
+#ifndef CMX_FAST_2D_INTERNAL_H_
+#define CMX_FAST_2D_INTERNAL_H_
+
+#include <vector>
+
+#include "scan_matching_2d.h"
+
+namespace cmx {
+
+// Cells by which the lowest-resolution level is dilated, either way, for the group bounds of the
+// fused front end (DilateLevelKernel builds the image, PrepScoreFusedKernel sums over it).
+constexpr int kGroupDilation = 2;
+constexpr int kFusedGroup = 3;           // rotations per workgroup under group bounds (see the kernel)
+// Node lists (frontiers, leaves) are split into kSubLists sub-lists, each with
+// its own counter, so that thousands of blocks appending at once do not
+// serialise on one atomic word (one word sustains only ~90 atomics/us).
+constexpr int kSubLists = 64;
+
+// SearchParameters ctor (SM2/correlative_scan_matcher_2d.cc:27-55), host side.
+struct HostSearch {
+  int num_angular;
+  double step;
+  int num_scans;
+  int nl;
+};
+// (MakeSearch, fast_2d_coarse.hip)
+
+struct PreparedBatch {
+  StageTrace* trace = nullptr;
+  int num_problems = 0;
+  int n = 0;
+  int max_scans = 0;
+  long long plane_acc_cells = 0;   // LDS accumulators the plane kernel needs (upper bound)
+  std::vector<HostSearch> search;
+  std::vector<cmx_pose2d> initial;
+  Fast2DProblem* d_problems = nullptr;
+  ProblemState* d_states = nullptr;
+  std::vector<Fast2DProblem> h_problems;
+  // Search scratch carved before the first kernel so that it can clear the counters.
+  char* d_misc = nullptr;          // (ReserveSearchScratch; laid out by fast_2d.hip)
+  int num_counter_words = 0;       // ints at the start of d_misc that the first kernel of a call clears
+  bool write_all_discrete = false; // debug entry point: keep every discretised scan
+  unsigned long long* d_timeline = nullptr;   // CMX_TIMELINE=1
+  int timeline_blocks = 0;
+  // The fused front end's launch, kept for the exact re-run of a problem whose leaves tie
+  // (RescoreExact): under group bounds the lowest-resolution scores are bounds.
+  bool any_group = false;
+  size_t fused_lds = 0;
+  int fused_acc = 0, fused_threads = 0;
+  const float* d_xyz = nullptr;
+};
+
+struct BatchResult {
+  std::vector<BestLeaf> best;
+  std::vector<ProblemState> states;
+  double device_ms = 0., dominant_ms = 0.;
+  double expansion_ms = 0.;          // wave-per-node stages of the first pass
+  int expansion_launches = 0;
+  long long expansion_nodes = 0, expansion_lookups = 0;
+  // Where the search left its leaf records (depth > 1): what the tie resolution reads.
+  const Node2D* d_leaves = nullptr;  // [kSubLists][leaf_sub_capacity]
+  int leaf_sub_capacity = 0;
+  std::vector<int> leaf_counts;      // [kSubLists] records per sub-list (may exceed the capacity)
+};
+
+// ---- fast_2d_coarse.hip
+// Uploads problem descriptors, carves scratch and runs the preparation +
+// lowest-resolution scoring kernels.  `d_xyz` is the device point cloud.
+void PrepareAndScoreCoarse(Workspace& ws, const Fast2DMatcher* const* matchers, int num,
+                           const cmx_pose2d* initial_or_null, bool full_submap,
+                           const float* d_xyz, int n, float max_range_xy, float min_score,
+                           PreparedBatch* out, const int32_t* full_flags = nullptr,
+                           const float* min_scores = nullptr);
+// The exact lowest-resolution scores of problem p of a batch scored under group bounds (no-op
+// otherwise), in place.
+void RescoreExact(Workspace& ws, const PreparedBatch& batch, int p);
+
+// ---- fast_2d.hip
+// Whether a batch of `num` problems over n points goes to the work-queue search (it keeps the
+// cells of surviving scans, which the front end has to know).
+bool QueueSearchWanted(int n, int num);
+// Before PrepareAndScoreCoarse: the search's scratch block, whose counters the front end clears.
+void ReserveSearchScratch(Workspace& ws, int num, PreparedBatch* batch);
+// Full search of a prepared batch; best leaves as the device selected them (ties unresolved).
+void RunBranchAndBound(Workspace& ws, const PreparedBatch& batch, BatchResult* result);
+// Nanoseconds this thread's current call has spent in the final synchronisation (host_trace).
+extern thread_local long long g_host_wait_ns;
+
+}  // namespace cmx
+
+#endif  // CMX_FAST_2D_INTERNAL_H_

@@ -1737,7 +1737,7 @@ void Match3DMany(const Search3D* searches, int num, const cmx_node_data3d& data,
     const long long total = pr.total;
     Best3 best = h_best[p];
     if (best.found && best.ties > 1) {
-      // Exact tie resolution (see fast_2d.hip ResolveTies): repeat the reference's
+      // Exact tie resolution (see fast_2d_match.hip ResolveTies): repeat the reference's
       // std::sort of the lowest-resolution candidates (:352-353) and take the
       // tied leaf its depth-first search meets first.  The dive and the search
       // record the same leaf twice, so first check that distinct leaves tie.

@@ -61,13 +61,13 @@ struct Fast2DProblem {
   const float2* scan_rot;   // [num_scans] (w, z) of AngleAxisf(f32(delta_theta_s), Z)
   float min_s, score_scale; // ToScore(v) = min_s + v * score_scale
   float min_score;          // caller's acceptance threshold
-  // Lowest-resolution level re-laid out as "phase planes" (see fast_2d.hip):
+  // Lowest-resolution level re-laid out as "phase planes" (see fast_2d_coarse.hip):
   // plane(py,px)[J][I] = level[depth-1] cell (I*w+px, J*w+py), w = 2^(depth-1).
   const uint8_t* planes;    // [(w*w + 1) planes][plane_stride]; the last plane is all zero
   int plane_i, plane_j;     // cells per plane along x / y
   int plane_stride;         // bytes per plane (multiple of 64)
   int use_planes;           // 0: generic gather scoring of the lowest resolution
-  // Group bounds of the fused front end (round 6, fast_2d.hip "group bounds"): the same planes of
+  // Group bounds of the fused front end (round 6, fast_2d_coarse.hip "group bounds"): the same planes of
   // the lowest-resolution level dilated by two cells either way (and stored two cells up: cell
   // (X + 2, Y + 2) of the dilated image bounds the cells within two of (X, Y)); `group` adjacent
   // rotations share ONE sum over them.  group == 1: every rotation summed on `planes` itself.

@@ -1,7 +1,7 @@
 """CPU checks (numpy float32 / float64 emulation, same IEEE operations) of two device-side
 shortcuts whose exactness the GPU parity tests rely on but cannot enumerate:
 
-* `SumUpperBound` (fast_2d.hip): the integer recovered from a node's f32 score must never be
+* `SumUpperBound` (fast_2d_device.h): the integer recovered from a node's f32 score must never be
   below the integer sum the score was computed from, or the early exit of `ExpandWaveKernel`
   could drop a child the reference keeps.
 * `FastCellIndex` (rt_3d.hip) / `CellIndexF64` (cmx_device.h): when the shortcut path is taken

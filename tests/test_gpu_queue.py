@@ -113,7 +113,7 @@ def test_queue_search_counts_its_work(sm, world8, debug):
 ], ids=lambda s: ",".join(f"{k}={v}" for k, v in s.items()))
 def test_group_bounds_equal_the_oracle_on_eight_scans(sm, world8, debug, switches):
     """The lowest-resolution scores of the default path are upper bounds shared by three
-    neighbouring rotations (fast_2d.hip, PrepScoreFusedKernel): results bit-equal to the oracle's on
+    neighbouring rotations (fast_2d_coarse.hip, PrepScoreFusedKernel): results bit-equal to the oracle's on
     all eight scans, with the device checking every bound against the exact sums of its rotations
     (a violation fails the call), and with every unit's outer rotations unbounded."""
     cells, lim, _, scans, refs = world8
