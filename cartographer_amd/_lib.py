@@ -161,6 +161,7 @@ EXPORTED_SYMBOLS = [
     "cmx_tsdf2d_create", "cmx_tsdf2d_destroy", "cmx_tsdf2d_get_limits", "cmx_tsdf2d_download",
     "cmx_tsdf2d_insert", "cmx_tsdf2d_crop", "cmx_rt2d_match_tsdf_grid",
     "cmx_fast2d_create_from_tsdf",
+    "cmx_rt2d_match_tsdf_grid_batch", "cmx_rt2d_match_tsdf_grid_batch_resident",
     "cmx_rt2d_match_grid_batch", "cmx_rt2d_match_grid_batch_resident",
     "cmx_grid3d_create", "cmx_grid3d_destroy", "cmx_grid3d_insert", "cmx_grid3d_info",
     "cmx_grid3d_download",
@@ -276,6 +277,9 @@ def lib():
     L.cmx_tsdf2d_crop.argtypes = [C.c_void_p]
     L.cmx_rt2d_match_tsdf_grid.argtypes = [P(RtOptions), C.c_void_p, P(Pose2d), C.c_void_p,
                                            C.c_int32, P(C.c_double), P(Pose2d), P(MatchStats)]
+    L.cmx_rt2d_match_tsdf_grid_batch.argtypes = L.cmx_rt2d_match_grid_batch.argtypes
+    L.cmx_rt2d_match_tsdf_grid_batch_resident.argtypes = \
+        L.cmx_rt2d_match_grid_batch_resident.argtypes
     L.cmx_fast2d_create_from_tsdf.argtypes = [P(Fast2DOptions), C.c_void_p, P(C.c_void_p)]
     L.cmx_fast2d_create.argtypes = [P(Fast2DOptions), P(Grid2DLimits), C.c_void_p, C.c_int32,
                                     P(C.c_void_p)]

@@ -87,6 +87,9 @@ cmx_status Guard(F&& body) {
   X(rt2d_bounds_fused)    /* 1: the bound kernel finishes its matches itself (no tail kernel: round 5's shape) */ \
   X(rt2d_bounds_level)    /* 2: blocks of 2 x 2 translations as the first level (default: 4 x 4, refined through 2 x 2) */ \
   X(rt2d_bounds_verify)   /* 1: every block is summed and checked against its bound (an error if one is below) */ \
+  X(rt2d_tsdf_batch_legacy) /* 1: the TSDF batch entries on the one-thread-per-candidate kernels (parity partner of rt_2d_tsdf.hip; also the default, see there) */ \
+  X(rt2d_tsdf_batch_bulk) /* 1: the TSDF batch entries on the integer bulk path of rt_2d_tsdf.hip for calls of any size */ \
+  X(rt2d_tsdf_verify)     /* 1: TSDF batch: every candidate's exact score is evaluated on the device and checked against its interval (an error if one lies outside) */ \
   X(timeline)             /* 1: in-kernel timelines (cmx_device.h Stamp) reported on stderr */     \
   X(trace)                /* 1: an event after every stage of a call, durations on stderr */       \
   X(host_trace)           /* 1: wall clock of the host phases of a call on stderr */               \

@@ -62,13 +62,6 @@ struct Rt2DParams {
   int prep_blocks;           // num_scans + blocks of the grid expansion
 };
 
-// The (term, weight) a TSDF cell contributes (real_time_..._2d.cc:38-59,
-// mapping/internal/2d/tsdf_2d.cc:88-98, tsd_value_converter.cc:22-33).
-__device__ __forceinline__ float2 TsdfTerm(float tsd, float weight, float max_tsd) {
-  const float normalized = (max_tsd - fabsf(tsd)) / max_tsd;
-  return make_float2(normalized * weight, weight);
-}
-
 // Every kernel serves a batch of independent matches: blockIdx.z picks the match, blocks
 // beyond a match's own extent return at once.
 template <bool kTsdf>
@@ -383,7 +376,6 @@ size_t Align16(size_t v) { return (v + 15) & ~static_cast<size_t>(15); }
 // one-thread-per-candidate kernels: TSDFs, flat score landscapes and whatever the tile path
 // (rt_2d_tiles.hip) does not take.  Per item `cells` is a host buffer, or -- when
 // `device_cells` is given -- ignored in favour of a grid that already lives in HBM (cmx_grid2d).
-namespace {
 void Rt2DLegacyBatch(const cmx_rt_options* options, const Rt2DItem* items, const Rt2DSearch* search,
                      int num, int32_t device, cmx_match_stats* stats) {
   struct Plan {
@@ -583,6 +575,7 @@ void Rt2DLegacyBatch(const cmx_rt_options* options, const Rt2DItem* items, const
   }
 }
 
+namespace {
 // ScoreCandidates (SM2/real_time_correlative_scan_matcher_2d.cc:147-175), the method the
 // reference keeps "visible for testing": ANY list of (scan, x offset, y offset) over discrete
 // scans handed in by the caller.  One thread per candidate, the f32 sums in point order
@@ -622,6 +615,24 @@ __global__ void Rt2DScoreCandidatesKernel(const uint16_t* __restrict__ cells,
 }
 }  // namespace
 
+void Rt2DCheckItems(const cmx_rt_options* options, const Rt2DItem* items, int num) {
+  CMX_REQUIRE(options && items && num >= 1, "null argument");
+  const bool tsdf = items[0].tsdf();
+  for (int m = 0; m < num; ++m) {
+    const Rt2DItem& it = items[m];
+    CMX_REQUIRE(it.limits && (it.cells || it.device_cells) && it.initial && it.xyz,
+                "null argument");
+    CMX_REQUIRE(it.pose != nullptr && it.score != nullptr,
+                "pose_estimate must not be null");            // CHECK at :121
+    CMX_REQUIRE(it.n >= 1 && it.n <= (1 << 24), "bad point count");
+    CMX_REQUIRE(it.limits->resolution > 0. && it.limits->num_x_cells >= 1 &&
+                    it.limits->num_y_cells >= 1,
+                "bad map limits");
+    CMX_REQUIRE(it.tsdf() == tsdf, "mixed grid types in one batch");
+    if (tsdf) CMX_REQUIRE(it.max_tsd > 0.f && it.max_weight > 0.f, "bad TSDF ranges");
+  }
+}
+
 void Rt2DMatchBatch(const cmx_rt_options* options, const Rt2DItem* items, int num, int32_t device,
                     cmx_match_stats* stats) {
   CMX_REQUIRE(options && items && num >= 1, "null argument");
@@ -640,19 +651,7 @@ void Rt2DMatchBatch(const cmx_rt_options* options, const Rt2DItem* items, int nu
     t_last = now;
   };
   const bool tsdf = items[0].tsdf();
-  for (int m = 0; m < num; ++m) {
-    const Rt2DItem& it = items[m];
-    CMX_REQUIRE(it.limits && (it.cells || it.device_cells) && it.initial && it.xyz,
-                "null argument");
-    CMX_REQUIRE(it.pose != nullptr && it.score != nullptr,
-                "pose_estimate must not be null");            // CHECK at :121
-    CMX_REQUIRE(it.n >= 1 && it.n <= (1 << 24), "bad point count");
-    CMX_REQUIRE(it.limits->resolution > 0. && it.limits->num_x_cells >= 1 &&
-                    it.limits->num_y_cells >= 1,
-                "bad map limits");
-    CMX_REQUIRE(it.tsdf() == tsdf, "mixed grid types in one batch");
-    if (tsdf) CMX_REQUIRE(it.max_tsd > 0.f && it.max_weight > 0.f, "bad TSDF ranges");
-  }
+  Rt2DCheckItems(options, items, num);
   // SearchParameters of every item (a range scan over its cloud, acos): on the host pool, part
   // by part (below), so that the first part's kernels start under the planning of the others.
   std::vector<Rt2DSearch> search(num);

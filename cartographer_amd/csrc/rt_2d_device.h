@@ -48,6 +48,13 @@ __device__ __forceinline__ float CellProbability(unsigned raw) {
   return 1.f - cost;
 }
 
+// The (term, weight) a TSDF cell contributes (real_time_..._2d.cc:38-59,
+// mapping/internal/2d/tsdf_2d.cc:88-98, tsd_value_converter.cc:22-33).
+__device__ __forceinline__ float2 TsdfTerm(float tsd, float weight, float max_tsd) {
+  const float normalized = (max_tsd - fabsf(tsd)) / max_tsd;
+  return make_float2(normalized * weight, weight);
+}
+
 // The reference's discretisation of one point: pre-rotation by the initial yaw (q0), rotation of
 // the scan (qs), translation, MapLimits::GetCellIndex -- two yaw rotations without the exactly
 // zero terms (RotateZ, cmx_device.h: bit-identical x / y for finite coordinates), the cell index

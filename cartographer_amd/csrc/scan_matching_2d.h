@@ -202,6 +202,25 @@ struct Rt2DImageCache {
   ~Rt2DImageCache();
 };
 
+// The two byte images of a resident TSDF2D (rt_2d_tsdf.hip, Tsdf2DImageKernel): numerator and
+// weight of the real-time score, quantised upwards, with a zero halo of kTsdfImageHalo cells; what
+// the workgroups of the batched TSDF matcher copy into LDS.  They depend on the planes only
+// (`version`), not on the window; a cmx_tsdf2d owns one cache.  No lock is held across kernels:
+// the call that finds the cache stale and idle builds into it and publishes the version after its
+// stream has been waited for; a call that finds it being built, or stale while others read it,
+// builds its images into scratch of its own.
+constexpr int kTsdfImageHalo = 16;
+struct Tsdf2DImageCache {
+  std::mutex mutex;              // guards the fields below; never held across device work
+  uint8_t* images = nullptr;     // device: numerator image, then weight image
+  size_t capacity = 0;
+  bool valid = false, building = false;
+  int readers = 0;
+  unsigned long long version = 0;
+  int nx = 0, ny = 0;
+  ~Tsdf2DImageCache();
+};
+
 // RealTimeCorrelativeScanMatcher2D::Match (rt_2d.hip); see there.
 struct Rt2DItem {            // one match of a batch
   const cmx_grid2d_limits* limits;
@@ -220,6 +239,7 @@ struct Rt2DItem {            // one match of a batch
   Rt2DImageCache* image_cache = nullptr;  // with device_cells of a cmx_grid2d
   unsigned long long grid_version = 0;
   const uint16_t* device_weight_cells = nullptr;  // TSDF weights already in HBM (cmx_tsdf2d)
+  Tsdf2DImageCache* tsdf_image_cache = nullptr;   // with the planes of a cmx_tsdf2d (batch entries)
   bool tsdf() const { return weight_cells != nullptr || device_weight_cells != nullptr; }
 };
 // SearchParameters of one match (SM2/correlative_scan_matcher_2d.cc:27-47 on the cloud
@@ -259,6 +279,17 @@ class Rt2DTileCall {
 };
 void Rt2DMatchBatch(const cmx_rt_options* options, const Rt2DItem* items, int num, int32_t device,
                     cmx_match_stats* stats);
+// The argument checks of a batch (rt_2d.hip).
+void Rt2DCheckItems(const cmx_rt_options* options, const Rt2DItem* items, int num);
+// rt_2d.hip: a batch on the one-thread-per-candidate kernels (every score is the reference's own
+// f32 sum).
+void Rt2DLegacyBatch(const cmx_rt_options* options, const Rt2DItem* items, const Rt2DSearch* search,
+                     int num, int32_t device, cmx_match_stats* stats);
+// rt_2d_tsdf.hip: a batch of matches on resident TSDF2Ds (cmx_rt2d_match_tsdf_grid_batch*).  By
+// default Rt2DLegacyBatch; under the debug switch rt2d_tsdf_batch_bulk an integer bulk pass out of
+// LDS, then exact scores for the candidates its intervals cannot exclude.
+void Rt2DTsdfMatchBatch(const cmx_rt_options* options, const Rt2DItem* items, int num,
+                        int32_t device, cmx_match_stats* stats);
 // grid_2d.hip: Grid2D::GrowLimits of one uint16 plane (the old plane in the middle of one twice
 // as large, which the caller has filled with the unknown value) and the box of its non-zero
 // cells ({min_x, min_y, max_x, max_y}, preset by the caller to {INT_MAX, INT_MAX, -1, -1}).

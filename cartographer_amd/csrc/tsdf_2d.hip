@@ -47,6 +47,7 @@ struct cmx_tsdf2d {
   uint16_t* weight = nullptr;                            // device, nx * ny
   int32_t* owner = nullptr;                              // device, nx * ny; kNoOwner between calls
   unsigned long long version = 1;                        // bumped whenever the planes change
+  mutable cmx::Tsdf2DImageCache rt_image;                // byte images of the batched matcher
 };
 
 namespace cmx {
@@ -673,6 +674,84 @@ extern "C" cmx_status cmx_rt2d_match_tsdf_grid(const cmx_rt_options* options,
     item.pose = pose_estimate;
     item.grid_version = grid->version;
     cmx::Rt2DMatchBatch(options, &item, 1, grid->device, stats);
+  });
+}
+
+namespace {
+// One item of a batch entry: grid m, pose m, its cloud (host pointer, or a cmx_cloud).
+cmx::Rt2DItem TsdfBatchItem(const cmx_tsdf2d* g, const cmx_grid2d_limits* limits,
+                            const cmx_pose2d* initial, double* score, cmx_pose2d* pose) {
+  cmx::Rt2DItem item{};
+  item.limits = limits;
+  item.device_cells = g->tsd;
+  item.device_weight_cells = g->weight;
+  item.max_tsd = g->max_tsd;
+  item.max_weight = g->max_weight;
+  item.initial = initial;
+  item.score = score;
+  item.pose = pose;
+  item.grid_version = g->version;
+  item.tsdf_image_cache = &g->rt_image;
+  return item;
+}
+}  // namespace
+
+extern "C" cmx_status cmx_rt2d_match_tsdf_grid_batch(const cmx_rt_options* options,
+                                                     const cmx_tsdf2d* const* grids,
+                                                     int32_t num_matches,
+                                                     const cmx_pose2d* initial_pose_estimates,
+                                                     const float* const* point_clouds_xyz,
+                                                     const int32_t* num_points, double* scores,
+                                                     cmx_pose2d* pose_estimates,
+                                                     cmx_match_stats* stats) {
+  return Guard([&] {
+    CMX_REQUIRE(options && grids && initial_pose_estimates && point_clouds_xyz && num_points &&
+                    scores && pose_estimates && num_matches >= 1,
+                "null argument");
+    std::vector<cmx_grid2d_limits> limits(num_matches);
+    std::vector<cmx::Rt2DItem> items(num_matches);
+    for (int m = 0; m < num_matches; ++m) {
+      const cmx_tsdf2d* g = grids[m];
+      CMX_REQUIRE(g != nullptr, "null grid");
+      CMX_REQUIRE(g->device == grids[0]->device, "all grids of a batch must live on one device");
+      limits[m] = cmx_grid2d_limits{g->resolution, g->max_x, g->max_y, g->nx, g->ny, 0.f, 0.f};
+      items[m] = TsdfBatchItem(g, &limits[m], &initial_pose_estimates[m], &scores[m],
+                               &pose_estimates[m]);
+      items[m].xyz = point_clouds_xyz[m];
+      items[m].n = num_points[m];
+    }
+    cmx::Rt2DTsdfMatchBatch(options, items.data(), num_matches, grids[0]->device, stats);
+  });
+}
+
+extern "C" cmx_status cmx_rt2d_match_tsdf_grid_batch_resident(
+    const cmx_rt_options* options, const cmx_tsdf2d* const* grids, int32_t num_matches,
+    const cmx_pose2d* initial_pose_estimates, const cmx_cloud* const* clouds, double* scores,
+    cmx_pose2d* pose_estimates, cmx_match_stats* stats) {
+  return Guard([&] {
+    CMX_REQUIRE(options && grids && initial_pose_estimates && clouds && scores &&
+                    pose_estimates && num_matches >= 1,
+                "null argument");
+    std::vector<cmx_grid2d_limits> limits(num_matches);
+    std::vector<cmx::Rt2DItem> items(num_matches);
+    for (int m = 0; m < num_matches; ++m) {
+      const cmx_tsdf2d* g = grids[m];
+      const cmx_cloud* c = clouds[m];
+      CMX_REQUIRE(g != nullptr && c != nullptr, "null grid or cloud");
+      CMX_REQUIRE(g->device == grids[0]->device && c->device == g->device,
+                  "all grids and clouds of a batch must live on one device");
+      limits[m] = cmx_grid2d_limits{g->resolution, g->max_x, g->max_y, g->nx, g->ny, 0.f, 0.f};
+      items[m] = TsdfBatchItem(g, &limits[m], &initial_pose_estimates[m], &scores[m],
+                               &pose_estimates[m]);
+      items[m].xyz = c->host_xyz.data();      // the range scan of SearchParameters runs on the host
+      items[m].device_xyz = c->xyz;
+      if (!c->far_points.empty()) {
+        items[m].far_points = c->far_points.data();
+        items[m].num_far_points = static_cast<int>(c->far_points.size());
+      }
+      items[m].n = c->num_points;
+    }
+    cmx::Rt2DTsdfMatchBatch(options, items.data(), num_matches, grids[0]->device, stats);
   });
 }
 

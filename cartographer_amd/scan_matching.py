@@ -137,13 +137,29 @@ class RealTimeCorrelativeScanMatcher2D:
         return score.value, Rigid2d(pose.x, pose.y, pose.theta)
 
 
+def _batch_entries(grids):
+    """(host-cloud entry, resident-cloud entry) for a batch on `grids`: all ProbabilityGridOnDevice
+    or all TSDF2DOnDevice; a list mixing the two classes raises."""
+    from .grid_2d import TSDF2DOnDevice
+    tsdf = [isinstance(g, TSDF2DOnDevice) for g in grids]
+    if any(tsdf) and not all(tsdf):
+        raise ValueError("a batch takes grids of one type: ProbabilityGridOnDevice or "
+                         "TSDF2DOnDevice, not both")
+    L = _lib.lib()
+    if any(tsdf):
+        return L.cmx_rt2d_match_tsdf_grid_batch, L.cmx_rt2d_match_tsdf_grid_batch_resident
+    return L.cmx_rt2d_match_grid_batch, L.cmx_rt2d_match_grid_batch_resident
+
+
 def rt2d_match_batch(options, grids, initial_pose_estimates, point_clouds):
-    """cmx_rt2d_match_grid_batch: match i = (point_clouds[i], grids[i], initial_pose_estimates[i]);
-    `grids` are ProbabilityGridOnDevice, `options` an RtOptions (or a
-    RealTimeCorrelativeScanMatcher2D).  Returns (scores, poses, stats)."""
+    """cmx_rt2d_match_grid_batch / cmx_rt2d_match_tsdf_grid_batch: match i = (point_clouds[i],
+    grids[i], initial_pose_estimates[i]); `grids` are all ProbabilityGridOnDevice or all
+    TSDF2DOnDevice, `options` an RtOptions (or a RealTimeCorrelativeScanMatcher2D).  Returns
+    (scores, poses, stats)."""
     if isinstance(options, RealTimeCorrelativeScanMatcher2D):
         options = options.options
     num = len(grids)
+    entry = _batch_entries(grids)[0]
     clouds = [_cloud(c)[0] for c in point_clouds]
     handles = (C.c_void_p * num)(*[g._h for g in grids])
     cloud_ptrs = (C.c_void_p * num)(*[c.ctypes.data for c in clouds])
@@ -152,23 +168,25 @@ def rt2d_match_batch(options, grids, initial_pose_estimates, point_clouds):
     scores = np.zeros(num, np.float64)
     poses = (Pose2d * num)()
     stats = MatchStats()
-    check(_lib.lib().cmx_rt2d_match_grid_batch(
+    check(entry(
         C.byref(options), handles, num, C.cast(initial, C.c_void_p), cloud_ptrs,
         counts.ctypes.data, scores.ctypes.data, C.cast(poses, C.c_void_p), C.byref(stats)))
     return (scores, [Rigid2d(p.x, p.y, p.theta) for p in poses], stats.as_dict())
 
 
 class Rt2DBatch:
-    """The argument arrays of cmx_rt2d_match_grid_batch, built once: what a C++ caller holds
+    """The argument arrays of cmx_rt2d_match_grid_batch (cmx_rt2d_match_tsdf_grid_batch when the
+    grids are TSDF2DOnDevice), built once: what a C++ caller holds
     anyway (one resident grid and one scan buffer per trajectory / robot).  `match(poses)` takes
     the initial pose estimates as an (n, 3) float64 array (x, y, theta) and returns
     (scores, poses as an (n, 3) array, stats)."""
 
     def __init__(self, options, grids, point_clouds, resident=False):
         """resident=True: the scans are uploaded once (cmx_cloud) and every match() goes through
-        cmx_rt2d_match_grid_batch_resident; `point_clouds` may then also be PointCloudOnDevice."""
+        the `_resident` entry; `point_clouds` may then also be PointCloudOnDevice."""
         if isinstance(options, RealTimeCorrelativeScanMatcher2D):
             options = options.options
+        host_entry, resident_entry = _batch_entries(grids)
         self.options = options
         self.num = len(grids)
         self._grids = list(grids)                                  # keep the handles alive
@@ -181,12 +199,12 @@ class Rt2DBatch:
             self._clouds = [c if isinstance(c, PointCloudOnDevice) else PointCloudOnDevice(c)
                             for c in point_clouds]
             self._cloud_ptrs = (C.c_void_p * self.num)(*[c._h for c in self._clouds])
-            self._fn = _lib.lib().cmx_rt2d_match_grid_batch_resident
+            self._fn = resident_entry
         else:
             self._clouds = [_cloud(c)[0] for c in point_clouds]
             self._cloud_ptrs = (C.c_void_p * self.num)(*[c.ctypes.data for c in self._clouds])
             self._counts = np.array([c.shape[0] for c in self._clouds], np.int32)
-            self._fn = _lib.lib().cmx_rt2d_match_grid_batch
+            self._fn = host_entry
 
     def match(self, initial_pose_estimates):
         init = np.ascontiguousarray(initial_pose_estimates, np.float64).reshape(self.num, 3)

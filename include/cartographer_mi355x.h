@@ -299,6 +299,29 @@ cmx_status cmx_rt2d_match_tsdf_grid(const cmx_rt_options* options, const cmx_tsd
                                     const float* point_cloud_xyz, int32_t num_points,
                                     double* score, cmx_pose2d* pose_estimate,
                                     cmx_match_stats* stats);
+/* `num_matches` independent real-time matches on resident TSDF2Ds in one set of kernel
+ * launches: match i is exactly cmx_rt2d_match_tsdf_grid(options, grids[i],
+ * &initial_pose_estimates[i], cloud i, ...), score and pose bit for bit.  All grids (and clouds)
+ * of a call live on one device.  The entries run the one-thread-per-candidate batch kernels:
+ * `stats` sums the matches, candidates_scored is the search space, coarse_candidates and
+ * finalists equal it (every candidate is summed with the reference's own f32 sums and stands
+ * for the host's first-maximum rule) and refined_candidates is 0.  Debug only (switch
+ * rt2d_tsdf_batch_bulk): an integer bulk pass over two quantised byte images kept with the
+ * cmx_tsdf2d; then coarse_candidates is what that pass summed, refined_candidates the
+ * candidates evaluated with the f32 sums and finalists those weighted on the host. */
+cmx_status cmx_rt2d_match_tsdf_grid_batch(const cmx_rt_options* options,
+                                          const cmx_tsdf2d* const* grids, int32_t num_matches,
+                                          const cmx_pose2d* initial_pose_estimates,
+                                          const float* const* point_clouds_xyz,
+                                          const int32_t* num_points, double* scores,
+                                          cmx_pose2d* pose_estimates, cmx_match_stats* stats);
+cmx_status cmx_rt2d_match_tsdf_grid_batch_resident(const cmx_rt_options* options,
+                                                   const cmx_tsdf2d* const* grids,
+                                                   int32_t num_matches,
+                                                   const cmx_pose2d* initial_pose_estimates,
+                                                   const cmx_cloud* const* clouds, double* scores,
+                                                   cmx_pose2d* pose_estimates,
+                                                   cmx_match_stats* stats);
 cmx_status cmx_fast2d_create_from_tsdf(const cmx_fast2d_options* options, const cmx_tsdf2d* grid,
                                        cmx_fast2d** out);
 
