@@ -17,7 +17,8 @@
 //   * exp() weighting and the strict-'>' first-maximum rule are finished on the
 //     host for the candidates within 1e-5 (relative) of the device maximum.
 #include <algorithm>
-#include <functional>
+#include <cstddef>
+#include <optional>
 #include <type_traits>
 
 #include "scan_matching_3d.h"
@@ -214,7 +215,7 @@ __global__ void Rt3DCollectKernel(const float* __restrict__ weighted, long long 
 //     the host applies the libm weight and the first-maximum rule to them exactly as before.
 // Returned score and pose are bit-identical to the one-thread-per-candidate kernel above,
 // which remains the path for flat score landscapes (more finalists than the list holds) and
-// for windows / grids beyond the limits checked in cmx_rt3d_match.
+// for windows / grids beyond the limits checked in ModeOf (Rt3DMode::use_bulk).
 constexpr int kBulk3DThreads = 256;
 constexpr int kCand3DThreads = 128;         // candidate pass: work lists are short (a block's idle
                                             // wavefronts only hold wave slots)
@@ -492,7 +493,7 @@ Rt3DBoundsKernel(Rt3DBulkParams P) {
 // alive after a quarter of the points, 10 % after half.
 //
 // grid (work descriptors): flags[r][t] = 1 for the listed candidates that stay.  `stage` = the
-// segment just finished (0 or 1).  Verification mode (`stage_ub` != null: CMX_RT3D_VERIFY): the
+// segment just finished (0 or 1).  Verification mode (`stage_ub` != null: debug switch rt3d_verify): the
 // lists stay as they are, every candidate is evaluated in full, and this kernel only records the
 // decision (`dropped`) and the smallest bound seen (in units of q) for Rt3DStageCheckKernel.
 __global__ void __launch_bounds__(1024)
@@ -560,7 +561,7 @@ Rt3DStageCheckKernel(Rt3DBulkParams P, const unsigned long long* __restrict__ st
   }
 }
 
-// CMX_RT3D_VERIFY=1 (tests): a group's upper bound must not lie below the LOWER bound of any of
+// Debug switch rt3d_verify (tests): a group's upper bound must not lie below the LOWER bound of any of
 // its members that was scored -- both bracket the same true score.  (A group pass reading the
 // wrong staged rotation once produced garbage bounds that every parity test survived: the
 // optimum happened not to be pruned.)  grid (work descriptors).
@@ -604,7 +605,7 @@ Rt3DVerifyKernel(Rt3DBulkParams P, const float* __restrict__ group_upper, int nu
 // block) takes the memory gathers for that chunk -- same arithmetic, same sums.  The integer
 // sums are accumulated over chunk slices (blockIdx.y) with atomics; bounds come from
 // Rt3DSumBoundsKernel / Rt3DBoundsKernel.  Every sum is identical to what Rt3DBulkKernel
-// computes (CMX_RT3D_TILES=0 runs that kernel; tests compare the two).
+// computes (debug switch rt3d_no_tiles runs that kernel; tests compare the two).
 constexpr int kTileChunkGroups = 512;      // points per chunk, group pass (fewer, fuller work units)
 constexpr int kTileChunkCandidates = 256;  // ... candidate pass (its f32 stage is 12 B per point and rotation)
 constexpr int kTileBin = 24;
@@ -629,7 +630,7 @@ struct Rt3DTileParams {
   const int* seg_bounds;
   int seg_first, seg_last;
   uint2* seg_sums;
-  unsigned long long* stats;     // CMX_RT3D_REPORT (its atomics cost ~0.5 ms per pass: not for timing): [0] chunks in LDS, [1] on the gather path,
+  unsigned long long* stats;     // debug switch rt3d_report (its atomics cost ~0.5 ms per pass: not for timing): [0] chunks in LDS, [1] on the gather path,
                                  // [2] tile bytes, [3] points (per workgroup and chunk); or null
 };
 
@@ -1288,7 +1289,7 @@ Rt3DTileKernel(Rt3DBulkParams P, Rt3DTileParams TP) {
   }
 }
 
-// CMX_RT3D_CROSSCHECK=1 (tests): the tiled passes against the memory-gather kernels, element by
+// Debug switch rt3d_crosscheck (tests): the tiled passes against the memory-gather kernels, element by
 // element -- group upper bounds (bitwise) and candidate sums Q.
 __global__ void Rt3DCompareFloatsKernel(const float* __restrict__ a, const float* __restrict__ b,
                                         long long n, int* __restrict__ mismatches) {
@@ -1594,13 +1595,153 @@ __global__ void BrickBulkKernel(const uint16_t* __restrict__ cells, long long n,
   tiled[TiledOffset(x, y, z, tiles_y, pitch_z)] = q;
 }
 
-// Debug switch rt3d_legacy keeps every candidate on the one-thread-per-candidate kernel,
-// rt3d_no_tiles keeps the bulk passes on the memory gathers (Rt3DBulkKernel); parity tests run
-// every path.
-bool Tiles3DEnabled() { return Debug().rt3d_no_tiles == 0; }
-bool Bulk3DEnabled() { return Debug().rt3d_legacy == 0; }
+
+// ---- host side: what the brick helpers and the match driver below share ----------------------
+
+// Workspace buffers (Workspace::dev) of this file, one name per slot.
+enum Rt3DSlot {
+  kSlotCloud = 0,            // the cloud as uploaded
+  kSlotRotations = 1,
+  kSlotTranslations = 2,
+  kSlotAngles = 3,
+  kSlotUnweighted = 4,       // exhaustive search: unweighted scores; bounds search: work items
+  kSlotWeighted = 5,         // exhaustive search: weighted scores; bounds search: candidate bounds
+  kSlotMisc = 6,             // Rt3DExhaustiveMisc
+  kSlotProbabilities = 7,    // the padded f32 brick
+  kSlotQBrick = 8,           // q = value >> 7: row-major | tiled
+  kSlotDilated = 9,
+  kSlotScratch = 10,         // dilation scratch, then the (Q, A) sums of the candidate passes
+  kSlotGroupUpper = 11,
+  kSlotFlags = 12,           // [R][G] group expanded | [R][T] candidate flagged
+  kSlotBulkMisc = 13,        // Rt3DBulkHead | counts per rotation | work blocks | Rt3DCounters
+  kSlotGroups = 14,
+  kSlotVoxels = 15,          // the voxel list as uploaded
+  kSlotSorted = 16,          // the cloud sorted into bins
+  kSlotBins = 17,
+  kSlotGroupSums = 18,
+  kSlotCrosscheck = 19,      // rt3d_crosscheck: the gather kernels' results
+  kSlotGroupBoxes = 20,
+  kSlotListBoxes = 21,
+  kSlotStageBounds = 22,     // rt3d_verify: what the staged round decided
+  kSlotStageDropped = 23,
+  kSlotBlockRotations = 24,
+  kSlotBlockAngles = 25,
+  kSlotDilatedTwice = 26,
+  kSlotBlockBounds = 27,
+  kSlotPairs = 28,           // [R][G] pair computed | [R][G] pair flagged
+  kSlotReport = 29,          // rt3d_report: the tile kernels' counters
+};
+// ... and of Workspace::pinned.
+enum Rt3DPinnedSlot { kPinnedReadBack = 1, kPinnedBulkHead = 2, kPinnedGroups = 3 };
+
+// The misc blocks: one struct each for the device block and its pinned copy.  The kernels
+// receive pointers to single fields, so the layouts are pinned down below.
+constexpr int kFinalistCap = 4096;
+struct Rt3DExhaustiveMisc {               // Rt3DScoreKernel, Rt3DCollectKernel
+  unsigned max_bits;                      // atomicMax of the weighted scores
+  int count;                              // candidates collected (may exceed the capacity)
+  int reserved[2];
+  long long finalists[kFinalistCap];      // candidate index t * R + r
+};
+constexpr size_t kExhaustiveHeadBytes = offsetof(Rt3DExhaustiveMisc, finalists);   // zeroed per call
+static_assert(offsetof(Rt3DExhaustiveMisc, count) == 4 && kExhaustiveHeadBytes == 16 &&
+                  sizeof(Rt3DExhaustiveMisc) == 16 + sizeof(long long) * kFinalistCap,
+              "layout of the exhaustive search's misc block");
+
+constexpr int kBulkFinalistCap = 4096;
+struct Rt3DBulkHead {                     // head of the bounds search's misc block
+  unsigned max_lower;                     // bits of the best weighted lower bound (candidates)
+  int count;                              // finalists collected (may exceed the capacity)
+  unsigned max_upper;                     // bits of the best weighted upper bound (groups)
+  int total;                              // candidates that went through the candidate passes
+  int finalists[kBulkFinalistCap];        // r * T + t
+  float exact[kBulkFinalistCap];          // their exact unweighted scores
+};
+constexpr size_t kBulkHeadZeroed = offsetof(Rt3DBulkHead, finalists);              // zeroed per call
+static_assert(offsetof(Rt3DBulkHead, count) == 4 && offsetof(Rt3DBulkHead, max_upper) == 8 &&
+                  offsetof(Rt3DBulkHead, total) == 12 && kBulkHeadZeroed == 16 &&
+                  offsetof(Rt3DBulkHead, exact) == 16 + sizeof(int) * kBulkFinalistCap &&
+                  sizeof(Rt3DBulkHead) == 16 + (sizeof(int) + sizeof(float)) * kBulkFinalistCap,
+              "layout of the bounds search's misc head");
+
+struct Rt3DCounters {                     // behind the work blocks (two int2 slots)
+  int num_blocks;                         // work blocks of the list being compacted
+  int violations;                         // rt3d_verify: bounds that do not hold
+  int stage_total;                        // items of the staged re-compactions (kept apart from
+                                          // Rt3DBulkHead::total, which counts every item once)
+  int pair_total;                         // (rotation, group) pairs the pair rounds computed
+};
+static_assert(sizeof(Rt3DCounters) == 2 * sizeof(int2) && offsetof(Rt3DCounters, violations) == 4 &&
+                  offsetof(Rt3DCounters, stage_total) == 8 && offsetof(Rt3DCounters, pair_total) == 12,
+              "layout of the bounds search's counters");
+
+// Chunk counts Rt3DBinScanKernel leaves behind the bins (eight ints).
+enum Rt3DSegmentCount {
+  kGroupChunks = 0, kCandidateChunks = 1,   // chunks of either list
+  kGroupSegments = 2,                       // [2..3]: first chunk of segments 1 and 2, group list
+  kCandidateSegments = 4,                   // [4..5]: ... candidate list
+  kNumSegmentCounts = 8,
+};
+struct Rt3DReadBack {                     // pinned: what the host sizes its launches by
+  int num_blocks;
+  int segments[kNumSegmentCounts];
+  int pair_total;
+};
+// One pinned reservation: the two searches of a call read back into regions of their own.
+struct Rt3DPinnedReadBack {
+  Rt3DExhaustiveMisc exhaustive;
+  Rt3DReadBack bounds;
+};
+
+// Which of the equivalent paths run, and their tuning: the debug switches (all zero in
+// production; parity tests run every path) and the problem sizes, read in one place.
+struct Rt3DMode {
+  bool use_bulk;          // integer bounds before the exact scores (else: exhaustive search only)
+  bool use_tiles;         // bulk passes on LDS tiles (else: memory gathers, Rt3DBulkKernel)
+  bool crosscheck;        // tiled passes next to the gather kernels, every sum compared
+  bool use_boxes;         // chunk boxes from a pre-pass kernel (else: reduced per chunk in the tile kernel)
+  bool staged;            // second candidate round segment by segment (Rt3DStageFilterKernel)
+  bool rotblocks;         // the rotation-block level above the group pass (Rt3DSelectPairsKernel)
+  bool verify;            // every bound checked on the device against what it bounds
+  bool report;            // pass-by-pass report on stderr
+  bool expand_all;        // every group expanded in the first round
+  int rot_per_block;      // rotations of a group-pass workgroup
+  int list_rotations;     // rotations sharing one work list of the tiled list passes
+  int block_items;        // items per work block of the candidate passes
+  int group_tile_capacity, cand_tile_capacity;   // bytes of LDS tile
+  int group_fixed_point;  // group centres in packed fixed point (0: f32)
+  int sixteenths0, sixteenths1;                  // ends of point segments 0 and 1, per window
+  float first_pair_factor, first_round_factor;   // thresholds of the first rounds
+};
+
 // A tuning override (debug switches of the profiling tools): 0 = the default.
 int Override(int value, int fallback) { return value > 0 ? value : fallback; }
+
+// Box [lo, hi] (inclusive) as a brick without cells, within the index range every dense brick
+// of this library supports.
+Brick BoxBrick(const int lo[3], const int hi[3]) {
+  for (int k = 0; k < 3; ++k) {
+    CMX_REQUIRE(lo[k] > -(1 << 20) && hi[k] < (1 << 20), "voxel index out of range");
+  }
+  Brick b{};
+  b.lo_x = lo[0]; b.lo_y = lo[1]; b.lo_z = lo[2];
+  b.nx = hi[0] - lo[0] + 1; b.ny = hi[1] - lo[1] + 1; b.nz = hi[2] - lo[2] + 1;
+  return b;
+}
+
+// Bounding box of a voxel list; the cell at the origin when the list is empty.
+void VoxelBoxOrOrigin(const cmx_voxel* voxels, int64_t n, int lo[3], int hi[3]) {
+  if (VoxelBounds(voxels, n, lo, hi)) return;
+  lo[0] = lo[1] = lo[2] = 0;
+  hi[0] = hi[1] = hi[2] = 0;
+}
+
+// The voxel list on the device (kSlotVoxels), copy enqueued on ws.stream.
+cmx_voxel* UploadVoxels(Workspace& ws, const cmx_voxel* voxels, int64_t n) {
+  cmx_voxel* d_vox = ws.dev[kSlotVoxels].ReserveAs<cmx_voxel>(n);
+  CMX_HIP(hipMemcpyAsync(d_vox, voxels, n * sizeof(cmx_voxel), hipMemcpyHostToDevice, ws.stream));
+  return d_vox;
+}
 
 }  // namespace
 
@@ -1630,12 +1771,7 @@ int GridSizeOf(const cmx_voxel* voxels, int64_t n) {
 }
 
 void AllocateDenseBrick(const int lo[3], const int hi[3], int bytes_per_cell, DeviceBrick* out) {
-  for (int k = 0; k < 3; ++k) {
-    CMX_REQUIRE(lo[k] > -(1 << 20) && hi[k] < (1 << 20), "voxel index out of range");
-  }
-  Brick b{};
-  b.lo_x = lo[0]; b.lo_y = lo[1]; b.lo_z = lo[2];
-  b.nx = hi[0] - lo[0] + 1; b.ny = hi[1] - lo[1] + 1; b.nz = hi[2] - lo[2] + 1;
+  Brick b = BoxBrick(lo, hi);
   const size_t cells = static_cast<size_t>(b.nx) * b.ny * b.nz;
   CMX_REQUIRE(cells * bytes_per_cell < (size_t(8) << 30),
               "dense grid of %d x %d x %d cells is too large", b.nx, b.ny, b.nz);
@@ -1648,17 +1784,12 @@ void AllocateDenseBrick(const int lo[3], const int hi[3], int bytes_per_cell, De
 void BuildBrickFromVoxels(Workspace& ws, const cmx_voxel* voxels, int64_t n, int bytes_per_cell,
                           DeviceBrick* out) {
   int lo[3], hi[3];
-  if (!VoxelBounds(voxels, n, lo, hi)) {
-    lo[0] = lo[1] = lo[2] = 0;
-    hi[0] = hi[1] = hi[2] = 0;
-  }
+  VoxelBoxOrOrigin(voxels, n, lo, hi);
   AllocateDenseBrick(lo, hi, bytes_per_cell, out);
   const Brick b = out->desc;
   CMX_HIP(hipMemsetAsync(out->mem, 0, out->bytes, ws.stream));
   if (n > 0) {
-    cmx_voxel* d_vox = ws.dev[15].ReserveAs<cmx_voxel>(n);
-    CMX_HIP(hipMemcpyAsync(d_vox, voxels, n * sizeof(cmx_voxel), hipMemcpyHostToDevice,
-                           ws.stream));
+    const cmx_voxel* d_vox = UploadVoxels(ws, voxels, n);
     ScatterVoxelsKernel<<<DivUp(n, 256), 256, 0, ws.stream>>>(d_vox, n, b, bytes_per_cell);
     CMX_HIP(hipGetLastError());
   }
@@ -1667,903 +1798,1212 @@ void BuildBrickFromVoxels(Workspace& ws, const cmx_voxel* voxels, int64_t n, int
 
 }  // namespace cmx
 
+// ---- RealTimeCorrelativeScanMatcher3D::Match: the host driver ---------------------------------
 namespace cmx {
 namespace {
-// RealTimeCorrelativeScanMatcher3D::Match.  The HybridGrid is either the voxel list (host
-// memory) or, when `resident` is set, the dense uint16 brick cmx_grid3d keeps in HBM
-// (`voxels` unused then).
+
+// What is computed before the GPU is touched: GenerateExhaustiveSearchTransforms (:55-95) and
+// the 2 x 2 x 2 blocks of its two lattices.
+struct Rt3DSearchSpace {
+  int n = 0;                         // points
+  float resolution = 0.f;
+  int L = 0, A = 0;                  // linear / angular window in steps
+  float step = 0.f;                  // angular step
+  int side_t = 0, side_r = 0;
+  long long T = 0, R = 0, num_candidates = 0;
+  h3::Rigid init;
+  std::vector<float4> rot;           // [R] normalized(init.q * q_r), (x, y, z, w)
+  std::vector<float4> trans;         // [T] init.q * t_c + init.t; w = |t_c|
+  std::vector<float> angle;          // [R] GetAngle(transform)
+  // Rotation blocks (see Rt3DSelectPairsKernel): the centre rotation and the smallest member
+  // angle of each.
+  int Ab = 0;
+  long long Rb = 0;
+  std::vector<float4> rot_b;
+  std::vector<float> angle_b;
+  // Translation groups: centre translation; w = the smallest member distance.
+  int gpa = 0, G = 0;
+  std::vector<float4> group;
+};
+
+// The 2 x 2 x 2 blocks (fewer members along the far faces) of a side^3 lattice whose index
+// `half` is the origin: emit(k, centre in lattice steps * step, the smallest value_of(member)).
+template <typename ValueOf, typename Emit>
+void ForEachBlock2x2x2(int side, int half, float step, ValueOf value_of, Emit emit) {
+  const int per_axis = (side + 1) / 2;
+  long long k = 0;
+  for (int bz = 0; bz < per_axis; ++bz)
+    for (int by = 0; by < per_axis; ++by)
+      for (int bx = 0; bx < per_axis; ++bx, ++k) {
+        const int nx = std::min(2, side - 2 * bx), ny = std::min(2, side - 2 * by),
+                  nz = std::min(2, side - 2 * bz);
+        const h3::V3 centre{(2 * bx + 0.5f * (nx - 1) - half) * step,
+                            (2 * by + 0.5f * (ny - 1) - half) * step,
+                            (2 * bz + 0.5f * (nz - 1) - half) * step};
+        float smallest = INFINITY;
+        for (int c = 0; c < nz; ++c)
+          for (int b = 0; b < ny; ++b)
+            for (int a = 0; a < nx; ++a)
+              smallest = std::min(
+                  smallest, value_of(((2 * bz + c) * side + (2 * by + b)) * side + (2 * bx + a)));
+        emit(k, centre, smallest);
+      }
+}
+
+void FillCandidateTables(Rt3DSearchSpace* S) {
+  const int A = S->A, L = S->L;
+  const float step = S->step, resolution = S->resolution;
+  const h3::Rigid& init = S->init;
+  S->rot.resize(S->R); S->angle.resize(S->R); S->trans.resize(S->T);
+  long long k = 0;
+  for (int rz = -A; rz <= A; ++rz)
+    for (int ry = -A; ry <= A; ++ry)
+      for (int rx = -A; rx <= A; ++rx, ++k) {
+        h3::Rigid tf;
+        tf.q = h3::FromAngleAxisVector({rx * step, ry * step, rz * step});
+        S->angle[k] = h3::GetAngle(tf);
+        const h3::Q q = h3::Normalized(h3::Mul(init.q, tf.q));
+        S->rot[k] = make_float4(q.x, q.y, q.z, q.w);
+      }
+  k = 0;
+  for (int z = -L; z <= L; ++z)
+    for (int y = -L; y <= L; ++y)
+      for (int x = -L; x <= L; ++x, ++k) {
+        const h3::V3 tc{x * resolution, y * resolution, z * resolution};
+        const h3::V3 r = h3::Rotate(init.q, tc);
+        S->trans[k] = make_float4(r.x + init.t.x, r.y + init.t.y, r.z + init.t.z, h3::Norm(tc));
+      }
+}
+
+void FillBlockTables(Rt3DSearchSpace* S) {
+  const h3::Rigid& init = S->init;
+  S->Ab = (S->side_r + 1) / 2;
+  S->Rb = 1ll * S->Ab * S->Ab * S->Ab;
+  S->rot_b.resize(S->Rb); S->angle_b.resize(S->Rb);
+  ForEachBlock2x2x2(
+      S->side_r, S->A, S->step, [&](int r) { return S->angle[r]; },
+      [&](long long k, const h3::V3& centre, float smallest) {
+        const h3::Q q = h3::Normalized(h3::Mul(init.q, h3::FromAngleAxisVector(centre)));
+        S->rot_b[k] = make_float4(q.x, q.y, q.z, q.w);
+        S->angle_b[k] = smallest;
+      });
+  S->gpa = (S->side_t + 1) / 2;
+  S->G = S->gpa * S->gpa * S->gpa;
+  S->group.resize(S->G);
+  ForEachBlock2x2x2(
+      S->side_t, S->L, S->resolution, [&](int t) { return S->trans[t].w; },
+      [&](long long g, const h3::V3& centre, float nearest) {
+        const h3::V3 rc = h3::Rotate(init.q, centre);
+        S->group[g] = make_float4(rc.x + init.t.x, rc.y + init.t.y, rc.z + init.t.z, nearest);
+      });
+}
+
+Rt3DSearchSpace BuildSearchSpace(const cmx_rt_options& options, float resolution,
+                                 const cmx_pose3d& initial_pose_estimate,
+                                 const float* point_cloud_xyz, int n) {
+  Rt3DSearchSpace S;
+  S.n = n;
+  S.resolution = resolution;
+  S.L = static_cast<int>(std::lround(options.linear_search_window / resolution));
+  float max_scan_range = 3.f * resolution;
+  for (int i = 0; i < n; ++i) {
+    const h3::V3 p{point_cloud_xyz[3 * i], point_cloud_xyz[3 * i + 1], point_cloud_xyz[3 * i + 2]};
+    max_scan_range = std::max(h3::Norm(p), max_scan_range);
+  }
+  const float kSafetyMargin = 1.f - 1e-3f;
+  S.step = kSafetyMargin * std::acos(1.f - (resolution * (resolution * 1.f)) /
+                                               (2.f * (max_scan_range * (max_scan_range * 1.f))));
+  S.A = static_cast<int>(std::lround(options.angular_search_window / S.step));
+  CMX_REQUIRE(S.L >= 0 && S.L < 512 && S.A >= 0 && S.A < 64, "unsupported search window");
+  S.side_t = 2 * S.L + 1; S.side_r = 2 * S.A + 1;
+  S.T = 1ll * S.side_t * S.side_t * S.side_t;
+  S.R = 1ll * S.side_r * S.side_r * S.side_r;
+  S.num_candidates = S.T * S.R;
+  CMX_REQUIRE(S.num_candidates < (1ll << 31), "search window too large");
+  S.init = h3::FromPose(initial_pose_estimate);
+  FillCandidateTables(&S);
+  FillBlockTables(&S);
+  return S;
+}
+
+// The HybridGrid of a call: the voxel list (host memory) or, when `resident` is set, the dense
+// uint16 brick cmx_grid3d keeps in HBM (`voxels` unused then).
+struct Rt3DGridSource {
+  const cmx_voxel* voxels;
+  int64_t num_voxels;
+  const Brick* resident;
+};
+
+// The grid's box (no cells yet): the resident brick's own box (cells never written hold 0) or
+// the voxels' bounding box.
+PaddedBrick GridBox(const Rt3DGridSource& grid) {
+  const Brick* resident = grid.resident;
+  int lo[3], hi[3];
+  if (resident != nullptr) {
+    lo[0] = resident->lo_x; lo[1] = resident->lo_y; lo[2] = resident->lo_z;
+    hi[0] = lo[0] + resident->nx - 1; hi[1] = lo[1] + resident->ny - 1;
+    hi[2] = lo[2] + resident->nz - 1;
+  } else {
+    VoxelBoxOrOrigin(grid.voxels, grid.num_voxels, lo, hi);
+  }
+  const Brick box = BoxBrick(lo, hi);
+  const size_t cells = static_cast<size_t>(box.nx + 2) * (box.ny + 2) * (box.nz + 2);
+  CMX_REQUIRE(cells < (size_t(1) << 29), "dense grid of %d x %d x %d cells is too large", box.nx,
+              box.ny, box.nz);
+  return PaddedBrick{nullptr, box.lo_x, box.lo_y, box.lo_z, box.nx, box.ny, box.nz};
+}
+
+// The bricks of the bounds search: the grid's box widened by `pad` cells on every side.
+struct Rt3DBulkGeometry {
+  int reach = 0;                    // |init.q * t_c| in cells, rounded up
+  int pad = 0;
+  long long bx = 0, by = 0, bz = 0; // (rows a multiple of 4 cells: the tiled passes copy boxes
+                                    // of the brick with aligned dwords)
+  size_t cells = 0;
+  int tiles_x = 0, tiles_y = 0, pitch_z = 0;   // the tiled brick, see TiledOffset
+  size_t tiled_cells = 0;
+};
+
+Rt3DBulkGeometry BulkGeometry(const PaddedBrick& brick, int L) {
+  Rt3DBulkGeometry g;
+  g.reach = static_cast<int>(std::ceil(L * 1.7320508075688772)) + 1;
+  g.pad = 2 * g.reach + 2;
+  g.bx = (brick.nx + 2ll * g.pad + 3) & ~3ll;
+  g.by = brick.ny + 2ll * g.pad;
+  g.bz = brick.nz + 2ll * g.pad;
+  g.cells = static_cast<size_t>(g.bx * g.by * g.bz);
+  g.tiles_x = DivUp(g.bx, 8); g.tiles_y = DivUp(g.by, 4);
+  g.pitch_z = DivUp(g.bz, 4) * 4;
+  g.tiled_cells = static_cast<size_t>(g.tiles_x) * g.tiles_y * g.pitch_z * 32;
+  return g;
+}
+
+// The only reader of the debug switches on the match path.
+// Limits of the bounds search: finite points (a NaN would read an unchecked cell), N small
+// enough for the rounding bound of the f32 chain to mean something, index arithmetic exact in
+// f32, weights that decrease with distance (a group is weighted by its nearest member).
+Rt3DMode ModeOf(const Rt3DSearchSpace& S, const Rt3DBulkGeometry& geo,
+                const cmx_rt_options& options, const float* point_cloud_xyz) {
+  const DebugOptions& debug = Debug();
+  Rt3DMode m{};
+  m.use_bulk = debug.rt3d_legacy == 0 && S.n <= (1 << 21) && S.R <= 65535 &&
+               geo.bx * geo.by * geo.bz < (1ll << 24) &&
+               options.translation_delta_cost_weight >= 0. &&
+               options.rotation_delta_cost_weight >= 0.;
+  for (int i = 0; i < 3 * S.n && m.use_bulk; ++i) m.use_bulk = std::isfinite(point_cloud_xyz[i]);
+  // Rotations of a group-pass workgroup: as many as fit 512 lanes, so that TWO workgroups
+  // share a CU and one computes while the other stages its next chunk (C4, 216 groups: two
+  // rotations = 448 lanes, group pass 5.51 -> 4.91 ms against four rotations in one 896-lane
+  // workgroup per CU; debug switch rt3d_group_rotations overrides, experiments).
+  m.rot_per_block = std::max(
+      1, std::min({kTileMaxRotations, std::max(1, 512 / std::max(S.G, 1)),
+                   Override(debug.rt3d_group_rotations, kTileMaxRotations)}));
+  m.use_tiles = debug.rt3d_no_tiles == 0 && S.G <= 1024;
+  m.crosscheck = m.use_tiles && debug.rt3d_crosscheck != 0;
+  m.use_boxes = debug.rt3d_no_boxes == 0;
+  // The cross-check compares complete sums and the expand-all mode has no second round.
+  m.staged = m.use_tiles && !m.crosscheck && debug.rt3d_unstaged == 0 && debug.rt3d_expand_all == 0;
+  // The rotation-block level needs a window of more than one rotation per axis, small enough
+  // for the 1.03 of its bound, and the lists of the tiled passes.
+  m.rotblocks = m.use_tiles && !m.crosscheck && debug.rt3d_no_rotblocks == 0 && S.A >= 1 &&
+                (S.A + 1) * static_cast<double>(S.step) * 1.7320508 <= 0.2;
+  m.verify = debug.rt3d_verify != 0;
+  m.report = debug.rt3d_report != 0;
+  // (with rt3d_verify: every group bound is then checked against every one of its members)
+  m.expand_all = debug.rt3d_expand_all != 0;
+  // (several rotations per work list, so that a tile serves some hundred lanes even when a
+  // rotation keeps only a few dozen entries)
+  m.list_rotations = m.use_tiles && !m.crosscheck
+                         ? std::max(1, std::min(8, Override(debug.rt3d_cand_rotations, 8))) : 1;
+  m.block_items = !m.use_tiles ? kCand3DThreads
+                  : m.crosscheck ? 256 : Override(debug.rt3d_cand_threads, 512);
+  m.group_tile_capacity = Override(debug.rt3d_group_tile_kb, 44) * 1024;
+  m.cand_tile_capacity = Override(debug.rt3d_cand_tile_kb, 48) * 1024;
+  // (the float path reproduces the gather kernel's sums)
+  m.group_fixed_point = (debug.rt3d_group_float || m.crosscheck) ? 0 : 1;
+  // rt3d_segments = a | b << 8: the first segment ends at a / 16, the second at b / 16 of a
+  // window; default a quarter and a half.
+  m.sixteenths0 = 4; m.sixteenths1 = 8;
+  if (const int seg = debug.rt3d_segments; seg > 0) {
+    m.sixteenths0 = std::max(1, std::min(15, seg & 0xff));
+    m.sixteenths1 = std::max(m.sixteenths0, std::min(15, (seg >> 8) & 0xff));
+  }
+  // first rounds: the pairs of the blocks / the members of the groups next to the best bound
+  const int permille = debug.rt3d_rotblock_permille;
+  m.first_pair_factor =
+      m.expand_all ? 0.f : permille > 0 ? std::min(permille, 1000) * 1e-3f : 0.97f;
+  m.first_round_factor = m.expand_all ? 0.f : 0.97f;
+  return m;
+}
+
+// What a call keeps on the device for both searches.
+struct Rt3DDevice {
+  PaddedBrick brick;                 // f32 probabilities, border of kMinProbability
+  const cmx_voxel* d_vox = nullptr;  // the uploaded voxel list, or null (none, or a resident grid)
+  float* d_xyz = nullptr;
+  float4 *d_rot = nullptr, *d_trans = nullptr, *d_rot_b = nullptr;
+  float *d_angle = nullptr, *d_angle_b = nullptr;
+  float *d_unweighted = nullptr, *d_weighted = nullptr;   // [num_candidates] each
+  Rt3DExhaustiveMisc* d_misc = nullptr;
+  Rt3DPinnedReadBack* pinned = nullptr;
+  Rt3DParams P;
+};
+
+// Padded f32 probability brick over `box`, filled with kMinProbability and then with the
+// voxels (uploaded here) or the resident brick's cells.
+void BuildProbabilityBrick(Workspace& ws, const PaddedBrick& box, const Rt3DGridSource& grid,
+                           Rt3DDevice* D) {
+  const Brick* resident = grid.resident;
+  const int64_t num_voxels = grid.num_voxels;
+  const size_t cells = static_cast<size_t>(box.nx + 2) * (box.ny + 2) * (box.nz + 2);
+  float* d_cells = ws.dev[kSlotProbabilities].ReserveAs<float>(cells);
+  D->brick = box;
+  D->brick.cells = d_cells;
+  FillFloatKernel<<<DivUp(cells, 256), 256, 0, ws.stream>>>(d_cells, cells, 0.1f);
+  if (resident != nullptr) {
+    const long long count = static_cast<long long>(resident->nx) * resident->ny * resident->nz;
+    BrickProbabilitiesKernel<<<DivUp(count, 256), 256, 0, ws.stream>>>(
+        static_cast<const uint16_t*>(resident->cells), count, resident->nx, resident->ny,
+        D->brick, d_cells);
+  } else if (num_voxels > 0) {
+    D->d_vox = UploadVoxels(ws, grid.voxels, num_voxels);
+    ScatterProbabilitiesKernel<<<DivUp(num_voxels, 256), 256, 0, ws.stream>>>(
+        D->d_vox, num_voxels, D->brick, d_cells);
+  }
+  CMX_HIP(hipGetLastError());
+}
+
+template <typename T>
+T* Upload(Workspace& ws, int slot, const std::vector<T>& table) {
+  T* d = ws.dev[slot].ReserveAs<T>(table.size());
+  CMX_HIP(hipMemcpyAsync(d, table.data(), table.size() * sizeof(T), hipMemcpyHostToDevice,
+                         ws.stream));
+  return d;
+}
+
+// Cloud and candidate tables; returns when the copies are done.
+void UploadTables(Workspace& ws, const Rt3DSearchSpace& S, const cmx_rt_options& options,
+                  const float* point_cloud_xyz, Rt3DDevice* D) {
+  D->d_xyz = ws.dev[kSlotCloud].ReserveAs<float>(3 * static_cast<size_t>(S.n));
+  D->d_unweighted = ws.dev[kSlotUnweighted].ReserveAs<float>(S.num_candidates);
+  D->d_weighted = ws.dev[kSlotWeighted].ReserveAs<float>(S.num_candidates);
+  D->d_misc = static_cast<Rt3DExhaustiveMisc*>(ws.dev[kSlotMisc].Reserve(sizeof(Rt3DExhaustiveMisc)));
+  D->pinned = static_cast<Rt3DPinnedReadBack*>(
+      ws.pinned[kPinnedReadBack].Reserve(sizeof(Rt3DPinnedReadBack)));
+  CMX_HIP(hipMemcpyAsync(D->d_xyz, point_cloud_xyz, 3 * sizeof(float) * S.n,
+                         hipMemcpyHostToDevice, ws.stream));
+  D->d_rot = Upload(ws, kSlotRotations, S.rot);
+  D->d_trans = Upload(ws, kSlotTranslations, S.trans);
+  D->d_angle = Upload(ws, kSlotAngles, S.angle);
+  D->d_rot_b = Upload(ws, kSlotBlockRotations, S.rot_b);
+  D->d_angle_b = Upload(ws, kSlotBlockAngles, S.angle_b);
+  CMX_HIP(hipMemsetAsync(D->d_misc, 0, kExhaustiveHeadBytes, ws.stream));
+  // pageable sources above: make sure the copies are done before they go away
+  CMX_HIP(hipStreamSynchronize(ws.stream));
+
+  Rt3DParams& P = D->P;
+  P.grid = D->brick;
+  P.resolution = S.resolution;
+  P.inv_resolution = 1.f / S.resolution;
+  P.num_translations = static_cast<int>(S.T);
+  P.num_rotations = static_cast<int>(S.R);
+  P.side_t = S.side_t; P.side_r = S.side_r;
+  P.rotation = D->d_rot; P.translation = D->d_trans; P.rotation_angle = D->d_angle;
+  P.wt = options.translation_delta_cost_weight;
+  P.wr = options.rotation_delta_cost_weight;
+}
+
+// What either search hands to the final weighting, and what the bounds search counted.
+struct Rt3DFinalists {
+  std::vector<long long> index;      // reference candidate index t * R + r, ascending
+  std::vector<float> acc;            // their exact unweighted scores
+  int num_finalists = 0;             // bounds search: candidates re-scored exactly
+  long long bounds_evaluated = 0;
+  long long group_bounds = 0;        // bounds above the candidates: rotation blocks + (rotation, group) pairs
+  bool second_pairs_pass = false;    // (its span: ev_x0 .. ev_x1)
+};
+
+// ---- integer bounds (rotation blocks, groups, then candidates) + exact finalists --------------
+
+// What crosses between the stages of the bounds search.
+struct Rt3DBoundsSearch {
+  Workspace* ws = nullptr;
+  const Rt3DSearchSpace* S = nullptr;
+  const Rt3DDevice* D = nullptr;
+  Rt3DMode mode{};
+  Rt3DBulkGeometry geo;
+  int cus = 256;
+  long long RG = 0;                  // (rotation, group) pairs
+  int num_lists = 0;                 // work lists of the list passes
+  int max_chunks = 0;                // capacity of either chunk list
+  // bricks of q = value >> 7
+  uint8_t* d_rows = nullptr;         // row-major (the input of the dilation, the tiled passes)
+  uint8_t* d_tiled = nullptr;        // columns of 8 x 4 cells (the gather candidate pass)
+  uint8_t* d_dilated = nullptr;      // 2 x 2 x 2 maximum: the group pass
+  uint8_t* d_tmp = nullptr;          // dilation scratch first, then the candidates' (Q, A)
+  // groups and candidates
+  float4* d_group = nullptr;
+  float* d_group_upper = nullptr;    // [R][G]
+  uint2* d_group_sums = nullptr;     // tiled passes: [R][G] totals (| [R][G] per segment: staged)
+  uint8_t* d_expanded = nullptr;     // [R][G]
+  uint8_t* d_flags = nullptr;        // [R][T]
+  float* d_upper = nullptr;          // [R][T], the exhaustive search's weighted scores reused
+  int* d_items = nullptr;            // [R][T], ... unweighted scores reused
+  Rt3DBulkHead* d_head = nullptr;
+  int* d_counts = nullptr;           // [R] items per rotation
+  int2* d_blocks = nullptr;          // work descriptors of a round
+  Rt3DCounters* d_counters = nullptr;
+  Rt3DBulkHead* h_head = nullptr;    // pinned
+  Rt3DReadBack* h_read = nullptr;    // pinned
+  // tiled passes
+  int* d_segment_counts = nullptr;   // Rt3DSegmentCount
+  float* d_list_boxes = nullptr;     // chunk boxes of the candidate chunk list, per work list
+  // rotation blocks
+  uint8_t* d_computed = nullptr;     // [R][G] pair computed | [R][G] pair flagged
+  float* d_block_upper = nullptr;    // [Rb][G]
+  unsigned* d_block_max = nullptr;
+  Rt3DBulkParams base{};             // what every pass shares
+  Rt3DTileParams tiles{};            // ... every tiled pass: sorted cloud, group chunk list
+  int round_blocks[2] = {0, 0};
+  int stage_blocks[2] = {-1, -1};    // work blocks left after segments 0 and 1
+  bool second_pairs_pass = false;
+  std::optional<StageTrace> trace;
+
+  hipStream_t stream() const { return ws->stream; }
+};
+
+// Row-major and tiled q bricks from the voxels or the resident brick, and the dilation.
+void BuildBulkBricks(Rt3DBoundsSearch* run, const Rt3DGridSource& grid) {
+  const Brick* resident = grid.resident;
+  const int64_t num_voxels = grid.num_voxels;
+  Workspace& ws = *run->ws;
+  const Rt3DBulkGeometry& g = run->geo;
+  const PaddedBrick& brick = run->D->brick;
+  const int bx = static_cast<int>(g.bx), by = static_cast<int>(g.by), bz = static_cast<int>(g.bz);
+  // [row-major q | tiled q]
+  run->d_rows = ws.dev[kSlotQBrick].ReserveAs<uint8_t>(g.cells + 128 + g.tiled_cells);
+  run->d_tiled = run->d_rows + (g.cells + 127) / 128 * 128;
+  run->d_dilated = ws.dev[kSlotDilated].ReserveAs<uint8_t>(g.cells);
+  run->d_tmp = ws.dev[kSlotScratch].ReserveAs<uint8_t>(
+      std::max<size_t>(g.cells, sizeof(uint2) * static_cast<size_t>(run->S->num_candidates)));
+  CMX_HIP(hipMemsetAsync(run->d_rows, 0, (run->d_tiled - run->d_rows) + g.tiled_cells, ws.stream));
+  if (resident != nullptr) {
+    const long long count = static_cast<long long>(resident->nx) * resident->ny * resident->nz;
+    BrickBulkKernel<<<DivUp(count, 256), 256, 0, ws.stream>>>(
+        static_cast<const uint16_t*>(resident->cells), count, resident->nx, resident->ny, g.pad,
+        bx, by, g.tiles_y, g.pitch_z, run->d_rows, run->d_tiled);
+  } else if (num_voxels > 0) {
+    ScatterBulkKernel<<<DivUp(num_voxels, 256), 256, 0, ws.stream>>>(
+        run->D->d_vox, num_voxels, brick.lo_x, brick.lo_y, brick.lo_z, g.pad, bx, by, g.tiles_y,
+        g.pitch_z, run->d_rows, run->d_tiled);
+  }
+  DilateXKernel<<<DivUp(g.cells, 256), 256, 0, ws.stream>>>(run->d_rows, run->d_tmp, bx, g.cells);
+  DilateYZKernel<<<DivUp(g.cells, 256), 256, 0, ws.stream>>>(run->d_tmp, run->d_dilated, bx, by, bz);
+}
+
+// Group table, bound arrays, flags and the misc block; everything a call starts from zeroed.
+void ReserveBoundsBuffers(Rt3DBoundsSearch* run) {
+  Workspace& ws = *run->ws;
+  const Rt3DSearchSpace& S = *run->S;
+  const long long RG = run->RG;
+  run->d_group = ws.dev[kSlotGroups].ReserveAs<float4>(S.G);
+  run->d_group_upper = ws.dev[kSlotGroupUpper].ReserveAs<float>(RG);
+  run->d_expanded = ws.dev[kSlotFlags].ReserveAs<uint8_t>(RG + S.num_candidates);
+  run->d_flags = run->d_expanded + RG;
+  run->d_upper = run->D->d_weighted;
+  run->d_items = reinterpret_cast<int*>(run->D->d_unweighted);
+  // work descriptors of a round: at most one per 256 translations and rotation
+  const int max_blocks = static_cast<int>(S.R) * DivUp(S.T, kCand3DThreads);   // (>= any block size used)
+  const size_t counts_bytes = (sizeof(int) * S.R + 15) / 16 * 16;
+  char* d_bmisc = static_cast<char*>(ws.dev[kSlotBulkMisc].Reserve(
+      sizeof(Rt3DBulkHead) + counts_bytes + sizeof(int2) * max_blocks + sizeof(Rt3DCounters)));
+  run->d_head = reinterpret_cast<Rt3DBulkHead*>(d_bmisc);
+  run->d_counts = reinterpret_cast<int*>(run->d_head + 1);
+  run->d_blocks = reinterpret_cast<int2*>(d_bmisc + sizeof(Rt3DBulkHead) + counts_bytes);
+  run->d_counters = reinterpret_cast<Rt3DCounters*>(run->d_blocks + max_blocks);
+  run->h_read = &run->D->pinned->bounds;
+  run->h_head = static_cast<Rt3DBulkHead*>(ws.pinned[kPinnedBulkHead].Reserve(sizeof(Rt3DBulkHead)));
+  float4* h_group = ws.pinned[kPinnedGroups].ReserveAs<float4>(S.G);
+  std::memcpy(h_group, S.group.data(), sizeof(float4) * S.G);
+  CMX_HIP(hipMemcpyAsync(run->d_group, h_group, sizeof(float4) * S.G, hipMemcpyHostToDevice,
+                         ws.stream));
+  CMX_HIP(hipMemsetAsync(run->d_head, 0, kBulkHeadZeroed, ws.stream));
+  CMX_HIP(hipMemsetAsync(run->d_counters, 0, sizeof(Rt3DCounters), ws.stream));
+  CMX_HIP(hipMemsetAsync(run->d_counts, 0, sizeof(int) * S.R, ws.stream));
+  CMX_HIP(hipMemsetAsync(run->d_expanded, 0, RG + S.num_candidates, ws.stream));
+  CMX_HIP(hipMemsetAsync(run->d_upper, 0, sizeof(float) * S.num_candidates, ws.stream));
+}
+
+// What every bulk pass shares: index arithmetic, clamp range, bound constants.
+Rt3DBulkParams BaseBulkParams(const Rt3DBoundsSearch& run) {
+  const Rt3DSearchSpace& S = *run.S;
+  const Rt3DBulkGeometry& g = run.geo;
+  const PaddedBrick& brick = run.D->brick;
+  const int n = S.n, pad = g.pad, reach = g.reach;
+  const float resolution = S.resolution;
+  Rt3DBulkParams B{};
+  B.cell_count = static_cast<unsigned>(g.cells);
+  B.pitch_x = static_cast<float>(g.bx); B.pitch_y = static_cast<float>(g.by);
+  B.off_x = static_cast<float>(pad - brick.lo_x);
+  B.off_y = static_cast<float>(pad - brick.lo_y);
+  B.off_z = static_cast<float>(pad - brick.lo_z);
+  B.inv_resolution = 1.f / resolution;
+  double q_abs = 0.;
+  const int los[3] = {brick.lo_x, brick.lo_y, brick.lo_z};
+  const int dims[3] = {brick.nx, brick.ny, brick.nz};
+  for (int k = 0; k < 3; ++k)
+    q_abs = std::max<double>(q_abs, std::max(std::abs(los[k] - pad),
+                                             std::abs(los[k] + dims[k] - 1 + pad)));
+  const double q_pad = static_cast<double>(std::max(g.bx, std::max(g.by, g.bz)));
+  // |q - (qe + off)| <= (2 |c / res| + |q|) 2^-24 (rounded 1/res, one fma rounding, the
+  // reference's rounded quotient qe); 25 % on top.
+  const double e = (2. * q_abs + q_pad + 4.) * 0x1p-24 * 1.25;
+  B.guard = std::nextafter(static_cast<float>(0.5 - e), 0.f);
+  B.t0x = S.init.t.x; B.t0y = S.init.t.y; B.t0z = S.init.t.z;
+  B.lo_x = (brick.lo_x - reach - 1) * resolution;
+  B.hi_x = (brick.lo_x + brick.nx + reach) * resolution;
+  B.lo_y = (brick.lo_y - reach - 1) * resolution;
+  B.hi_y = (brick.lo_y + brick.ny + reach) * resolution;
+  B.lo_z = (brick.lo_z - reach - 1) * resolution;
+  B.hi_z = (brick.lo_z + brick.nz + reach) * resolution;
+  B.num_rotations = static_cast<int>(S.R);
+  B.n = n;
+  B.rotation = run.D->d_rot; B.rotation_angle = run.D->d_angle;
+  B.wt = run.D->P.wt; B.wr = run.D->P.wr;
+  const float kMinP = 0.1f, kMaxP = 1.f - kMinP;
+  const float scale = (kMaxP - kMinP) / (32768 - 2.f);
+  B.min_probability = kMinP;
+  B.scale_over_n = 128. * static_cast<double>(scale) / n;
+  B.slack_hi = 127. * static_cast<double>(scale) + 2e-7;
+  const double ku = (n + 8.) * 0x1p-24;
+  B.delta = ku / (1. - ku) * 1.01 + 2e-6;
+  B.max_lower_bits = &run.d_head->max_lower; B.max_upper_bits = &run.d_head->max_upper;
+  return B;
+}
+
+// Tiled passes: the cloud sorted into bins of kTileBin^3 cells at the central candidate, and
+// the two chunk lists over the bins.
+void SortCloudIntoBins(Rt3DBoundsSearch* run) {
+  Workspace& ws = *run->ws;
+  const Rt3DSearchSpace& S = *run->S;
+  const Rt3DBulkGeometry& g = run->geo;
+  const Rt3DBulkParams& B = run->base;
+  const int n = S.n;
+  Rt3DBinParams BP{};
+  BP.rotation = S.rot[S.R / 2];
+  BP.translation = S.trans[S.T / 2];
+  BP.inv_resolution = B.inv_resolution;
+  BP.off_x = B.off_x; BP.off_y = B.off_y; BP.off_z = B.off_z;
+  BP.t0x = B.t0x; BP.t0y = B.t0y; BP.t0z = B.t0z;
+  BP.lo_x = B.lo_x; BP.hi_x = B.hi_x; BP.lo_y = B.lo_y; BP.hi_y = B.hi_y;
+  BP.lo_z = B.lo_z; BP.hi_z = B.hi_z;
+  BP.bins_x = DivUp(g.bx, kTileBin); BP.bins_y = DivUp(g.by, kTileBin);
+  BP.bins_z = DivUp(g.bz, kTileBin);
+  BP.n = n;
+  const int num_bins = BP.bins_x * BP.bins_y * BP.bins_z;
+  run->max_chunks = n / kTileChunkCandidates + num_bins + 1;      // (either list)
+  const int max_chunks = run->max_chunks;
+  float* d_sorted = ws.dev[kSlotSorted].ReserveAs<float>(3 * static_cast<size_t>(n));
+  // [bin counts | Rt3DSegmentCount | group chunk list | candidate chunk list]
+  int* d_bin_count = static_cast<int*>(ws.dev[kSlotBins].Reserve(
+      sizeof(int) * (num_bins + kNumSegmentCounts) +
+      2 * sizeof(int2) * static_cast<size_t>(max_chunks)));
+  int* d_chunk_count = d_bin_count + num_bins;
+  int2* d_chunks = reinterpret_cast<int2*>(d_chunk_count + kNumSegmentCounts);
+  int2* d_chunks_candidates = d_chunks + max_chunks;
+  CMX_HIP(hipMemsetAsync(d_bin_count, 0, sizeof(int) * (num_bins + kNumSegmentCounts), ws.stream));
+  Rt3DBinCountKernel<<<DivUp(n, 256), 256, 0, ws.stream>>>(BP, run->D->d_xyz, d_bin_count);
+  // (segment windows: sixteen or more periods over a large cloud, never shorter than four
+  // group-pass pieces)
+  const int segment_window = n >= 32768 ? 4096 : 2048;
+  Rt3DBinScanKernel<<<1, 1024, 0, ws.stream>>>(
+      d_bin_count, num_bins, d_chunks, d_chunks_candidates, d_chunk_count, segment_window,
+      segment_window / 16 * run->mode.sixteenths0, segment_window / 16 * run->mode.sixteenths1);
+  run->d_segment_counts = d_chunk_count;
+  Rt3DBinScatterKernel<<<DivUp(n, 256), 256, 0, ws.stream>>>(BP, run->D->d_xyz, d_bin_count,
+                                                              d_sorted);
+  CMX_HIP(hipGetLastError());
+  Rt3DTileParams& TG = run->tiles;
+  if (run->mode.report) {
+    TG.stats = reinterpret_cast<unsigned long long*>(ws.dev[kSlotReport].Reserve(64));
+    CMX_HIP(hipMemsetAsync(TG.stats, 0, 64, ws.stream));
+  }
+  TG.sorted_xyz = d_sorted;
+  TG.chunks = d_chunks;
+  TG.num_chunks = d_chunk_count + kGroupChunks;
+  TG.pitch_x = static_cast<int>(g.bx); TG.pitch_y = static_cast<int>(g.by);
+  TG.pitch_z = static_cast<int>(g.bz);
+  run->trace->Mark("bins");
+}
+
+// Span of a translation table in cells (what widens a chunk's box into its tile).
+void SpanOf(const std::vector<float4>& table, float inv_resolution, Rt3DTileParams* tp) {
+  for (int a = 0; a < 3; ++a) { tp->tr_lo[a] = INFINITY; tp->tr_hi[a] = -INFINITY; }
+  for (const float4& v : table) {
+    const float c[3] = {v.x * inv_resolution, v.y * inv_resolution, v.z * inv_resolution};
+    for (int a = 0; a < 3; ++a) {
+      tp->tr_lo[a] = std::min(tp->tr_lo[a], c[a]);
+      tp->tr_hi[a] = std::max(tp->tr_hi[a], c[a]);
+    }
+  }
+}
+
+// ---- the parameter sets of the passes: what differs from the base -----------------------------
+
+// Group pass: every rotation, every block of translations, on the dilated brick.
+Rt3DBulkParams GroupParams(const Rt3DBoundsSearch& run) {
+  Rt3DBulkParams p = run.base;
+  p.cells = run.d_dilated;
+  p.translation = run.d_group; p.num_translations = run.S->G;
+  p.upper = run.d_group_upper;
+  p.sums = run.d_group_sums;
+  return p;
+}
+
+// ... tiled: the group table's span, several rotations per workgroup; staged: the sums over
+// point segments 0 and 1 next to the totals.
+Rt3DTileParams GroupTiles(const Rt3DBoundsSearch& run) {
+  Rt3DTileParams t = run.tiles;
+  SpanOf(run.S->group, run.base.inv_resolution, &t);
+  t.rotations_per_block = run.mode.rot_per_block;
+  t.tile_capacity = run.mode.group_tile_capacity;
+  t.fixed_point = run.mode.group_fixed_point;
+  if (run.mode.staged) {
+    t.seg_bounds = run.d_segment_counts + kGroupSegments;
+    t.seg_first = 0; t.seg_last = 2;
+    t.seg_sums = run.d_group_sums + run.RG;
+  }
+  return t;
+}
+
+// Sparse pair pass: the group pass over work lists of (rotation, group) pairs, on the
+// candidate pass's chunk list (256 points).
+constexpr int kPairItems = 512;
+Rt3DBulkParams PairParams(const Rt3DBoundsSearch& run) {
+  Rt3DBulkParams p = GroupParams(run);
+  p.counts = run.d_counts; p.items = run.d_items; p.blocks = run.d_blocks;
+  p.list_rotations = run.mode.list_rotations; p.block_items = kPairItems;
+  return p;
+}
+Rt3DTileParams PairTiles(const Rt3DBoundsSearch& run) {
+  Rt3DTileParams t = GroupTiles(run);
+  t.chunks = run.tiles.chunks + run.max_chunks;
+  t.num_chunks = run.d_segment_counts + kCandidateChunks;
+  t.block_items = kPairItems;
+  t.boxes = run.d_list_boxes;
+  if (run.mode.staged) t.seg_bounds = run.d_segment_counts + kCandidateSegments;
+  return t;
+}
+
+// Candidate passes: work lists over the translation table; the tiled brick for the gathers, the
+// row-major one for the tiles.
+Rt3DBulkParams CandidateParams(const Rt3DBoundsSearch& run) {
+  Rt3DBulkParams p = run.base;
+  p.cells = run.d_tiled;
+  p.cell_count = static_cast<unsigned>(run.geo.tiled_cells);
+  p.tiles_y = run.geo.tiles_y; p.pitch_z = run.geo.pitch_z;
+  p.translation = run.D->d_trans; p.num_translations = static_cast<int>(run.S->T);
+  p.counts = run.d_counts; p.items = run.d_items; p.blocks = run.d_blocks;
+  p.upper = run.d_upper;
+  p.sums = reinterpret_cast<uint2*>(run.d_tmp);
+  p.block_items = run.mode.block_items;
+  p.list_rotations = run.mode.list_rotations;
+  if (run.mode.use_tiles) {
+    p.cells = run.d_rows;
+    p.cell_count = static_cast<unsigned>(run.geo.cells);
+  }
+  return p;
+}
+Rt3DTileParams CandidateTiles(const Rt3DBoundsSearch& run) {
+  Rt3DTileParams t = run.tiles;
+  if (!run.mode.use_tiles) return t;
+  SpanOf(run.S->trans, run.base.inv_resolution, &t);
+  t.chunks = run.tiles.chunks + run.max_chunks;                 // the candidate pass's own list
+  t.num_chunks = run.d_segment_counts + kCandidateChunks;
+  t.rotations_per_block = 1;
+  t.boxes = run.d_list_boxes;                                   // (computed before the group pass)
+  t.tile_capacity = run.mode.cand_tile_capacity;
+  t.block_items = run.mode.block_items;
+  return t;
+}
+// (dynamic LDS of a tiled candidate launch, opted in)
+size_t CandidateLds(const Rt3DBoundsSearch& run) {
+  const size_t lds = sizeof(v2f) * (3 * kTileChunkCandidates / 2 + 2) * run.mode.list_rotations +
+                     run.mode.cand_tile_capacity + 32;
+  OptInLds(reinterpret_cast<const void*>(Rt3DTileKernel<false, true>), run.ws->device, lds);
+  return lds;
+}
+
+// ---- the stages -------------------------------------------------------------------------------
+
+// The work blocks of the list just compacted: what the next launch is sized by.
+int ReadBackNumBlocks(Rt3DBoundsSearch* run) {
+  Workspace& ws = *run->ws;
+  CMX_HIP(hipMemcpyAsync(&run->h_read->num_blocks, &run->d_counters->num_blocks, sizeof(int),
+                         hipMemcpyDeviceToHost, ws.stream));
+  CMX_HIP(hipStreamSynchronize(ws.stream));
+  return run->h_read->num_blocks;
+}
+
+int ReadBackInt(Workspace& ws, const int* d_value) {
+  int value = -1;
+  CMX_HIP(hipMemcpyAsync(&value, d_value, sizeof(int), hipMemcpyDeviceToHost, ws.stream));
+  CMX_HIP(hipStreamSynchronize(ws.stream));
+  return value;
+}
+
+// Launch shape of a tiled pass over whole rotations (the dense group pass, the rotation blocks).
+struct Rt3DGroupLaunch {
+  int threads, blocks, slices;
+  size_t lds;
+};
+Rt3DGroupLaunch GroupLaunch(const Rt3DBoundsSearch& run, long long rotations) {
+  const int rot_per_block = run.mode.rot_per_block;
+  Rt3DGroupLaunch l;
+  l.threads = std::min(1024, DivUp(rot_per_block * run.S->G, 64) * 64);
+  l.lds = (sizeof(v2f) * (3 * kTileChunkGroups / 2 + 2) + sizeof(uint32_t) * kTileChunkGroups) *
+              rot_per_block + run.mode.group_tile_capacity + 32;
+  l.blocks = DivUp(rotations, rot_per_block);
+  l.slices = std::max(1, std::min(run.max_chunks, DivUp(8 * run.cus, l.blocks)));
+  return l;
+}
+
+// The group sums, and what the tiled group passes share: LDS opt-in and the chunk boxes of the
+// list passes (the candidate chunk list under list_rotations rotations -- the sparse pair pass
+// and the candidate passes share them).
+void PrepareTiledGroupPass(Rt3DBoundsSearch* run) {
+  Workspace& ws = *run->ws;
+  const size_t sums_bytes = sizeof(uint2) * run->RG * (run->mode.staged ? 2 : 1);
+  run->d_group_sums = reinterpret_cast<uint2*>(ws.dev[kSlotGroupSums].Reserve(sums_bytes));
+  CMX_HIP(hipMemsetAsync(run->d_group_sums, 0, sums_bytes, ws.stream));
+  OptInLds(reinterpret_cast<const void*>(Rt3DTileKernel<true, false>), ws.device,
+           GroupLaunch(*run, run->S->R).lds);
+  if (!run->mode.use_boxes) return;
+  run->d_list_boxes = ws.dev[kSlotListBoxes].ReserveAs<float>(
+      static_cast<size_t>(run->num_lists) * run->max_chunks * 6);
+  Rt3DChunkBoxKernel<<<dim3(run->num_lists, 8), 256, 0, ws.stream>>>(
+      GroupParams(*run), run->tiles.sorted_xyz, run->tiles.chunks + run->max_chunks,
+      run->d_segment_counts + kCandidateChunks, run->mode.list_rotations, run->d_list_boxes);
+}
+
+// Tiled bounds of `rotations` rotations x every group: chunk boxes, tile kernel, sums -> bounds.
+void TiledBoundsOverRotations(Rt3DBoundsSearch* run, const Rt3DBulkParams& P, Rt3DTileParams T,
+                              long long rotations) {
+  Workspace& ws = *run->ws;
+  const Rt3DGroupLaunch l = GroupLaunch(*run, rotations);
+  if (run->mode.use_boxes) {
+    float* d_boxes = ws.dev[kSlotGroupBoxes].ReserveAs<float>(
+        static_cast<size_t>(l.blocks) * run->max_chunks * 6);
+    Rt3DChunkBoxKernel<<<dim3(l.blocks, 8), 256, 0, ws.stream>>>(
+        P, run->tiles.sorted_xyz, run->tiles.chunks, run->tiles.num_chunks,
+        run->mode.rot_per_block, d_boxes);
+    T.boxes = d_boxes;
+  }
+  Rt3DTileKernel<true, false><<<dim3(l.blocks, l.slices), l.threads, l.lds, ws.stream>>>(P, T);
+  Rt3DSumBoundsKernel<<<DivUp(rotations * run->S->G, 256), 256, 0, ws.stream>>>(P);
+}
+
+// Blocks of 2 x 2 x 2 rotations x groups: the group kernel over the centre rotations and the
+// twice-dilated brick.
+void RotationBlockPass(Rt3DBoundsSearch* run) {
+  Workspace& ws = *run->ws;
+  const Rt3DBulkGeometry& g = run->geo;
+  const int bx = static_cast<int>(g.bx), by = static_cast<int>(g.by), bz = static_cast<int>(g.bz);
+  uint8_t* d_dilated2 = ws.dev[kSlotDilatedTwice].ReserveAs<uint8_t>(g.cells);
+  DilateXKernel<<<DivUp(g.cells, 256), 256, 0, ws.stream>>>(run->d_dilated, run->d_tmp, bx, g.cells);
+  DilateYZKernel<<<DivUp(g.cells, 256), 256, 0, ws.stream>>>(run->d_tmp, d_dilated2, bx, by, bz);
+  // [sums | bounds | the best bound's bits]
+  const long long RbG = run->S->Rb * run->S->G;
+  const size_t bounds_bytes = (sizeof(uint2) + sizeof(float)) * RbG + 16;
+  char* d_block = static_cast<char*>(ws.dev[kSlotBlockBounds].Reserve(bounds_bytes));
+  run->d_block_upper = reinterpret_cast<float*>(d_block + sizeof(uint2) * RbG);
+  run->d_block_max = reinterpret_cast<unsigned*>(run->d_block_upper + RbG);
+  CMX_HIP(hipMemsetAsync(d_block, 0, bounds_bytes, ws.stream));
+  run->d_computed = ws.dev[kSlotPairs].ReserveAs<uint8_t>(2 * run->RG);
+  CMX_HIP(hipMemsetAsync(run->d_computed, 0, 2 * run->RG, ws.stream));
+  Rt3DBulkParams BS = GroupParams(*run);
+  BS.cells = d_dilated2;
+  BS.num_rotations = static_cast<int>(run->S->Rb);
+  BS.rotation = run->D->d_rot_b; BS.rotation_angle = run->D->d_angle_b;
+  BS.upper = run->d_block_upper; BS.sums = reinterpret_cast<uint2*>(d_block);
+  BS.max_upper_bits = run->d_block_max;
+  Rt3DTileParams TB = GroupTiles(*run);        // (one segment: every chunk)
+  TB.seg_bounds = nullptr; TB.seg_sums = nullptr; TB.seg_first = 0; TB.seg_last = 2;
+  TiledBoundsOverRotations(run, BS, TB, run->S->Rb);
+  run->trace->Mark("rotation blocks");
+}
+
+// One round of the sparse group pass: the pairs of the rotation blocks `factor` * the threshold
+// cannot exclude and that no earlier round has computed.
+void PairRound(Rt3DBoundsSearch* run, const unsigned* threshold_bits, float factor) {
+  Workspace& ws = *run->ws;
+  const Rt3DSearchSpace& S = *run->S;
+  const long long RG = run->RG;
+  const int G = S.G, R = static_cast<int>(S.R), list_rotations = run->mode.list_rotations;
+  uint8_t* d_pair_flags = run->d_computed + RG;
+  const size_t lds = (sizeof(v2f) * (3 * kTileChunkCandidates / 2 + 2) +
+                      sizeof(uint32_t) * kTileChunkCandidates) * list_rotations +
+                     run->mode.group_tile_capacity + 32;
+  OptInLds(reinterpret_cast<const void*>(Rt3DTileKernel<true, true>), ws.device, lds);
+  CMX_HIP(hipMemsetAsync(&run->d_counters->num_blocks, 0, sizeof(int), ws.stream));
+  Rt3DSelectPairsKernel<<<DivUp(RG, 256), 256, 0, ws.stream>>>(
+      run->d_block_upper, G, R, S.side_r, S.Ab, threshold_bits, factor, run->d_computed,
+      d_pair_flags);
+  Rt3DCompactKernel<<<run->num_lists, 256, 0, ws.stream>>>(
+      d_pair_flags, G, R, list_rotations, run->d_counts, run->d_items,
+      &run->d_counters->pair_total, run->d_blocks, &run->d_counters->num_blocks, kPairItems);
+  CMX_HIP(hipMemcpyAsync(&run->h_read->num_blocks, &run->d_counters->num_blocks, sizeof(int),
+                         hipMemcpyDeviceToHost, ws.stream));
+  CMX_HIP(hipMemcpyAsync(run->h_read->segments, run->d_segment_counts,
+                         sizeof(int) * kNumSegmentCounts, hipMemcpyDeviceToHost, ws.stream));
+  CMX_HIP(hipStreamSynchronize(ws.stream));
+  const int nbq = run->h_read->num_blocks;
+  const int list_chunks = run->h_read->segments[kCandidateChunks];
+  if (nbq > 0 && list_chunks > 0) {
+    const int slices = std::max(1, std::min(list_chunks, DivUp(8 * run->cus, nbq)));
+    Rt3DTileKernel<true, true><<<dim3(nbq, slices), kPairItems, lds, ws.stream>>>(
+        PairParams(*run), PairTiles(*run));
+  }
+  Rt3DSumBoundsMaskedKernel<<<DivUp(RG, 256), 256, 0, ws.stream>>>(GroupParams(*run),
+                                                                   run->d_computed);
+  if (run->mode.verify)
+    Rt3DVerifyBlocksKernel<<<DivUp(RG, 256), 256, 0, ws.stream>>>(
+        run->d_block_upper, run->d_group_upper, run->d_computed, G, R, S.side_r, S.Ab,
+        &run->d_counters->violations);
+}
+
+// rt3d_report: what the tile kernels of the group level counted.
+void ReportGroupTiles(Rt3DBoundsSearch* run) {
+  Workspace& ws = *run->ws;
+  const Rt3DGroupLaunch l = GroupLaunch(*run, run->S->R);
+  unsigned long long* d_stats = run->tiles.stats;
+  unsigned long long h[4];
+  int chunks_made = 0;
+  CMX_HIP(hipMemcpyAsync(h, d_stats, sizeof(h), hipMemcpyDeviceToHost, ws.stream));
+  CMX_HIP(hipMemcpyAsync(&chunks_made, run->tiles.num_chunks, sizeof(int), hipMemcpyDeviceToHost,
+                         ws.stream));
+  CMX_HIP(hipMemsetAsync(d_stats, 0, 64, ws.stream));
+  CMX_HIP(hipStreamSynchronize(ws.stream));
+  const double units = static_cast<double>(h[0] + h[1]);
+  fprintf(stderr,
+          "[cmx] rt3d tiles (groups): %d chunks, %d rotations x %d lanes per block, %d "
+          "slices; %.0f (block, chunk) units: %.1f %% in LDS, mean tile %.1f KB, mean "
+          "chunk %.1f points\n",
+          chunks_made, run->mode.rot_per_block, l.threads, l.slices, units,
+          100. * h[0] / std::max(units, 1.), h[2] / std::max(units, 1.) / 1024.,
+          h[3] / std::max(units, 1.));
+}
+
+// The group pass on the memory gathers.  Flat (rotation, group) lanes: as many whole wavefronts
+// per block as fit G + 1 lanes.
+void GatherGroupPass(Rt3DBoundsSearch* run, const Rt3DBulkParams& P) {
+  const int G = run->S->G;
+  const long long R = run->S->R;
+  const int flat_threads = std::min(kBulk3DThreads, (G + 1) / 64 * 64);
+  if (flat_threads >= 128 && R >= 2)
+    Rt3DBulkKernel<true><<<DivUp(run->RG, flat_threads), flat_threads, 0, run->stream()>>>(
+        P, run->D->d_xyz);
+  else
+    Rt3DBulkKernel<true><<<dim3(DivUp(G, kBulk3DThreads), std::max<unsigned>(2u, R)),
+                           kBulk3DThreads, 0, run->stream()>>>(P, run->D->d_xyz);
+}
+
+// rt3d_crosscheck: the gather kernel's group bounds next to the tiled ones, compared bitwise.
+void CrossCheckGroupPass(Rt3DBoundsSearch* run) {
+  Workspace& ws = *run->ws;
+  const long long RG = run->RG;
+  Rt3DBulkParams B2 = GroupParams(*run);
+  float* d_upper2 = ws.dev[kSlotCrosscheck].ReserveAs<float>(RG + 4);
+  B2.upper = d_upper2;
+  B2.max_upper_bits = reinterpret_cast<unsigned*>(d_upper2 + RG);
+  int* d_mismatch = reinterpret_cast<int*>(d_upper2 + RG + 1);
+  CMX_HIP(hipMemsetAsync(d_upper2 + RG, 0, 16, ws.stream));
+  GatherGroupPass(run, B2);
+  Rt3DCompareFloatsKernel<<<DivUp(RG, 256), 256, 0, ws.stream>>>(run->d_group_upper, d_upper2, RG,
+                                                                 d_mismatch);
+  const int mismatches = ReadBackInt(ws, d_mismatch);
+  CMX_REQUIRE(mismatches == 0,
+              "internal error: %d of %lld tiled group bounds differ from the gather kernel's",
+              mismatches, RG);
+}
+
+// The group level between ev_k0 and ev_k1: upper bounds of (rotation, group) pairs.
+void GroupLevel(Rt3DBoundsSearch* run) {
+  if (!run->mode.use_tiles) {
+    GatherGroupPass(run, GroupParams(*run));
+    return;
+  }
+  PrepareTiledGroupPass(run);
+  if (run->mode.rotblocks) {
+    RotationBlockPass(run);
+    // first round: the pairs of the blocks next to the best block bound
+    PairRound(run, run->d_block_max, run->mode.first_pair_factor);
+  } else {
+    TiledBoundsOverRotations(run, GroupParams(*run), GroupTiles(*run), run->S->R);
+  }
+  if (run->tiles.stats) ReportGroupTiles(run);
+  if (run->mode.crosscheck) CrossCheckGroupPass(run);
+}
+
+// Flags the members of the groups `round`'s threshold cannot exclude and compacts them into
+// work lists; returns the number of work blocks.  The launch is sized by what survived: one
+// sync per round (tens of microseconds) instead of hundreds of thousands of blocks that find
+// nothing to do.
+int SelectCandidates(Rt3DBoundsSearch* run, int round) {
+  Workspace& ws = *run->ws;
+  const Rt3DSearchSpace& S = *run->S;
+  const int R = static_cast<int>(S.R), T = static_cast<int>(S.T);
+  Rt3DSelectGroupsKernel<<<DivUp(run->RG, 256), 256, 0, ws.stream>>>(
+      run->d_group_upper, S.G, R, S.side_t, S.gpa,
+      round == 0 ? &run->d_head->max_upper : &run->d_head->max_lower,
+      round == 0 ? run->mode.first_round_factor : 1.f, run->d_expanded, run->d_flags, T);
+  Rt3DCompactKernel<<<run->num_lists, 256, 0, ws.stream>>>(
+      run->d_flags, T, R, run->mode.list_rotations, run->d_counts, run->d_items,
+      &run->d_head->total, run->d_blocks, &run->d_counters->num_blocks, run->mode.block_items);
+  CMX_HIP(hipMemcpyAsync(&run->h_read->num_blocks, &run->d_counters->num_blocks, sizeof(int),
+                         hipMemcpyDeviceToHost, ws.stream));
+  if (run->mode.staged && round == 0)
+    CMX_HIP(hipMemcpyAsync(run->h_read->segments, run->d_segment_counts,
+                           sizeof(int) * kNumSegmentCounts, hipMemcpyDeviceToHost, ws.stream));
+  CMX_HIP(hipStreamSynchronize(ws.stream));
+  return run->round_blocks[round] = run->h_read->num_blocks;
+}
+
+// rt3d_crosscheck: the same work lists on the gather kernel, into a second (Q, A) array.
+void CrossCheckCandidateRound(Rt3DBoundsSearch* run, const Rt3DBulkParams& BC, int round, int nb) {
+  Workspace& ws = *run->ws;
+  const long long num_candidates = run->S->num_candidates;
+  const size_t bytes = sizeof(uint2) * static_cast<size_t>(num_candidates) + 16;
+  Rt3DBulkParams B2 = BC;
+  uint2* d_sums2 = reinterpret_cast<uint2*>(ws.dev[kSlotCrosscheck].Reserve(bytes));
+  int* d_mismatch = reinterpret_cast<int*>(d_sums2 + num_candidates);
+  B2.sums = d_sums2;
+  B2.cells = run->d_tiled;
+  B2.cell_count = static_cast<unsigned>(run->geo.tiled_cells);
+  if (round == 0) CMX_HIP(hipMemsetAsync(d_sums2, 0, bytes, ws.stream));
+  B2.slice_points = DivUp(run->S->n, kBulk3DChunk) * kBulk3DChunk;
+  Rt3DBulkKernel<false><<<dim3(nb, 1, 1), run->mode.block_items, 0, ws.stream>>>(B2, run->D->d_xyz);
+  Rt3DCompareSumsKernel<<<DivUp(num_candidates, 256), 256, 0, ws.stream>>>(
+      BC.sums, d_sums2, num_candidates, d_mismatch);
+  const int mismatches = ReadBackInt(ws, d_mismatch);
+  CMX_REQUIRE(mismatches == 0,
+              "internal error: %d tiled candidate sums differ from the gather kernel's",
+              mismatches);
+}
+
+// One candidate round in one piece: the (Q, A) sums of `nb` work blocks, then their bounds.
+void CandidateRound(Rt3DBoundsSearch* run, int round, int nb) {
+  Workspace& ws = *run->ws;
+  const int n = run->S->n, block_items = run->mode.block_items;
+  Rt3DBulkParams BC = CandidateParams(*run);
+  if (run->mode.use_tiles) {
+    const size_t lds = CandidateLds(*run);
+    const int slices = std::max(1, std::min(run->max_chunks, DivUp(8 * run->cus, nb)));
+    Rt3DTileKernel<false, true><<<dim3(nb, slices), block_items, lds, ws.stream>>>(
+        BC, CandidateTiles(*run));
+    if (run->mode.crosscheck) CrossCheckCandidateRound(run, BC, round, nb);
+  } else {
+    // Points are split over blockIdx.z until the launch is ~32 blocks per CU.
+    // (blocks of two wavefronts: sixteen fit a CU)
+    const int want = std::max(1, DivUp(32 * run->cus, nb));
+    BC.slice_points = std::max(1, DivUp(DivUp(n, want), kBulk3DChunk)) * kBulk3DChunk;
+    const dim3 cand_grid(nb, 1, DivUp(n, BC.slice_points));
+    Rt3DBulkKernel<false><<<cand_grid, kCand3DThreads, 0, ws.stream>>>(BC, run->D->d_xyz);
+  }
+  Rt3DBoundsKernel<<<nb, block_items, 0, ws.stream>>>(BC);
+  if (run->mode.verify)
+    Rt3DVerifyKernel<<<nb, block_items, 0, ws.stream>>>(
+        BC, run->d_group_upper, run->S->G, run->S->side_t, run->S->gpa,
+        &run->d_counters->violations);
+  run->trace->Mark(round == 0 ? "candidate pass 1" : "candidate pass 2");
+}
+
+// The second candidate round segment by segment; after the first and the second, the
+// candidates whose bound (own sum so far + the group's sum over the rest) has fallen below the
+// best lower bound leave the work lists.  Verification mode keeps the lists and records the
+// decisions instead (Rt3DStageCheckKernel).
+void StagedSecondRound(Rt3DBoundsSearch* run, int nb) {
+  Workspace& ws = *run->ws;
+  const Rt3DSearchSpace& S = *run->S;
+  const bool verify = run->mode.verify;
+  const int block_items = run->mode.block_items;
+  const int R = static_cast<int>(S.R), T = static_cast<int>(S.T);
+  const Rt3DBulkParams BC = CandidateParams(*run);
+  const Rt3DTileParams TC = CandidateTiles(*run);
+  const size_t lds = CandidateLds(*run);
+  unsigned long long* d_stage_ub = nullptr;
+  uint8_t* d_dropped = nullptr;
+  if (verify) {
+    d_stage_ub = ws.dev[kSlotStageBounds].ReserveAs<unsigned long long>(
+        static_cast<size_t>(S.num_candidates));
+    d_dropped = ws.dev[kSlotStageDropped].ReserveAs<uint8_t>(static_cast<size_t>(S.num_candidates));
+  }
+  const int* seg = run->h_read->segments;
+  const int seg_chunks[3] = {seg[kCandidateSegments],
+                             seg[kCandidateSegments + 1] - seg[kCandidateSegments],
+                             seg[kCandidateChunks] - seg[kCandidateSegments + 1]};
+  int live = nb;
+  for (int stage = 0; stage < 3 && live > 0; ++stage) {
+    Rt3DTileParams TS = TC;
+    TS.seg_bounds = run->d_segment_counts + kCandidateSegments;
+    TS.seg_first = TS.seg_last = stage;
+    if (seg_chunks[stage] > 0) {
+      const int slices = std::max(1, std::min(seg_chunks[stage], DivUp(8 * run->cus, live)));
+      Rt3DTileKernel<false, true><<<dim3(live, slices), block_items, lds, ws.stream>>>(BC, TS);
+    }
+    if (stage == 2) break;
+    Rt3DStageFilterKernel<<<live, block_items, 0, ws.stream>>>(
+        BC, run->d_group_sums, run->d_group_sums + run->RG, S.G, S.side_t, S.gpa, stage,
+        run->d_flags, d_stage_ub, d_dropped);
+    if (verify) continue;
+    CMX_HIP(hipMemsetAsync(&run->d_counters->num_blocks, 0, sizeof(int), ws.stream));
+    Rt3DCompactKernel<<<run->num_lists, 256, 0, ws.stream>>>(
+        run->d_flags, T, R, run->mode.list_rotations, run->d_counts, run->d_items,
+        &run->d_counters->stage_total, run->d_blocks, &run->d_counters->num_blocks, block_items);
+    live = ReadBackNumBlocks(run);
+    run->stage_blocks[stage] = live;
+  }
+  if (live > 0) {
+    Rt3DBoundsKernel<<<live, block_items, 0, ws.stream>>>(BC);
+    if (verify) {
+      Rt3DStageCheckKernel<<<live, block_items, 0, ws.stream>>>(BC, d_stage_ub, d_dropped,
+                                                                &run->d_counters->violations);
+      Rt3DVerifyKernel<<<live, block_items, 0, ws.stream>>>(
+          BC, run->d_group_upper, S.G, S.side_t, S.gpa, &run->d_counters->violations);
+    }
+  }
+  run->trace->Mark("candidate pass 2 (staged)");
+}
+
+// Everything within 1e-5 of the best lower bound, scored exactly; false: a flat score landscape
+// (more finalists than the list holds) -- every candidate on the per-candidate kernel then.
+bool CollectFinalists(Rt3DBoundsSearch* run, Rt3DFinalists* out) {
+  Workspace& ws = *run->ws;
+  const Rt3DSearchSpace& S = *run->S;
+  Rt3DBulkHead* d_head = run->d_head;
+  Rt3DBulkCollectKernel<<<DivUp(S.num_candidates, 256), 256, 0, ws.stream>>>(
+      run->d_upper, S.num_candidates, &d_head->max_lower, &d_head->count, d_head->finalists,
+      kBulkFinalistCap);
+  Rt3DExactKernel<<<kBulkFinalistCap, 256, 0, ws.stream>>>(
+      run->D->P, run->D->d_xyz, S.n, d_head->finalists, &d_head->count, kBulkFinalistCap,
+      d_head->exact);
+  run->trace->Mark("finalists");
+  CMX_HIP(hipGetLastError());
+  RecordEvent(ws.ev_end, ws.stream);
+  CMX_HIP(hipMemcpyAsync(run->h_head, d_head, sizeof(Rt3DBulkHead), hipMemcpyDeviceToHost,
+                         ws.stream));
+  CMX_HIP(hipMemcpyAsync(&run->h_read->pair_total, &run->d_counters->pair_total, sizeof(int),
+                         hipMemcpyDeviceToHost, ws.stream));
+  CMX_HIP(hipStreamSynchronize(ws.stream));
+  run->trace->Report();
+  const Rt3DBulkHead& head = *run->h_head;
+  if (run->mode.verify) {
+    int violations = 0;
+    CMX_HIP(hipMemcpy(&violations, &run->d_counters->violations, sizeof(int),
+                      hipMemcpyDeviceToHost));
+    CMX_REQUIRE(violations == 0,
+                "internal error: %d bound violations (a group bound below a member's lower "
+                "bound, or a staged bound below the candidate's final sum)", violations);
+  }
+  // rotation blocks: their bounds + the pairs that went through the group pass
+  const long long group_bounds =
+      run->mode.rotblocks ? S.Rb * S.G + run->h_read->pair_total : run->RG;
+  if (run->mode.report) {
+    float lo_f, up_f;
+    std::memcpy(&lo_f, &head.max_lower, 4);
+    std::memcpy(&up_f, &head.max_upper, 4);
+    fprintf(stderr,
+            "[cmx] rt3d: group pass %.3f ms (%lld bounds), %d of %lld candidates scored, "
+            "%d finalists, best lower %.6f, best group upper %.6f, work blocks %d + %d "
+            "(staged: %d after a quarter of the points, %d after half), device %.3f ms\n",
+            ElapsedMs(ws.ev_k0, ws.ev_k1), group_bounds, head.total, S.num_candidates, head.count,
+            lo_f, up_f, run->round_blocks[0], run->round_blocks[1], run->stage_blocks[0],
+            run->stage_blocks[1], ElapsedMs(ws.ev_begin, ws.ev_end));
+  }
+  if (head.count < 1 || head.count > kBulkFinalistCap) return false;
+  std::vector<std::pair<long long, float>> pairs(head.count);
+  for (int i = 0; i < head.count; ++i) {
+    const long long r = head.finalists[i] / S.T, t = head.finalists[i] % S.T;
+    pairs[i] = {t * S.R + r, head.exact[i]};
+  }
+  std::sort(pairs.begin(), pairs.end());
+  out->index.resize(head.count);
+  out->acc.resize(head.count);
+  for (int i = 0; i < head.count; ++i) {
+    out->index[i] = pairs[i].first;
+    out->acc[i] = pairs[i].second;
+  }
+  out->num_finalists = head.count;
+  out->group_bounds = group_bounds;
+  out->bounds_evaluated = group_bounds + head.total;
+  return true;
+}
+
+// The bounds search; false when it did not narrow the search down (see CollectFinalists).
+bool RunBoundsSearch(Workspace& ws, const Rt3DSearchSpace& S, const Rt3DMode& mode,
+                     const Rt3DBulkGeometry& geo, const Rt3DDevice& D, const Rt3DGridSource& grid,
+                     Rt3DFinalists* out) {
+  Rt3DBoundsSearch run;
+  run.ws = &ws; run.S = &S; run.D = &D; run.mode = mode; run.geo = geo;
+  run.RG = S.R * S.G;
+  run.num_lists = DivUp(S.R, mode.list_rotations);
+  BuildBulkBricks(&run, grid);
+  ReserveBoundsBuffers(&run);
+  run.base = BaseBulkParams(run);
+  run.trace.emplace(ws.stream);
+  run.trace->Mark("bricks");
+  (void)hipDeviceGetAttribute(&run.cus, hipDeviceAttributeMultiprocessorCount, ws.device);
+  if (mode.use_tiles) SortCloudIntoBins(&run);
+  RecordEvent(ws.ev_k0, ws.stream);
+  GroupLevel(&run);
+  RecordEvent(ws.ev_k1, ws.stream);
+  // Candidate pass, twice: the members of the groups next to the best upper bound yield a
+  // lower bound; then everything that lower bound cannot exclude.  (The threshold only
+  // rises afterwards, so no third round can add a group.)
+  CMX_HIP(hipMemsetAsync(run.d_tmp, 0, sizeof(uint2) * static_cast<size_t>(S.num_candidates),
+                         ws.stream));
+  run.trace->Mark("group pass");
+  for (int round = 0; round < 2; ++round) {
+    CMX_HIP(hipMemsetAsync(&run.d_counters->num_blocks, 0, sizeof(int), ws.stream));
+    if (round == 1 && mode.rotblocks) {
+      // the pairs of every rotation block the lower bound of round 0 cannot exclude
+      RecordEvent(ws.ev_x0, ws.stream);
+      PairRound(&run, &run.d_head->max_lower, 1.f);
+      RecordEvent(ws.ev_x1, ws.stream);
+      out->second_pairs_pass = true;
+      CMX_HIP(hipMemsetAsync(&run.d_counters->num_blocks, 0, sizeof(int), ws.stream));
+      run.trace->Mark("group pass 2 (pairs)");
+    }
+    const int nb = SelectCandidates(&run, round);
+    if (nb == 0) continue;
+    if (mode.staged && round == 1) {
+      StagedSecondRound(&run, nb);
+    } else {
+      CandidateRound(&run, round, nb);
+    }
+  }
+  return CollectFinalists(&run, out);
+}
+
+// Every candidate on the one-thread-per-candidate kernel; finalists = the candidates within
+// 1e-5 (relative) of the best weighted score, or all of them when the list overflows.
+void RunExhaustiveSearch(Workspace& ws, const Rt3DSearchSpace& S, const Rt3DDevice& D,
+                         Rt3DFinalists* out) {
+  const long long num_candidates = S.num_candidates;
+  Rt3DExhaustiveMisc* d_misc = D.d_misc;
+  RecordEvent(ws.ev_k0, ws.stream);
+  Rt3DScoreKernel<<<dim3(DivUp(S.T, 64), static_cast<unsigned>(S.R)), 64, 0, ws.stream>>>(
+      D.P, D.d_xyz, S.n, D.d_unweighted, D.d_weighted, &d_misc->max_bits);
+  RecordEvent(ws.ev_k1, ws.stream);
+  Rt3DCollectKernel<<<DivUp(num_candidates, 256), 256, 0, ws.stream>>>(
+      D.d_weighted, num_candidates, &d_misc->max_bits, &d_misc->count, d_misc->finalists,
+      kFinalistCap);
+  CMX_HIP(hipGetLastError());
+  RecordEvent(ws.ev_end, ws.stream);
+  const Rt3DExhaustiveMisc& h_misc = D.pinned->exhaustive;
+  CMX_HIP(hipMemcpyAsync(&D.pinned->exhaustive, d_misc, sizeof(Rt3DExhaustiveMisc),
+                         hipMemcpyDeviceToHost, ws.stream));
+  CMX_HIP(hipStreamSynchronize(ws.stream));
+  const int count = h_misc.count;
+  if (count <= kFinalistCap) {
+    out->index.assign(h_misc.finalists, h_misc.finalists + count);
+    std::sort(out->index.begin(), out->index.end());
+    out->acc.resize(count);
+    for (int i = 0; i < count; ++i)
+      CMX_HIP(hipMemcpy(&out->acc[i], D.d_unweighted + out->index[i], sizeof(float),
+                        hipMemcpyDeviceToHost));
+  } else {
+    out->index.resize(num_candidates);
+    for (long long c = 0; c < num_candidates; ++c) out->index[c] = c;
+    out->acc.resize(num_candidates);
+    CMX_HIP(hipMemcpy(out->acc.data(), D.d_unweighted, sizeof(float) * num_candidates,
+                      hipMemcpyDeviceToHost));
+  }
+}
+
+// Exact weighting and the strict '>' running maximum of :44-50.
+void PickBest(const Rt3DSearchSpace& S, const Rt3DParams& P, const Rt3DFinalists& fin,
+              float* score, cmx_pose3d* pose_estimate) {
+  CMX_REQUIRE(!fin.index.empty(), "internal error: no candidate collected");
+  float best_score = -1.f;
+  long long best = -1;
+  for (size_t i = 0; i < fin.index.size(); ++i) {
+    const long long c = fin.index[i];
+    const long long t = c / S.R, r = c % S.R;
+    float sc = fin.acc[i];
+    const double penalty = static_cast<double>(S.trans[t].w) * P.wt +
+                           static_cast<double>(S.angle[r]) * P.wr;
+    sc *= std::exp(-(penalty * (penalty * 1.)));
+    if (sc > best_score) { best_score = sc; best = c; }
+  }
+  const long long t = best / S.R, r = best % S.R;
+  h3::Rigid candidate;
+  candidate.t = {S.trans[t].x, S.trans[t].y, S.trans[t].z};
+  candidate.q = {S.rot[r].w, S.rot[r].x, S.rot[r].y, S.rot[r].z};
+  *pose_estimate = h3::ToPose(candidate);
+  *score = best_score;
+}
+
+// Bounds search: the search space is covered by bounds -- the group bounds plus the candidates
+// scored one by one; `candidates_scored` stays the size of the search space (what the
+// reference scores), `coarse_candidates` says how many bounds that took.
+cmx_match_stats StatsOf(Workspace& ws, const Rt3DSearchSpace& S, const Rt3DFinalists& fin) {
+  cmx_match_stats st{};
+  st.candidates_scored = S.num_candidates;
+  st.coarse_candidates = fin.bounds_evaluated ? fin.bounds_evaluated : S.num_candidates;
+  st.num_scans = static_cast<int>(S.R);
+  st.nodes_expanded = fin.num_finalists;
+  st.device_ms = ElapsedMs(ws.ev_begin, ws.ev_end);
+  st.dominant_kernel_ms = ElapsedMs(ws.ev_k0, ws.ev_k1);
+  // the bounds above the candidates (rotation blocks, then the (rotation, group) pairs they
+  // leave): how many, their lookups, and the time of ALL their passes
+  st.expansion_nodes = fin.group_bounds;
+  st.expansion_lookups = fin.group_bounds * S.n;
+  st.expansion_ms = st.dominant_kernel_ms;
+  if (fin.second_pairs_pass) st.expansion_ms += ElapsedMs(ws.ev_x0, ws.ev_x1);
+  return st;
+}
+
+// RealTimeCorrelativeScanMatcher3D::Match: the bounds search where its limits hold (ModeOf) and
+// it narrows the search down, else the exhaustive search; the reference's weighting and
+// first-maximum rule over what either leaves.
+void Rt3DMatch(const cmx_rt_options* options, float grid_resolution, const cmx_voxel* voxels,
+               int64_t num_voxels, const Brick* resident, const cmx_pose3d* initial_pose_estimate,
+               const float* point_cloud_xyz, int32_t num_points, int32_t device, float* score,
+               cmx_pose3d* pose_estimate, cmx_match_stats* stats) {
+  CMX_REQUIRE(options && initial_pose_estimate && point_cloud_xyz, "null argument");
+  CMX_REQUIRE(pose_estimate != nullptr && score != nullptr,
+              "pose_estimate must not be null");                       // CHECK at :39
+  CMX_REQUIRE(resident != nullptr || num_voxels == 0 || voxels != nullptr, "voxels is null");
+  CMX_REQUIRE(num_points >= 1 && num_points <= (1 << 24), "bad point count");
+  CMX_REQUIRE(grid_resolution > 0.f, "resolution must be > 0");
+  const Rt3DSearchSpace S = BuildSearchSpace(*options, grid_resolution, *initial_pose_estimate,
+                                             point_cloud_xyz, num_points);
+  WorkspaceLease ws(device);
+  const Rt3DGridSource grid{voxels, num_voxels, resident};
+  const PaddedBrick box = GridBox(grid);
+  const Rt3DBulkGeometry geo = BulkGeometry(box, S.L);
+  const Rt3DMode mode = ModeOf(S, geo, *options, point_cloud_xyz);
+  Rt3DDevice D;
+  BuildProbabilityBrick(*ws, box, grid, &D);
+  UploadTables(*ws, S, *options, point_cloud_xyz, &D);
+
+  Rt3DFinalists finalists;
+  RecordEvent(ws->ev_begin, ws->stream);
+  const bool done = mode.use_bulk && RunBoundsSearch(*ws, S, mode, geo, D, grid, &finalists);
+  if (!done) RunExhaustiveSearch(*ws, S, D, &finalists);
+  PickBest(S, D.P, finalists, score, pose_estimate);
+  if (stats) *stats = StatsOf(*ws, S, finalists);
+}
+
 cmx_status Rt3DMatchImpl(const cmx_rt_options* options, float grid_resolution,
                          const cmx_voxel* voxels, int64_t num_voxels, const Brick* resident,
                          const cmx_pose3d* initial_pose_estimate, const float* point_cloud_xyz,
                          int32_t num_points, int32_t device, float* score,
                          cmx_pose3d* pose_estimate, cmx_match_stats* stats) {
   return Guard([&] {
-    CMX_REQUIRE(options && initial_pose_estimate && point_cloud_xyz, "null argument");
-    CMX_REQUIRE(pose_estimate != nullptr && score != nullptr,
-                "pose_estimate must not be null");                       // CHECK at :39
-    CMX_REQUIRE(resident != nullptr || num_voxels == 0 || voxels != nullptr, "voxels is null");
-    CMX_REQUIRE(num_points >= 1 && num_points <= (1 << 24), "bad point count");
-    CMX_REQUIRE(grid_resolution > 0.f, "resolution must be > 0");
-    const int n = num_points;
-    const float resolution = grid_resolution;
-
-    // GenerateExhaustiveSearchTransforms (:55-95), host side.
-    const int L = static_cast<int>(std::lround(options->linear_search_window / resolution));
-    float max_scan_range = 3.f * resolution;
-    for (int i = 0; i < n; ++i) {
-      const h3::V3 p{point_cloud_xyz[3 * i], point_cloud_xyz[3 * i + 1],
-                     point_cloud_xyz[3 * i + 2]};
-      max_scan_range = std::max(h3::Norm(p), max_scan_range);
-    }
-    const float kSafetyMargin = 1.f - 1e-3f;
-    const float step =
-        kSafetyMargin * std::acos(1.f - (resolution * (resolution * 1.f)) /
-                                            (2.f * (max_scan_range * (max_scan_range * 1.f))));
-    const int A = static_cast<int>(std::lround(options->angular_search_window / step));
-    CMX_REQUIRE(L >= 0 && L < 512 && A >= 0 && A < 64, "unsupported search window");
-    const int side_t = 2 * L + 1, side_r = 2 * A + 1;
-    const long long T = 1ll * side_t * side_t * side_t, R = 1ll * side_r * side_r * side_r;
-    const long long num_candidates = T * R;
-    CMX_REQUIRE(num_candidates < (1ll << 31), "search window too large");
-
-    const h3::Rigid init = h3::FromPose(*initial_pose_estimate);
-    std::vector<float4> rot(R), trans(T);
-    std::vector<float> angle(R);
-    std::vector<h3::Q> rot_q(R);
-    {
-      long long k = 0;
-      for (int rz = -A; rz <= A; ++rz)
-        for (int ry = -A; ry <= A; ++ry)
-          for (int rx = -A; rx <= A; ++rx, ++k) {
-            h3::Rigid tf;
-            tf.q = h3::FromAngleAxisVector({rx * step, ry * step, rz * step});
-            rot_q[k] = tf.q;
-            angle[k] = h3::GetAngle(tf);
-            const h3::Q q = h3::Normalized(h3::Mul(init.q, tf.q));
-            rot[k] = make_float4(q.x, q.y, q.z, q.w);
-          }
-      k = 0;
-      for (int z = -L; z <= L; ++z)
-        for (int y = -L; y <= L; ++y)
-          for (int x = -L; x <= L; ++x, ++k) {
-            const h3::V3 tc{x * resolution, y * resolution, z * resolution};
-            const h3::V3 r = h3::Rotate(init.q, tc);
-            trans[k] = make_float4(r.x + init.t.x, r.y + init.t.y, r.z + init.t.z, h3::Norm(tc));
-          }
-    }
-
-    // Rotation blocks (2 x 2 x 2 of the angle-axis lattice, see Rt3DSelectPairsKernel): the
-    // centre rotation and the smallest member angle of each.
-    const int Ab = (side_r + 1) / 2;
-    const long long Rb = 1ll * Ab * Ab * Ab;
-    std::vector<float4> rot_b(Rb);
-    std::vector<float> angle_b(Rb);
-    {
-      long long k = 0;
-      for (int bz = 0; bz < Ab; ++bz)
-        for (int by = 0; by < Ab; ++by)
-          for (int bx = 0; bx < Ab; ++bx, ++k) {
-            const int nx = std::min(2, side_r - 2 * bx), ny = std::min(2, side_r - 2 * by),
-                      nz = std::min(2, side_r - 2 * bz);
-            h3::Rigid tf;
-            tf.q = h3::FromAngleAxisVector({(2 * bx + 0.5f * (nx - 1) - A) * step,
-                                            (2 * by + 0.5f * (ny - 1) - A) * step,
-                                            (2 * bz + 0.5f * (nz - 1) - A) * step});
-            const h3::Q q = h3::Normalized(h3::Mul(init.q, tf.q));
-            rot_b[k] = make_float4(q.x, q.y, q.z, q.w);
-            float smallest = INFINITY;
-            for (int c = 0; c < nz; ++c)
-              for (int b = 0; b < ny; ++b)
-                for (int a = 0; a < nx; ++a)
-                  smallest = std::min(smallest, angle[((2 * bz + c) * side_r + (2 * by + b)) * side_r + (2 * bx + a)]);
-            angle_b[k] = smallest;
-          }
-    }
-
-    WorkspaceLease ws(device);
-    // Padded f32 probability brick over the voxels' bounding box.
-    PaddedBrick brick{};
-    {
-      int lo[3], hi[3];
-      if (resident != nullptr) {             // the brick's own box (cells never written hold 0)
-        lo[0] = resident->lo_x; lo[1] = resident->lo_y; lo[2] = resident->lo_z;
-        hi[0] = lo[0] + resident->nx - 1; hi[1] = lo[1] + resident->ny - 1;
-        hi[2] = lo[2] + resident->nz - 1;
-      } else if (!VoxelBounds(voxels, num_voxels, lo, hi)) {
-        lo[0] = lo[1] = lo[2] = 0;
-        hi[0] = hi[1] = hi[2] = 0;
-      }
-      for (int k = 0; k < 3; ++k)
-        CMX_REQUIRE(lo[k] > -(1 << 20) && hi[k] < (1 << 20), "voxel index out of range");
-      brick.lo_x = lo[0]; brick.lo_y = lo[1]; brick.lo_z = lo[2];
-      brick.nx = hi[0] - lo[0] + 1; brick.ny = hi[1] - lo[1] + 1; brick.nz = hi[2] - lo[2] + 1;
-      const size_t cells = static_cast<size_t>(brick.nx + 2) * (brick.ny + 2) * (brick.nz + 2);
-      CMX_REQUIRE(cells < (size_t(1) << 29), "dense grid of %d x %d x %d cells is too large",
-                  brick.nx, brick.ny, brick.nz);
-      float* d_cells = ws->dev[7].ReserveAs<float>(cells);
-      brick.cells = d_cells;
-      FillFloatKernel<<<DivUp(cells, 256), 256, 0, ws->stream>>>(d_cells, cells, 0.1f);
-      if (resident != nullptr) {
-        const long long count = static_cast<long long>(resident->nx) * resident->ny * resident->nz;
-        BrickProbabilitiesKernel<<<DivUp(count, 256), 256, 0, ws->stream>>>(
-            static_cast<const uint16_t*>(resident->cells), count, resident->nx, resident->ny, brick,
-            d_cells);
-      } else if (num_voxels > 0) {
-        cmx_voxel* d_vox = ws->dev[15].ReserveAs<cmx_voxel>(num_voxels);
-        CMX_HIP(hipMemcpyAsync(d_vox, voxels, num_voxels * sizeof(cmx_voxel),
-                               hipMemcpyHostToDevice, ws->stream));
-        ScatterProbabilitiesKernel<<<DivUp(num_voxels, 256), 256, 0, ws->stream>>>(
-            d_vox, num_voxels, brick, d_cells);
-      }
-      CMX_HIP(hipGetLastError());
-    }
-
-    float* d_xyz = ws->dev[0].ReserveAs<float>(3 * static_cast<size_t>(n));
-    float4* d_rot = ws->dev[1].ReserveAs<float4>(R);
-    float4* d_trans = ws->dev[2].ReserveAs<float4>(T);
-    float* d_angle = ws->dev[3].ReserveAs<float>(R);
-    float* d_unweighted = ws->dev[4].ReserveAs<float>(num_candidates);
-    float* d_weighted = ws->dev[5].ReserveAs<float>(num_candidates);
-    const int kFinalistCap = 4096;
-    int num_finalists = 0;
-    char* d_misc = static_cast<char*>(ws->dev[6].Reserve(16 + sizeof(long long) * kFinalistCap));
-    unsigned* d_max = reinterpret_cast<unsigned*>(d_misc);
-    int* d_count = reinterpret_cast<int*>(d_misc + 4);
-    long long* d_finalists = reinterpret_cast<long long*>(d_misc + 16);
-    char* h_misc = static_cast<char*>(ws->pinned[1].Reserve(16 + sizeof(long long) * kFinalistCap));
-
-    CMX_HIP(hipMemcpyAsync(d_xyz, point_cloud_xyz, 3 * sizeof(float) * n, hipMemcpyHostToDevice,
-                           ws->stream));
-    CMX_HIP(hipMemcpyAsync(d_rot, rot.data(), R * sizeof(float4), hipMemcpyHostToDevice,
-                           ws->stream));
-    CMX_HIP(hipMemcpyAsync(d_trans, trans.data(), T * sizeof(float4), hipMemcpyHostToDevice,
-                           ws->stream));
-    CMX_HIP(hipMemcpyAsync(d_angle, angle.data(), R * sizeof(float), hipMemcpyHostToDevice,
-                           ws->stream));
-    float4* d_rot_b = ws->dev[24].ReserveAs<float4>(Rb);
-    float* d_angle_b = ws->dev[25].ReserveAs<float>(Rb);
-    CMX_HIP(hipMemcpyAsync(d_rot_b, rot_b.data(), Rb * sizeof(float4), hipMemcpyHostToDevice,
-                           ws->stream));
-    CMX_HIP(hipMemcpyAsync(d_angle_b, angle_b.data(), Rb * sizeof(float), hipMemcpyHostToDevice,
-                           ws->stream));
-    CMX_HIP(hipMemsetAsync(d_misc, 0, 16, ws->stream));
-    // pageable sources above: make sure the copies are done before they go away
-    CMX_HIP(hipStreamSynchronize(ws->stream));
-
-    Rt3DParams P;
-    P.grid = brick;
-    P.resolution = resolution;
-    P.inv_resolution = 1.f / resolution;
-    P.num_translations = static_cast<int>(T);
-    P.num_rotations = static_cast<int>(R);
-    P.side_t = side_t; P.side_r = side_r;
-    P.rotation = d_rot; P.translation = d_trans; P.rotation_angle = d_angle;
-    P.wt = options->translation_delta_cost_weight;
-    P.wr = options->rotation_delta_cost_weight;
-
-    std::vector<long long> finalists;     // reference candidate index t * R + r, ascending
-    std::vector<float> acc;               // their exact unweighted scores
-    bool done = false;
-    RecordEvent(ws->ev_begin, ws->stream);
-
-    // ---- integer bounds (groups, then candidates) + exact finalists --------------------
-    // Limits: finite points (a NaN would read an unchecked cell), N small enough for the
-    // rounding bound of the f32 chain to mean something, index arithmetic exact in f32,
-    // weights that decrease with distance (a group is weighted by its nearest member).
-    const int reach = static_cast<int>(std::ceil(L * 1.7320508075688772)) + 1;   // |init.q * t_c|
-    const int pad = 2 * reach + 2;
-    // (rows a multiple of 4 cells: the tiled passes copy boxes of the brick with aligned dwords)
-    const long long bx = (brick.nx + 2ll * pad + 3) & ~3ll, by = brick.ny + 2ll * pad,
-                    bz = brick.nz + 2ll * pad;
-    bool use_bulk = Bulk3DEnabled() && n <= (1 << 21) && R <= 65535 &&
-                    bx * by * bz < (1ll << 24) &&
-                    options->translation_delta_cost_weight >= 0. &&
-                    options->rotation_delta_cost_weight >= 0.;
-    for (int i = 0; i < 3 * n && use_bulk; ++i) use_bulk = std::isfinite(point_cloud_xyz[i]);
-    long long bounds_evaluated = 0;
-    long long group_bounds = 0;          // bounds above the candidates: rotation blocks + (rotation, group) pairs
-    bool second_pairs_pass = false;      // (its span: ev_x0 .. ev_x1)
-    if (use_bulk) {
-      const size_t cells = static_cast<size_t>(bx * by * bz);
-      const int tiles_x = DivUp(bx, 8), tiles_y = DivUp(by, 4);
-      const int pitch_z = DivUp(bz, 4) * 4;
-      const size_t tiled_cells = static_cast<size_t>(tiles_x) * tiles_y * pitch_z * 32;
-      // [row-major q (only the input of the dilation) | tiled q]
-      uint8_t* d_bulk = ws->dev[8].ReserveAs<uint8_t>(cells + 128 + tiled_cells);
-      uint8_t* d_tiled = d_bulk + (cells + 127) / 128 * 128;
-      uint8_t* d_dilated = ws->dev[9].ReserveAs<uint8_t>(cells);
-      // (dilation scratch first, then the (Q, A) pairs of the candidate pass)
-      uint8_t* d_tmp = ws->dev[10].ReserveAs<uint8_t>(
-          std::max<size_t>(cells, sizeof(uint2) * static_cast<size_t>(num_candidates)));
-      CMX_HIP(hipMemsetAsync(d_bulk, 0, (d_tiled - d_bulk) + tiled_cells, ws->stream));
-      if (resident != nullptr) {
-        const long long count = static_cast<long long>(resident->nx) * resident->ny * resident->nz;
-        BrickBulkKernel<<<DivUp(count, 256), 256, 0, ws->stream>>>(
-            static_cast<const uint16_t*>(resident->cells), count, resident->nx, resident->ny, pad,
-            static_cast<int>(bx), static_cast<int>(by), tiles_y, pitch_z, d_bulk, d_tiled);
-      } else if (num_voxels > 0) {
-        const cmx_voxel* d_vox = static_cast<const cmx_voxel*>(ws->dev[15].get());
-        ScatterBulkKernel<<<DivUp(num_voxels, 256), 256, 0, ws->stream>>>(
-            d_vox, num_voxels, brick.lo_x, brick.lo_y, brick.lo_z, pad, static_cast<int>(bx),
-            static_cast<int>(by), tiles_y, pitch_z, d_bulk, d_tiled);
-      }
-      DilateXKernel<<<DivUp(cells, 256), 256, 0, ws->stream>>>(d_bulk, d_tmp,
-                                                               static_cast<int>(bx), cells);
-      DilateYZKernel<<<DivUp(cells, 256), 256, 0, ws->stream>>>(
-          d_tmp, d_dilated, static_cast<int>(bx), static_cast<int>(by), static_cast<int>(bz));
-
-      // 2 x 2 x 2 blocks of lattice steps: centre translation + the smallest member distance.
-      const int gpa = (side_t + 1) / 2;
-      const int G = gpa * gpa * gpa;
-      std::vector<float4> group(G);
-      for (int gz = 0, g = 0; gz < gpa; ++gz)
-        for (int gy = 0; gy < gpa; ++gy)
-          for (int gx = 0; gx < gpa; ++gx, ++g) {
-            const int nx = std::min(2, side_t - 2 * gx), ny = std::min(2, side_t - 2 * gy),
-                      nz = std::min(2, side_t - 2 * gz);
-            const h3::V3 tc{(2 * gx + 0.5f * (nx - 1) - L) * resolution,
-                            (2 * gy + 0.5f * (ny - 1) - L) * resolution,
-                            (2 * gz + 0.5f * (nz - 1) - L) * resolution};
-            const h3::V3 rc = h3::Rotate(init.q, tc);
-            float nearest = INFINITY;
-            for (int c = 0; c < nz; ++c)
-              for (int b = 0; b < ny; ++b)
-                for (int a = 0; a < nx; ++a)
-                  nearest = std::min(
-                      nearest,
-                      trans[((2 * gz + c) * side_t + (2 * gy + b)) * side_t + (2 * gx + a)].w);
-            group[g] = make_float4(rc.x + init.t.x, rc.y + init.t.y, rc.z + init.t.z, nearest);
-          }
-
-      const int kBulkFinalistCap = 4096;
-      const long long RG = R * G;
-      float4* d_group = ws->dev[14].ReserveAs<float4>(G);
-      float* d_group_upper = ws->dev[11].ReserveAs<float>(RG);
-      uint8_t* d_expanded = ws->dev[12].ReserveAs<uint8_t>(RG + num_candidates);
-      uint8_t* d_flags = d_expanded + RG;                             // [R][T]
-      float* d_upper = d_weighted;                                   // [R][T], reused
-      int* d_items = reinterpret_cast<int*>(d_unweighted);           // [R][T], reused
-      const size_t head_bytes = 16 + (sizeof(int) + sizeof(float)) * kBulkFinalistCap;   // 16 | 32768
-      // work descriptors of a round: at most one per 256 translations and rotation, + count
-      const int max_blocks = static_cast<int>(R) * DivUp(T, kCand3DThreads);   // (>= any block size used)
-      const size_t counts_bytes = (sizeof(int) * R + 15) / 16 * 16;
-      char* d_bmisc = static_cast<char*>(ws->dev[13].Reserve(
-          head_bytes + counts_bytes + sizeof(int2) * (max_blocks + 2)));
-      unsigned* d_max_lower = reinterpret_cast<unsigned*>(d_bmisc);
-      int* d_bcount = reinterpret_cast<int*>(d_bmisc + 4);
-      unsigned* d_max_upper = reinterpret_cast<unsigned*>(d_bmisc + 8);
-      int* d_total = reinterpret_cast<int*>(d_bmisc + 12);
-      int* d_bfinalists = reinterpret_cast<int*>(d_bmisc + 16);
-      float* d_exact = reinterpret_cast<float*>(d_bmisc + 16 + sizeof(int) * kBulkFinalistCap);
-      int* d_counts = reinterpret_cast<int*>(d_bmisc + head_bytes);
-      int2* d_blocks = reinterpret_cast<int2*>(d_bmisc + head_bytes + counts_bytes);
-      int* d_num_blocks = reinterpret_cast<int*>(d_blocks + max_blocks);
-      int* d_violations = d_num_blocks + 1;          // (the second word of that int2 slot)
-      int* d_stage_scratch = d_num_blocks + 2;       // item total of the staged re-compactions (unused)
-      const bool verify = Debug().rt3d_verify != 0;
-      int* h_num_blocks = ws->pinned[1].ReserveAs<int>(16);
-      char* h_bmisc = static_cast<char*>(ws->pinned[2].Reserve(head_bytes));
-      float4* h_group = ws->pinned[3].ReserveAs<float4>(G);
-      std::memcpy(h_group, group.data(), sizeof(float4) * G);
-      CMX_HIP(hipMemcpyAsync(d_group, h_group, sizeof(float4) * G, hipMemcpyHostToDevice,
-                             ws->stream));
-      CMX_HIP(hipMemsetAsync(d_bmisc, 0, 16, ws->stream));
-      CMX_HIP(hipMemsetAsync(d_num_blocks, 0, sizeof(int) * 4, ws->stream));   // blocks, violations, totals
-      CMX_HIP(hipMemsetAsync(d_counts, 0, sizeof(int) * R, ws->stream));
-      CMX_HIP(hipMemsetAsync(d_expanded, 0, RG + num_candidates, ws->stream));
-      CMX_HIP(hipMemsetAsync(d_upper, 0, sizeof(float) * num_candidates, ws->stream));
-
-      Rt3DBulkParams B{};
-      B.cell_count = static_cast<unsigned>(cells);
-      B.pitch_x = static_cast<float>(bx); B.pitch_y = static_cast<float>(by);
-      B.off_x = static_cast<float>(pad - brick.lo_x);
-      B.off_y = static_cast<float>(pad - brick.lo_y);
-      B.off_z = static_cast<float>(pad - brick.lo_z);
-      B.inv_resolution = 1.f / resolution;
-      double q_abs = 0.;
-      const int los[3] = {brick.lo_x, brick.lo_y, brick.lo_z};
-      const int dims[3] = {brick.nx, brick.ny, brick.nz};
-      for (int k = 0; k < 3; ++k)
-        q_abs = std::max<double>(q_abs, std::max(std::abs(los[k] - pad),
-                                                 std::abs(los[k] + dims[k] - 1 + pad)));
-      const double q_pad = static_cast<double>(std::max(bx, std::max(by, bz)));
-      // |q - (qe + off)| <= (2 |c / res| + |q|) 2^-24 (rounded 1/res, one fma rounding, the
-      // reference's rounded quotient qe); 25 % on top.
-      const double e = (2. * q_abs + q_pad + 4.) * 0x1p-24 * 1.25;
-      B.guard = std::nextafter(static_cast<float>(0.5 - e), 0.f);
-      B.t0x = init.t.x; B.t0y = init.t.y; B.t0z = init.t.z;
-      B.lo_x = (brick.lo_x - reach - 1) * resolution;
-      B.hi_x = (brick.lo_x + brick.nx + reach) * resolution;
-      B.lo_y = (brick.lo_y - reach - 1) * resolution;
-      B.hi_y = (brick.lo_y + brick.ny + reach) * resolution;
-      B.lo_z = (brick.lo_z - reach - 1) * resolution;
-      B.hi_z = (brick.lo_z + brick.nz + reach) * resolution;
-      B.num_rotations = static_cast<int>(R);
-      B.n = n;
-      B.rotation = d_rot; B.rotation_angle = d_angle;
-      B.wt = options->translation_delta_cost_weight;
-      B.wr = options->rotation_delta_cost_weight;
-      const float kMinP = 0.1f, kMaxP = 1.f - kMinP;
-      const float scale = (kMaxP - kMinP) / (32768 - 2.f);
-      B.min_probability = kMinP;
-      B.scale_over_n = 128. * static_cast<double>(scale) / n;
-      B.slack_hi = 127. * static_cast<double>(scale) + 2e-7;
-      const double ku = (n + 8.) * 0x1p-24;
-      B.delta = ku / (1. - ku) * 1.01 + 2e-6;
-      B.max_lower_bits = d_max_lower; B.max_upper_bits = d_max_upper;
-
-      // Group pass: every rotation, every block of translations, on the dilated brick.
-      Rt3DBulkParams BG = B;
-      BG.cells = d_dilated;
-      BG.translation = d_group; BG.num_translations = G;
-      BG.upper = d_group_upper;
-      StageTrace trace(ws->stream);
-      trace.Mark("bricks");
-      int cus = 256;
-      (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device);
-      // Tiled passes: the cloud sorted into bins of kTileBin^3 cells at the central candidate.
-      // Rotations of a group-pass workgroup: as many as fit 512 lanes, so that TWO workgroups
-      // share a CU and one computes while the other stages its next chunk (C4, 216 groups: two
-      // rotations = 448 lanes, group pass 5.51 -> 4.91 ms against four rotations in one 896-lane
-      // workgroup per CU; debug switch rt3d_group_rotations overrides, experiments).
-      const int rot_per_block = std::max(
-          1, std::min({kTileMaxRotations, std::max(1, 512 / std::max(G, 1)),
-                       Override(Debug().rt3d_group_rotations, kTileMaxRotations)}));
-      const bool use_tiles = Tiles3DEnabled() && G <= 1024;
-      const bool crosscheck = use_tiles && Debug().rt3d_crosscheck != 0;
-      // (boxes of the rotated chunks from a pre-pass kernel instead of a reduction per chunk
-      // inside the tile kernel; debug switch rt3d_no_boxes for the A/B)
-      const bool use_boxes = Debug().rt3d_no_boxes == 0;
-      Rt3DTileParams TG{};
-      int max_chunks = 0;
-      int* d_segment_counts = nullptr;
-      // Staged second candidate round (see Rt3DStageFilterKernel); CMX_RT3D_STAGED=0 for the A/B.
-      // The cross-check compares complete sums and the expand-all mode has no second round.
-      const bool staged = use_tiles && !crosscheck && Debug().rt3d_unstaged == 0 &&
-                          Debug().rt3d_expand_all == 0;
-      // The rotation-block level above the group pass (Rt3DSelectPairsKernel): needs a window of
-      // more than one rotation per axis, small enough for the 1.03 of its bound, and the lists of
-      // the tiled passes.
-      const bool rotblocks = use_tiles && !crosscheck && Debug().rt3d_no_rotblocks == 0 && A >= 1 &&
-                             (A + 1) * static_cast<double>(step) * 1.7320508 <= 0.2;
-      // (work lists of the tiled list passes: several rotations each, so that a tile serves some
-      // hundred lanes even when a rotation keeps only a few dozen entries)
-      const int list_rotations =
-          use_tiles && !crosscheck ? std::max(1, std::min(8, Override(Debug().rt3d_cand_rotations, 8))) : 1;
-      const int num_lists = DivUp(R, list_rotations);
-      uint8_t* d_computed = nullptr;       // rotblocks: [R][G] pair computed | [R][G] pair flagged
-      float* d_block_upper = nullptr;      // rotblocks: [Rb][G]
-      unsigned* d_block_max = nullptr;
-      float* d_list_boxes = nullptr;       // chunk boxes of the candidate chunk list, per work list
-      std::function<void(const unsigned*, float)> run_pairs;   // one round of the sparse group pass
-      if (use_tiles) {
-        Rt3DBinParams BP{};
-        BP.rotation = rot[R / 2];
-        BP.translation = trans[T / 2];
-        BP.inv_resolution = B.inv_resolution;
-        BP.off_x = B.off_x; BP.off_y = B.off_y; BP.off_z = B.off_z;
-        BP.t0x = B.t0x; BP.t0y = B.t0y; BP.t0z = B.t0z;
-        BP.lo_x = B.lo_x; BP.hi_x = B.hi_x; BP.lo_y = B.lo_y; BP.hi_y = B.hi_y;
-        BP.lo_z = B.lo_z; BP.hi_z = B.hi_z;
-        BP.bins_x = DivUp(bx, kTileBin); BP.bins_y = DivUp(by, kTileBin);
-        BP.bins_z = DivUp(bz, kTileBin);
-        BP.n = n;
-        const int num_bins = BP.bins_x * BP.bins_y * BP.bins_z;
-        max_chunks = n / kTileChunkCandidates + num_bins + 1;      // (either list)
-        float* d_sorted = ws->dev[16].ReserveAs<float>(3 * static_cast<size_t>(n));
-        char* d_bins = static_cast<char*>(ws->dev[17].Reserve(
-            sizeof(int) * (num_bins + 8) + 2 * sizeof(int2) * static_cast<size_t>(max_chunks)));
-        int* d_bin_count = reinterpret_cast<int*>(d_bins);
-        // [0] group list, [1] candidate list, [2..3] / [4..5] their segment boundaries
-        int* d_chunk_count = d_bin_count + num_bins;
-        int2* d_chunks = reinterpret_cast<int2*>(d_bin_count + num_bins + 8);
-        int2* d_chunks_candidates = d_chunks + max_chunks;
-        CMX_HIP(hipMemsetAsync(d_bin_count, 0, sizeof(int) * (num_bins + 8), ws->stream));
-        Rt3DBinCountKernel<<<DivUp(n, 256), 256, 0, ws->stream>>>(BP, d_xyz, d_bin_count);
-        // (segment windows: sixteen or more periods over a large cloud, never shorter than four
-        // group-pass pieces)
-        const int segment_window = n >= 32768 ? 4096 : 2048;
-        // (debug switch rt3d_segments = a | b << 8: the first segment ends at a / 16, the second
-        // at b / 16 of a window; default a quarter and a half.  Experiments.)
-        int sixteenths0 = 4, sixteenths1 = 8;
-        if (const int seg = Debug().rt3d_segments; seg > 0) {
-          sixteenths0 = std::max(1, std::min(15, seg & 0xff));
-          sixteenths1 = std::max(sixteenths0, std::min(15, (seg >> 8) & 0xff));
-        }
-        Rt3DBinScanKernel<<<1, 1024, 0, ws->stream>>>(
-            d_bin_count, num_bins, d_chunks, d_chunks_candidates, d_chunk_count, segment_window,
-            segment_window / 16 * sixteenths0, segment_window / 16 * sixteenths1);
-        d_segment_counts = d_chunk_count;
-        Rt3DBinScatterKernel<<<DivUp(n, 256), 256, 0, ws->stream>>>(BP, d_xyz, d_bin_count,
-                                                                    d_sorted);
-        CMX_HIP(hipGetLastError());
-        if (Debug().rt3d_report) {
-          TG.stats = reinterpret_cast<unsigned long long*>(ws->dev[19].Reserve(64));
-          CMX_HIP(hipMemsetAsync(TG.stats, 0, 64, ws->stream));
-        }
-        TG.sorted_xyz = d_sorted;
-        TG.chunks = d_chunks;
-        TG.num_chunks = d_chunk_count;
-        TG.pitch_x = static_cast<int>(bx); TG.pitch_y = static_cast<int>(by);
-        TG.pitch_z = static_cast<int>(bz);
-        trace.Mark("bins");
-      }
-      // Span of a translation table in cells (what widens a chunk's box into its tile).
-      const auto span_of = [&](const std::vector<float4>& table, Rt3DTileParams* tp) {
-        for (int a = 0; a < 3; ++a) { tp->tr_lo[a] = INFINITY; tp->tr_hi[a] = -INFINITY; }
-        for (const float4& v : table) {
-          const float c[3] = {v.x * B.inv_resolution, v.y * B.inv_resolution,
-                              v.z * B.inv_resolution};
-          for (int a = 0; a < 3; ++a) {
-            tp->tr_lo[a] = std::min(tp->tr_lo[a], c[a]);
-            tp->tr_hi[a] = std::max(tp->tr_hi[a], c[a]);
-          }
-        }
-      };
-      RecordEvent(ws->ev_k0, ws->stream);
-      if (use_tiles) {
-        Rt3DTileParams TP = TG;
-        span_of(group, &TP);
-        TP.rotations_per_block = rot_per_block;
-        TP.tile_capacity = Override(Debug().rt3d_group_tile_kb, 44) * 1024;
-        const int threads = std::min(1024, DivUp(rot_per_block * G, 64) * 64);
-        TP.fixed_point = Debug().rt3d_group_float ? 0 : 1;
-        if (crosscheck) TP.fixed_point = 0;       // (the float path reproduces the gather kernel's sums)
-        const size_t lds = (sizeof(v2f) * (3 * kTileChunkGroups / 2 + 2) +
-                            sizeof(uint32_t) * kTileChunkGroups) * rot_per_block +
-                           TP.tile_capacity + 32;
-        const int blocks = DivUp(R, rot_per_block);
-        const int slices = std::max(1, std::min(max_chunks, DivUp(8 * cus, blocks)));
-        BG.cell_count = static_cast<unsigned>(cells);
-        BG.sums = reinterpret_cast<uint2*>(ws->dev[18].Reserve(sizeof(uint2) * RG * (staged ? 2 : 1)));
-        CMX_HIP(hipMemsetAsync(BG.sums, 0, sizeof(uint2) * RG * (staged ? 2 : 1), ws->stream));
-        if (staged) {
-          TP.seg_bounds = d_segment_counts + 2;
-          TP.seg_first = 0; TP.seg_last = 2;
-          TP.seg_sums = BG.sums + RG;
-        }
-        OptInLds(reinterpret_cast<const void*>(Rt3DTileKernel<true, false>), ws->device, lds);
-        if (use_boxes) {
-          // (the chunk boxes of the list passes: the candidate chunk list under list_rotations
-          // rotations -- the sparse group pass and the candidate passes share them)
-          d_list_boxes = ws->dev[21].ReserveAs<float>(static_cast<size_t>(num_lists) * max_chunks * 6);
-          Rt3DChunkBoxKernel<<<dim3(num_lists, 8), 256, 0, ws->stream>>>(
-              BG, TG.sorted_xyz, TG.chunks + max_chunks, TG.num_chunks + 1, list_rotations, d_list_boxes);
-        }
-        if (rotblocks) {
-          // ---- blocks of 2 x 2 x 2 rotations x groups: the same kernel over the centre rotations
-          // and the twice-dilated brick --------------------------------------------------------
-          uint8_t* d_dilated2 = ws->dev[26].ReserveAs<uint8_t>(cells);
-          DilateXKernel<<<DivUp(cells, 256), 256, 0, ws->stream>>>(d_dilated, d_tmp,
-                                                                   static_cast<int>(bx), cells);
-          DilateYZKernel<<<DivUp(cells, 256), 256, 0, ws->stream>>>(
-              d_tmp, d_dilated2, static_cast<int>(bx), static_cast<int>(by), static_cast<int>(bz));
-          const long long RbG = Rb * G;
-          char* d_block = static_cast<char*>(ws->dev[27].Reserve((sizeof(uint2) + sizeof(float)) * RbG + 16));
-          uint2* d_block_sums = reinterpret_cast<uint2*>(d_block);
-          d_block_upper = reinterpret_cast<float*>(d_block + sizeof(uint2) * RbG);
-          d_block_max = reinterpret_cast<unsigned*>(d_block + (sizeof(uint2) + sizeof(float)) * RbG);
-          CMX_HIP(hipMemsetAsync(d_block, 0, (sizeof(uint2) + sizeof(float)) * RbG + 16, ws->stream));
-          d_computed = ws->dev[28].ReserveAs<uint8_t>(2 * RG);
-          CMX_HIP(hipMemsetAsync(d_computed, 0, 2 * RG, ws->stream));
-          Rt3DBulkParams BS = BG;
-          BS.cells = d_dilated2;
-          BS.num_rotations = static_cast<int>(Rb);
-          BS.rotation = d_rot_b; BS.rotation_angle = d_angle_b;
-          BS.upper = d_block_upper; BS.sums = d_block_sums; BS.max_upper_bits = d_block_max;
-          Rt3DTileParams TB = TP;
-          TB.seg_bounds = nullptr; TB.seg_sums = nullptr; TB.seg_first = 0; TB.seg_last = 2;
-          const int blocks_b = DivUp(Rb, rot_per_block);
-          const int slices_b = std::max(1, std::min(max_chunks, DivUp(8 * cus, blocks_b)));
-          if (use_boxes) {
-            float* d_boxes = ws->dev[20].ReserveAs<float>(static_cast<size_t>(blocks_b) * max_chunks * 6);
-            Rt3DChunkBoxKernel<<<dim3(blocks_b, 8), 256, 0, ws->stream>>>(
-                BS, TG.sorted_xyz, TG.chunks, TG.num_chunks, rot_per_block, d_boxes);
-            TB.boxes = d_boxes;
-          }
-          Rt3DTileKernel<true, false><<<dim3(blocks_b, slices_b), threads, lds, ws->stream>>>(BS, TB);
-          Rt3DSumBoundsKernel<<<DivUp(RbG, 256), 256, 0, ws->stream>>>(BS);
-          trace.Mark("rotation blocks");
-          // ---- the group pass proper over the pairs a threshold cannot exclude -----------------
-          const int pair_items = 512;
-          Rt3DBulkParams BQ = BG;                // (sums, upper, group table, once-dilated brick)
-          BQ.counts = d_counts; BQ.items = d_items; BQ.blocks = d_blocks;
-          BQ.list_rotations = list_rotations; BQ.block_items = pair_items;
-          Rt3DTileParams TQ = TP;
-          TQ.chunks = TG.chunks + max_chunks;    // the candidate pass's chunk list (256 points)
-          TQ.num_chunks = TG.num_chunks + 1;
-          TQ.block_items = pair_items;
-          TQ.boxes = d_list_boxes;
-          if (staged) TQ.seg_bounds = d_segment_counts + 4;      // (seg_first .. seg_last, seg_sums: TP's)
-          const size_t lds_q = (sizeof(v2f) * (3 * kTileChunkCandidates / 2 + 2) +
-                                sizeof(uint32_t) * kTileChunkCandidates) * list_rotations +
-                               TQ.tile_capacity + 32;
-          OptInLds(reinterpret_cast<const void*>(Rt3DTileKernel<true, true>), ws->device, lds_q);
-          int* d_pair_total = d_num_blocks + 3;
-          uint8_t* d_pair_flags = d_computed + RG;
-          const bool check_blocks = verify;
-          run_pairs = [=, &ws](const unsigned* threshold_bits, float factor) {
-            CMX_HIP(hipMemsetAsync(d_num_blocks, 0, sizeof(int), ws->stream));
-            Rt3DSelectPairsKernel<<<DivUp(RG, 256), 256, 0, ws->stream>>>(
-                d_block_upper, G, static_cast<int>(R), side_r, Ab, threshold_bits, factor, d_computed,
-                d_pair_flags);
-            Rt3DCompactKernel<<<num_lists, 256, 0, ws->stream>>>(
-                d_pair_flags, G, static_cast<int>(R), list_rotations, d_counts, d_items, d_pair_total,
-                d_blocks, d_num_blocks, pair_items);
-            CMX_HIP(hipMemcpyAsync(h_num_blocks, d_num_blocks, sizeof(int), hipMemcpyDeviceToHost,
-                                   ws->stream));
-            CMX_HIP(hipMemcpyAsync(h_num_blocks + 4, d_segment_counts, sizeof(int) * 8,
-                                   hipMemcpyDeviceToHost, ws->stream));
-            CMX_HIP(hipStreamSynchronize(ws->stream));
-            const int nbq = *h_num_blocks;
-            const int list_chunks = h_num_blocks[4 + 1];         // chunks of the candidate list
-            if (nbq > 0 && list_chunks > 0) {
-              const int slices_q = std::max(1, std::min(list_chunks, DivUp(8 * cus, nbq)));
-              Rt3DTileKernel<true, true><<<dim3(nbq, slices_q), pair_items, lds_q, ws->stream>>>(BQ, TQ);
-            }
-            Rt3DSumBoundsMaskedKernel<<<DivUp(RG, 256), 256, 0, ws->stream>>>(BG, d_computed);
-            if (check_blocks)
-              Rt3DVerifyBlocksKernel<<<DivUp(RG, 256), 256, 0, ws->stream>>>(
-                  d_block_upper, d_group_upper, d_computed, G, static_cast<int>(R), side_r, Ab,
-                  d_violations);
-          };
-          // first round: the pairs of the blocks next to the best block bound (all of them when
-          // every group is to be expanded: rt3d_expand_all)
-          const int permille = Debug().rt3d_rotblock_permille;
-          run_pairs(d_block_max, Debug().rt3d_expand_all ? 0.f : permille > 0 ? std::min(permille, 1000) * 1e-3f : 0.97f);
-        } else {
-          if (use_boxes) {
-            float* d_boxes = ws->dev[20].ReserveAs<float>(static_cast<size_t>(blocks) * max_chunks * 6);
-            Rt3DChunkBoxKernel<<<dim3(blocks, 8), 256, 0, ws->stream>>>(
-                BG, TG.sorted_xyz, TG.chunks, TG.num_chunks, rot_per_block, d_boxes);
-            TP.boxes = d_boxes;
-          }
-          Rt3DTileKernel<true, false><<<dim3(blocks, slices), threads, lds, ws->stream>>>(BG, TP);
-          Rt3DSumBoundsKernel<<<DivUp(RG, 256), 256, 0, ws->stream>>>(BG);
-        }
-        if (TG.stats) {
-          unsigned long long h[4];
-          int chunks_made = 0;
-          CMX_HIP(hipMemcpyAsync(h, TG.stats, sizeof(h), hipMemcpyDeviceToHost, ws->stream));
-          CMX_HIP(hipMemcpyAsync(&chunks_made, TG.num_chunks, sizeof(int), hipMemcpyDeviceToHost,
-                                 ws->stream));
-          CMX_HIP(hipMemsetAsync(TG.stats, 0, 64, ws->stream));
-          CMX_HIP(hipStreamSynchronize(ws->stream));
-          const double units = static_cast<double>(h[0] + h[1]);
-          fprintf(stderr,
-                  "[cmx] rt3d tiles (groups): %d chunks, %d rotations x %d lanes per block, %d "
-                  "slices; %.0f (block, chunk) units: %.1f %% in LDS, mean tile %.1f KB, mean "
-                  "chunk %.1f points\n",
-                  chunks_made, rot_per_block, threads, slices, units, 100. * h[0] / std::max(units, 1.),
-                  h[2] / std::max(units, 1.) / 1024., h[3] / std::max(units, 1.));
-        }
-        if (crosscheck) {
-          Rt3DBulkParams B2 = BG;
-          float* d_upper2 = ws->dev[19].ReserveAs<float>(RG + 4);
-          B2.upper = d_upper2;
-          B2.max_upper_bits = reinterpret_cast<unsigned*>(d_upper2 + RG);
-          int* d_mismatch = reinterpret_cast<int*>(d_upper2 + RG + 1);
-          CMX_HIP(hipMemsetAsync(d_upper2 + RG, 0, 16, ws->stream));
-          const int flat_threads = std::min(kBulk3DThreads, (G + 1) / 64 * 64);
-          if (flat_threads >= 128 && R >= 2)
-            Rt3DBulkKernel<true><<<DivUp(RG, flat_threads), flat_threads, 0, ws->stream>>>(B2, d_xyz);
-          else
-            Rt3DBulkKernel<true><<<dim3(DivUp(G, kBulk3DThreads), std::max<unsigned>(2u, R)),
-                                   kBulk3DThreads, 0, ws->stream>>>(B2, d_xyz);
-          Rt3DCompareFloatsKernel<<<DivUp(RG, 256), 256, 0, ws->stream>>>(d_group_upper, d_upper2,
-                                                                         RG, d_mismatch);
-          int mismatches = -1;
-          CMX_HIP(hipMemcpyAsync(&mismatches, d_mismatch, sizeof(int), hipMemcpyDeviceToHost,
-                                 ws->stream));
-          CMX_HIP(hipStreamSynchronize(ws->stream));
-          CMX_REQUIRE(mismatches == 0,
-                      "internal error: %d of %lld tiled group bounds differ from the gather kernel's",
-                      mismatches, RG);
-        }
-      } else {
-      // Flat (rotation, group) lanes: as many whole wavefronts per block as fit G + 1 lanes.
-      const int flat_threads = std::min(kBulk3DThreads, (G + 1) / 64 * 64);
-      if (flat_threads >= 128 && R >= 2)
-        Rt3DBulkKernel<true><<<DivUp(RG, flat_threads), flat_threads, 0, ws->stream>>>(BG, d_xyz);
-      else
-        Rt3DBulkKernel<true><<<dim3(DivUp(G, kBulk3DThreads), std::max<unsigned>(2u, R)),
-                               kBulk3DThreads, 0, ws->stream>>>(BG, d_xyz);
-      }
-      RecordEvent(ws->ev_k1, ws->stream);
-      // Candidate pass, twice: the members of the groups next to the best upper bound yield a
-      // lower bound; then everything that lower bound cannot exclude.  (The threshold only
-      // rises afterwards, so no third round can add a group.)
-      Rt3DBulkParams BC = B;
-      BC.cells = d_tiled;
-      BC.cell_count = static_cast<unsigned>(tiled_cells);
-      BC.tiles_y = tiles_y; BC.pitch_z = pitch_z;
-      BC.translation = d_trans; BC.num_translations = static_cast<int>(T);
-      BC.counts = d_counts; BC.items = d_items; BC.blocks = d_blocks;
-      BC.upper = d_upper;
-      BC.sums = reinterpret_cast<uint2*>(d_tmp);
-      CMX_HIP(hipMemsetAsync(d_tmp, 0, sizeof(uint2) * static_cast<size_t>(num_candidates),
-                             ws->stream));
-      trace.Mark("group pass");
-      Rt3DTileParams TC = TG;
-      const int block_items =
-          !use_tiles ? kCand3DThreads : crosscheck ? 256 : Override(Debug().rt3d_cand_threads, 512);
-      BC.block_items = block_items;
-      BC.list_rotations = list_rotations;
-      if (use_tiles) {
-        span_of(trans, &TC);
-        TC.chunks = TG.chunks + max_chunks;                        // the candidate pass's own list
-        TC.num_chunks = TG.num_chunks + 1;
-        TC.rotations_per_block = 1;
-        TC.boxes = d_list_boxes;                        // (computed before the group pass)
-        TC.tile_capacity = Override(Debug().rt3d_cand_tile_kb, 48) * 1024;
-        TC.block_items = block_items;
-        BC.cells = d_bulk;                              // the row-major q brick
-        BC.cell_count = static_cast<unsigned>(cells);
-      }
-      int round_blocks[2] = {0, 0};
-      int stage_blocks[2] = {-1, -1};            // work blocks left after segments 0 and 1
-      int* h_segments = h_num_blocks + 4;        // pinned: the chunk counts by segment
-      int* d_stage_total = d_stage_scratch;      // (re-compactions must not count items twice)
-      // Debug switch rt3d_expand_all (tests, with rt3d_verify): every group is expanded in the
-      // first round, so every group bound is checked against every one of its members.
-      const float first_round_factor = Debug().rt3d_expand_all ? 0.f : 0.97f;
-      for (int round = 0; round < 2; ++round) {
-        CMX_HIP(hipMemsetAsync(d_num_blocks, 0, sizeof(int), ws->stream));
-        if (round == 1 && rotblocks) {
-          // the pairs of every rotation block the lower bound of round 0 cannot exclude
-          RecordEvent(ws->ev_x0, ws->stream);
-          run_pairs(d_max_lower, 1.f);
-          RecordEvent(ws->ev_x1, ws->stream);
-          second_pairs_pass = true;
-          CMX_HIP(hipMemsetAsync(d_num_blocks, 0, sizeof(int), ws->stream));
-          trace.Mark("group pass 2 (pairs)");
-        }
-        Rt3DSelectGroupsKernel<<<DivUp(RG, 256), 256, 0, ws->stream>>>(
-            d_group_upper, G, static_cast<int>(R), side_t, gpa,
-            round == 0 ? d_max_upper : d_max_lower, round == 0 ? first_round_factor : 1.f, d_expanded,
-            d_flags, static_cast<int>(T));
-        Rt3DCompactKernel<<<num_lists, 256, 0, ws->stream>>>(
-            d_flags, static_cast<int>(T), static_cast<int>(R), list_rotations, d_counts, d_items,
-            d_total, d_blocks, d_num_blocks, block_items);
-        // The launch is sized by what survived: one sync per round (tens of microseconds)
-        // instead of hundreds of thousands of blocks that find nothing to do.
-        CMX_HIP(hipMemcpyAsync(h_num_blocks, d_num_blocks, sizeof(int), hipMemcpyDeviceToHost,
-                               ws->stream));
-        if (staged && round == 0)
-          CMX_HIP(hipMemcpyAsync(h_segments, d_segment_counts, sizeof(int) * 8,
-                                 hipMemcpyDeviceToHost, ws->stream));
-        CMX_HIP(hipStreamSynchronize(ws->stream));
-        int nb = round_blocks[round] = *h_num_blocks;
-        if (nb == 0) continue;
-        if (use_tiles) {
-          const size_t lds = sizeof(v2f) * (3 * kTileChunkCandidates / 2 + 2) * list_rotations +
-                             TC.tile_capacity + 32;
-          OptInLds(reinterpret_cast<const void*>(Rt3DTileKernel<false, true>), ws->device, lds);
-          if (staged && round == 1) {
-            // Segment by segment; after the first and the second, the candidates whose bound
-            // (own sum so far + the group's sum over the rest) has fallen below the best lower
-            // bound leave the work lists.  Verification mode keeps the lists and records the
-            // decisions instead (Rt3DStageCheckKernel).
-            unsigned long long* d_stage_ub = nullptr;
-            uint8_t* d_dropped = nullptr;
-            if (verify) {
-              d_stage_ub = reinterpret_cast<unsigned long long*>(
-                  ws->dev[22].Reserve(sizeof(unsigned long long) * static_cast<size_t>(num_candidates)));
-              d_dropped = ws->dev[23].ReserveAs<uint8_t>(static_cast<size_t>(num_candidates));
-            }
-            int live = nb;
-            for (int stage = 0; stage < 3 && live > 0; ++stage) {
-              Rt3DTileParams TS = TC;
-              TS.seg_bounds = d_segment_counts + 4;
-              TS.seg_first = TS.seg_last = stage;
-              const int seg_chunks =
-                  stage == 0 ? h_segments[4] : stage == 1 ? h_segments[5] - h_segments[4]
-                                                          : h_segments[1] - h_segments[5];
-              if (seg_chunks > 0) {
-                const int slices = std::max(1, std::min(seg_chunks, DivUp(8 * cus, live)));
-                Rt3DTileKernel<false, true><<<dim3(live, slices), block_items, lds, ws->stream>>>(BC, TS);
-              }
-              if (stage == 2) break;
-              Rt3DStageFilterKernel<<<live, block_items, 0, ws->stream>>>(
-                  BC, BG.sums, BG.sums + RG, G, side_t, gpa, stage, d_flags, d_stage_ub, d_dropped);
-              if (verify) continue;
-              CMX_HIP(hipMemsetAsync(d_num_blocks, 0, sizeof(int), ws->stream));
-              Rt3DCompactKernel<<<num_lists, 256, 0, ws->stream>>>(
-                  d_flags, static_cast<int>(T), static_cast<int>(R), list_rotations, d_counts,
-                  d_items, d_stage_total, d_blocks, d_num_blocks, block_items);
-              CMX_HIP(hipMemcpyAsync(h_num_blocks, d_num_blocks, sizeof(int), hipMemcpyDeviceToHost,
-                                     ws->stream));
-              CMX_HIP(hipStreamSynchronize(ws->stream));
-              live = *h_num_blocks;
-              stage_blocks[stage] = live;
-            }
-            nb = live;
-            if (nb > 0) {
-              Rt3DBoundsKernel<<<nb, block_items, 0, ws->stream>>>(BC);
-              if (verify) {
-                Rt3DStageCheckKernel<<<nb, block_items, 0, ws->stream>>>(BC, d_stage_ub, d_dropped,
-                                                                          d_violations);
-                Rt3DVerifyKernel<<<nb, block_items, 0, ws->stream>>>(BC, d_group_upper, G, side_t,
-                                                                        gpa, d_violations);
-              }
-            }
-            trace.Mark("candidate pass 2 (staged)");
-            continue;
-          }
-          const int slices = std::max(1, std::min(max_chunks, DivUp(8 * cus, nb)));
-          Rt3DTileKernel<false, true><<<dim3(nb, slices), block_items, lds, ws->stream>>>(BC, TC);
-          if (crosscheck) {
-            // the same work lists on the gather kernel, into a second (Q, A) array
-            Rt3DBulkParams B2 = BC;
-            uint2* d_sums2 = reinterpret_cast<uint2*>(
-                ws->dev[19].Reserve(sizeof(uint2) * static_cast<size_t>(num_candidates) + 16));
-            int* d_mismatch = reinterpret_cast<int*>(d_sums2 + num_candidates);
-            B2.sums = d_sums2;
-            B2.cells = d_tiled;
-            B2.cell_count = static_cast<unsigned>(tiled_cells);
-            if (round == 0)
-              CMX_HIP(hipMemsetAsync(d_sums2, 0,
-                                     sizeof(uint2) * static_cast<size_t>(num_candidates) + 16,
-                                     ws->stream));
-            B2.slice_points = DivUp(n, kBulk3DChunk) * kBulk3DChunk;
-            Rt3DBulkKernel<false><<<dim3(nb, 1, 1), block_items, 0, ws->stream>>>(B2, d_xyz);
-            Rt3DCompareSumsKernel<<<DivUp(num_candidates, 256), 256, 0, ws->stream>>>(
-                BC.sums, d_sums2, num_candidates, d_mismatch);
-            int mismatches = -1;
-            CMX_HIP(hipMemcpyAsync(&mismatches, d_mismatch, sizeof(int), hipMemcpyDeviceToHost,
-                                   ws->stream));
-            CMX_HIP(hipStreamSynchronize(ws->stream));
-            CMX_REQUIRE(mismatches == 0,
-                        "internal error: %d tiled candidate sums differ from the gather kernel's",
-                        mismatches);
-          }
-        } else {
-        // Points are split over blockIdx.z until the launch is ~32 blocks per CU.
-        // (blocks of two wavefronts: sixteen fit a CU)
-        const int want = std::max(1, DivUp(32 * cus, nb));
-        BC.slice_points = std::max(1, DivUp(DivUp(n, want), kBulk3DChunk)) * kBulk3DChunk;
-        const dim3 cand_grid(nb, 1, DivUp(n, BC.slice_points));
-        Rt3DBulkKernel<false><<<cand_grid, kCand3DThreads, 0, ws->stream>>>(BC, d_xyz);
-        }
-        Rt3DBoundsKernel<<<nb, block_items, 0, ws->stream>>>(BC);
-        if (verify)
-          Rt3DVerifyKernel<<<nb, block_items, 0, ws->stream>>>(BC, d_group_upper, G, side_t,
-                                                                  gpa, d_violations);
-        trace.Mark(round == 0 ? "candidate pass 1" : "candidate pass 2");
-      }
-      Rt3DBulkCollectKernel<<<DivUp(num_candidates, 256), 256, 0, ws->stream>>>(
-          d_upper, num_candidates, d_max_lower, d_bcount, d_bfinalists, kBulkFinalistCap);
-      Rt3DExactKernel<<<kBulkFinalistCap, 256, 0, ws->stream>>>(P, d_xyz, n, d_bfinalists,
-                                                                d_bcount, kBulkFinalistCap,
-                                                                d_exact);
-      trace.Mark("finalists");
-      CMX_HIP(hipGetLastError());
-      RecordEvent(ws->ev_end, ws->stream);
-      CMX_HIP(hipMemcpyAsync(h_bmisc, d_bmisc, head_bytes, hipMemcpyDeviceToHost, ws->stream));
-      CMX_HIP(hipMemcpyAsync(h_num_blocks + 12, d_num_blocks + 3, sizeof(int), hipMemcpyDeviceToHost,
-                             ws->stream));          // (rotation blocks: pairs that went through the group pass)
-      CMX_HIP(hipStreamSynchronize(ws->stream));
-      trace.Report();
-      const int count = *reinterpret_cast<int*>(h_bmisc + 4);
-      const int total_items = *reinterpret_cast<int*>(h_bmisc + 12);
-      if (verify) {
-        int violations = 0;
-        CMX_HIP(hipMemcpy(&violations, d_violations, sizeof(int), hipMemcpyDeviceToHost));
-        CMX_REQUIRE(violations == 0,
-                    "internal error: %d bound violations (a group bound below a member's lower "
-                    "bound, or a staged bound below the candidate's final sum)", violations);
-      }
-      if (Debug().rt3d_report) {
-        float ms = 0.f, all = 0.f;
-        ms = ElapsedMs(ws->ev_k0, ws->ev_k1);
-        all = ElapsedMs(ws->ev_begin, ws->ev_end);
-        float lo_f, up_f;
-        std::memcpy(&lo_f, h_bmisc, 4);
-        std::memcpy(&up_f, h_bmisc + 8, 4);
-        fprintf(stderr,
-                "[cmx] rt3d: group pass %.3f ms (%lld bounds), %d of %lld candidates scored, "
-                "%d finalists, best lower %.6f, best group upper %.6f, work blocks %d + %d "
-                "(staged: %d after a quarter of the points, %d after half), device %.3f ms\n",
-                ms, rotblocks ? Rb * G + h_num_blocks[12] : RG, total_items, num_candidates, count, lo_f, up_f, round_blocks[0],
-                round_blocks[1], stage_blocks[0], stage_blocks[1], all);
-      }
-      if (count >= 1 && count <= kBulkFinalistCap) {
-        const int* fin = reinterpret_cast<const int*>(h_bmisc + 16);
-        const float* exact =
-            reinterpret_cast<const float*>(h_bmisc + 16 + sizeof(int) * kBulkFinalistCap);
-        std::vector<std::pair<long long, float>> pairs(count);
-        for (int i = 0; i < count; ++i) {
-          const long long r = fin[i] / T, t = fin[i] % T;
-          pairs[i] = {t * R + r, exact[i]};
-        }
-        std::sort(pairs.begin(), pairs.end());
-        finalists.resize(count);
-        acc.resize(count);
-        for (int i = 0; i < count; ++i) { finalists[i] = pairs[i].first; acc[i] = pairs[i].second; }
-        num_finalists = count;
-        group_bounds = rotblocks ? Rb * G + h_num_blocks[12] : RG;
-        bounds_evaluated = group_bounds + total_items;
-        done = true;
-      }
-      // else: a flat score landscape -- every candidate on the per-candidate kernel below.
-    }
-
-    if (!done) {
-    RecordEvent(ws->ev_k0, ws->stream);
-    Rt3DScoreKernel<<<dim3(DivUp(T, 64), static_cast<unsigned>(R)), 64, 0, ws->stream>>>(
-        P, d_xyz, n, d_unweighted, d_weighted, d_max);
-    RecordEvent(ws->ev_k1, ws->stream);
-    Rt3DCollectKernel<<<DivUp(num_candidates, 256), 256, 0, ws->stream>>>(
-        d_weighted, num_candidates, d_max, d_count, d_finalists, kFinalistCap);
-    CMX_HIP(hipGetLastError());
-    RecordEvent(ws->ev_end, ws->stream);
-    CMX_HIP(hipMemcpyAsync(h_misc, d_misc, 16 + sizeof(long long) * kFinalistCap,
-                           hipMemcpyDeviceToHost, ws->stream));
-    CMX_HIP(hipStreamSynchronize(ws->stream));
-
-    const int count = *reinterpret_cast<int*>(h_misc + 4);
-    const long long* h_finalists = reinterpret_cast<long long*>(h_misc + 16);
-    if (count <= kFinalistCap) {
-      finalists.assign(h_finalists, h_finalists + count);
-      std::sort(finalists.begin(), finalists.end());
-      acc.resize(count);
-      for (int i = 0; i < count; ++i)
-        CMX_HIP(hipMemcpy(&acc[i], d_unweighted + finalists[i], sizeof(float),
-                          hipMemcpyDeviceToHost));
-    } else {
-      finalists.resize(num_candidates);
-      for (long long c = 0; c < num_candidates; ++c) finalists[c] = c;
-      acc.resize(num_candidates);
-      CMX_HIP(hipMemcpy(acc.data(), d_unweighted, sizeof(float) * num_candidates,
-                        hipMemcpyDeviceToHost));
-    }
-    }
-    CMX_REQUIRE(!finalists.empty(), "internal error: no candidate collected");
-    // Exact weighting and the strict '>' running maximum of :44-50.
-    float best_score = -1.f;
-    long long best = -1;
-    for (size_t i = 0; i < finalists.size(); ++i) {
-      const long long c = finalists[i];
-      const long long t = c / R, r = c % R;
-      float sc = acc[i];
-      const double penalty = static_cast<double>(trans[t].w) * P.wt +
-                             static_cast<double>(angle[r]) * P.wr;
-      sc *= std::exp(-(penalty * (penalty * 1.)));
-      if (sc > best_score) { best_score = sc; best = c; }
-    }
-    {
-      const long long t = best / R, r = best % R;
-      h3::Rigid candidate;
-      candidate.t = {trans[t].x, trans[t].y, trans[t].z};
-      candidate.q = {rot[r].w, rot[r].x, rot[r].y, rot[r].z};
-      *pose_estimate = h3::ToPose(candidate);
-      *score = best_score;
-    }
-    if (stats) {
-      cmx_match_stats st{};
-      // Bulk path: the search space is covered by bounds -- R * G group bounds plus the
-      // candidates scored one by one; `candidates_scored` stays the size of the search space
-      // (what the reference scores), `coarse_candidates` says how many bounds that took.
-      st.candidates_scored = num_candidates;
-      st.coarse_candidates = bounds_evaluated ? bounds_evaluated : num_candidates;
-      st.num_scans = static_cast<int>(R);
-      st.nodes_expanded = num_finalists;   // bulk path: candidates re-scored exactly
-      float ms = 0.f;
-      ms = ElapsedMs(ws->ev_begin, ws->ev_end);
-      st.device_ms = ms;
-      ms = ElapsedMs(ws->ev_k0, ws->ev_k1);
-      st.dominant_kernel_ms = ms;
-      // the bounds above the candidates (rotation blocks, then the (rotation, group) pairs they
-      // leave): how many, their lookups, and the time of ALL their passes
-      st.expansion_nodes = group_bounds;
-      st.expansion_lookups = group_bounds * n;
-      st.expansion_ms = ms;
-      if (second_pairs_pass) {
-        ms = ElapsedMs(ws->ev_x0, ws->ev_x1);
-        st.expansion_ms += ms;
-      }
-      *stats = st;
-    }
+    Rt3DMatch(options, grid_resolution, voxels, num_voxels, resident, initial_pose_estimate,
+              point_cloud_xyz, num_points, device, score, pose_estimate, stats);
   });
 }
 }  // namespace

@@ -400,6 +400,59 @@ def test_rt3d_bulk_pass_flat_landscape_falls_back(sm3, oracle):
     np.testing.assert_array_equal(_pose7(pose), ref["pose"])
 
 
+def test_rt3d_resident_grid_paths_and_remaining_switches(sm3, oracle, synth, debug):
+    """The resident-grid entry on every path of the driver (shipped, verified, gather kernels,
+    exhaustive), and the voxel entry under the switches no other test sets (chunk boxes inside
+    the tile kernels, second candidate round in one piece, group centres in f32), each verified
+    on the device.  A cloud of more than 2 048 points -- the segment window below 32 768 points
+    -- so all three point segments hold chunks.  Oracle's score and pose bit for bit."""
+    from cartographer_amd import _lib, grid_3d
+    world = synth.World3D(5, (8.0, 8.0, 4.0))
+    dev, host = grid_3d.HybridGridOnDevice(0.1), synth.HybridGrid(0.1)
+    for p in range(4):
+        pos = world.free_position(50 + p, 0.5)
+        sensor = world.scan(pos, 0.2 * p, 6, 64, seed=p).astype(np.float64)
+        c, s = math.cos(0.2 * p), math.sin(0.2 * p)
+        in_map = np.stack([pos[0] + c * sensor[:, 0] - s * sensor[:, 1],
+                           pos[1] + s * sensor[:, 0] + c * sensor[:, 1],
+                           pos[2] + sensor[:, 2]], 1).astype(np.float32)
+        dev.insert(pos.astype(np.float32), in_map, 0.7, 0.4, 2)
+        host.insert(pos.astype(np.float32), in_map, 0.7, 0.4, 2)
+    cloud = world.scan(pos, 0.6, 16, 256, seed=9)[:2500].copy()
+    assert cloud.shape[0] > 2048
+    init = list(pos + np.array([0.07, -0.04, 0.02])) + quat_from_angle_axis(0.61, [0, 0, 1])
+    vox = host.voxels()
+    ref = oracle.rt3d_match(0.1, vox, init, cloud, 0.2, math.radians(1.0), 0.1, 0.1)
+    # the intended window: (2L+1)^3 (2A+1)^3 with L = 2 and A >= 1 (the rotation-block level is on)
+    rotations, rest = divmod(ref["num_candidates"], 5 ** 3)
+    side_r = round(rotations ** (1.0 / 3.0))
+    assert rest == 0 and side_r ** 3 == rotations and side_r % 2 == 1 and side_r >= 3
+    m = sm3.RealTimeCorrelativeScanMatcher3D(0.2, math.radians(1.0), 0.1, 0.1)
+    rigid = sm3.Rigid3d(tuple(init[:3]), tuple(init[3:]))
+    runs = [("grid", {}),
+            ("grid", dict(rt3d_verify=1)),
+            ("grid", dict(rt3d_no_tiles=1, rt3d_verify=1)),
+            ("grid", dict(rt3d_legacy=1)),
+            ("voxels", dict(rt3d_no_boxes=1, rt3d_verify=1)),
+            ("voxels", dict(rt3d_unstaged=1, rt3d_verify=1)),
+            ("voxels", dict(rt3d_group_float=1, rt3d_verify=1))]
+    for entry, switches in runs:
+        _lib.debug_reset()
+        debug(**switches)
+        if entry == "grid":
+            score, pose = m.match_grid(rigid, cloud, dev)
+        else:
+            score, pose = m.match(rigid, cloud, 0.1, vox)
+        print(entry, switches, float(score), dict(m.last_stats))
+        assert np.float32(score) == np.float32(ref["score"]), (entry, switches)
+        np.testing.assert_array_equal(_pose7(pose), ref["pose"])
+        assert m.last_stats["candidates_scored"] == ref["num_candidates"]
+        if switches.get("rt3d_legacy"):
+            assert m.last_stats["nodes_expanded"] == 0
+        else:
+            assert 1 <= m.last_stats["nodes_expanded"] <= 4096, (entry, switches)
+
+
 # ----------------------------------------------------------------------------
 # fast-3D device batch (round 2): one chain of launches for all pairs of a node
 # ----------------------------------------------------------------------------
