@@ -152,6 +152,18 @@ class Result3D(C.Structure):
                 ("low_resolution_score", C.c_float)]
 
 
+class DebugFast2DProblemPlan(C.Structure):
+    _fields_ = [("use_planes", C.c_int32), ("plane_stride", C.c_int32), ("use_fused", C.c_int32),
+                ("group", C.c_int32), ("num_scans", C.c_int32), ("reserved", C.c_int32),
+                ("acc", C.c_int64)]
+
+
+class DebugFast2DLaunchPlan(C.Structure):
+    _fields_ = [("fused_lds", C.c_int64), ("fused_acc", C.c_int64),
+                ("plane_acc_cells", C.c_int64), ("any_group", C.c_int32),
+                ("max_scans", C.c_int32), ("per_unit", C.c_int32), ("reserved", C.c_int32)]
+
+
 # Every symbol include/cartographer_mi355x.h declares.
 EXPORTED_SYMBOLS = [
     "cmx_version", "cmx_status_string", "cmx_last_error", "cmx_device_count", "cmx_set_stream",
@@ -191,7 +203,7 @@ EXPORTED_SYMBOLS = [
 ]
 
 # include/cartographer_mi355x_debug.h (test and tool switches, not part of the boundary).
-DEBUG_SYMBOLS = ["cmx_debug_set", "cmx_debug_reset"]
+DEBUG_SYMBOLS = ["cmx_debug_set", "cmx_debug_reset", "cmx_debug_fast2d_plan"]
 
 _lib = None
 
@@ -396,6 +408,10 @@ def lib():
     if hasattr(L, "cmx_debug_set"):        # (absent from the round-3 library the A/B tools load)
         L.cmx_debug_set.argtypes = [C.c_char_p, C.c_int32]
         L.cmx_debug_reset.restype = None
+    if hasattr(L, "cmx_debug_fast2d_plan"):
+        L.cmx_debug_fast2d_plan.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
+                                            C.c_void_p, C.c_int32, C.c_float, C.c_void_p,
+                                            P(DebugFast2DLaunchPlan)]
     _lib = L
     return L
 

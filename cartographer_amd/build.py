@@ -32,7 +32,8 @@ def build_hip(force=False, verbose=False):
     os.makedirs(LIB, exist_ok=True)
     srcs = sorted(glob.glob(os.path.join(CSRC, "*.hip")))
     hdrs = sorted(glob.glob(os.path.join(CSRC, "*.h"))) + \
-        [os.path.join(HERE, "..", "include", "cartographer_mi355x.h")]
+        [os.path.join(HERE, "..", "include", h) for h in ("cartographer_mi355x.h",
+                                                          "cartographer_mi355x_debug.h")]
     objs = []
     procs = []
     for src in srcs:

@@ -525,6 +525,7 @@ ScoreCoarsePlanesDwordKernel(const Fast2DProblem* __restrict__ problems, int n,
 // Dynamic LDS: pts[group][n_pad] u32 | misc[kFusedMisc] | cand_acc[acc_cap] | point words[waves][64].
 constexpr int kFusedMaxPoints = 4096;    // = kPointCache of the tree search
 constexpr int kFusedMisc = 128;          // ints of bookkeeping between the cells and the accumulators
+constexpr long long kFusedLdsLimit = 64 * 1024;   // dynamic LDS of a launch that does not opt in to more
 
 // Points kFirst .. kFirst + 7 of a lane group (LDS words at a stride of 16 bytes from `base`): the
 // low halves into lo[0..7], the high halves into hi[0..7], zero-extended; returns when they landed.
@@ -1055,6 +1056,100 @@ std::shared_ptr<const std::vector<float2>> HostRotationTable(double step, int nu
   return table;
 }
 
+// Every decision of the front end, per problem and per launch (fast_2d_internal.h).
+FrontEndPlan PlanFrontEnd(const PlanMatcher* matchers, int num, const int32_t* full_flags,
+                          bool full_submap, int n, float max_range_xy, bool write_all_discrete) {
+  const auto is_full = [&](int p) { return full_flags ? full_flags[p] != 0 : full_submap; };
+  FrontEndPlan plan;
+  plan.problems.resize(num);
+  const bool fused_enabled = FusedEnabled();
+  const long long n_pad = (n + 63) & ~63;
+  // Dynamic LDS of PrepScoreFusedKernel: pts | misc | candidate sums | 64 point words per
+  // wavefront (at most four).  The kernel does not opt in to more than kFusedLdsLimit.
+  const auto fused_lds = [&](int group, long long acc) {
+    return 4 * n_pad * group + 4 * (kFusedMisc + acc) + 4 * 256;
+  };
+  for (int p = 0; p < num; ++p) {
+    const PlanMatcher& m = matchers[p];
+    const cmx_grid2d_limits& lim = m.limits;
+    ProblemPlan& Q = plan.problems[p];
+    HostSearch h;
+    if (is_full(p)) {
+      // SM2/fast_...2d.cc:213-222.
+      h = MakeSearch(1e6 * lim.resolution, M_PI, max_range_xy, lim.resolution);
+    } else {
+      h = MakeSearch(m.linear_search_window, m.angular_search_window, max_range_xy, lim.resolution);
+    }
+    CMX_REQUIRE(h.num_scans >= 1 && h.num_scans < (1 << 20), "unsupported number of scans %d",
+                h.num_scans);
+    Q.search = h;
+    plan.max_scans = std::max(plan.max_scans, h.num_scans);
+    // Upper bound of lowest-resolution candidates per scan: the shrunk window
+    // never exceeds nx-1 plus the cell spread of the scan, nor 2*nl.
+    const int step = 1 << (m.depth - 1);
+    const double spread_cells = 2.0 * (std::max(max_range_xy, 0.f) / lim.resolution + 2.0);
+    auto per_axis = [&](int cells) {
+      const double width = std::min(2.0 * h.nl, cells - 1 + spread_cells);
+      return static_cast<long long>(width / step) + 2;
+    };
+    const long long ax = per_axis(lim.num_x_cells), ay = per_axis(lim.num_y_cells);
+    CMX_REQUIRE(ax * ay * h.num_scans < (1ll << 30),
+                "search too large: %lld lowest-resolution candidates", ax * ay * h.num_scans);
+    Q.ax = ax;
+    Q.ay = ay;
+    Q.use_planes = m.planes && ax * ay <= kMaxCoarsePerScan &&
+                   (ax + m.plane_i - 1) * (ay + m.plane_j - 1) <= kMaxBuckets &&
+                   ax + m.plane_i - 1 <= 255 && ay + m.plane_j - 1 <= 255 &&   // 8-bit bx, by
+                   (ax + 2 * m.plane_i - 2) * (ay + 2 * m.plane_j - 2) <= kMaxAccCells &&
+                   m.depth > 1;
+    const long long acc = (ax + 2 * m.plane_i - 2) * (ay + 2 * m.plane_j - 2);
+    Q.acc = acc;
+    if (Q.use_planes) plan.plane_acc_cells = std::max(plan.plane_acc_cells, acc);
+    // Fused front end: 64-byte planes, the scan + the accumulators within the 64 KB of
+    // dynamic LDS a launch gets without opting in to more.
+    // (... and the lattice block of a point + 1 within 16 bits: the fused kernel's point words)
+    Q.use_fused = fused_enabled && Q.use_planes && m.plane_stride == 64 &&
+                  n <= kFusedMaxPoints && fused_lds(1, acc) <= kFusedLdsLimit &&
+                  (ax + m.plane_i - 2) * (ay + 2 * m.plane_j - 2) + (ay + m.plane_j - 1) <= 65535;
+    if (Q.use_fused) {
+      plan.any_fused = true;
+      plan.fused_acc = std::max(plan.fused_acc, acc);
+    } else {
+      plan.any_unfused = true;
+    }
+    // Group bounds: three rotations per workgroup, one sum over the dilated level (the kernel's
+    // long comment).  Not for the callers that need every exact lowest-resolution score
+    // (introspection, depth 1), not where two cells of dilation are a large part of the
+    // lowest-resolution window (below 16 cells the bounds stop excluding anything).
+    // fast2d_group: 1 never, 2 whenever the planes exist.
+    const int sw = Debug().fast2d_group;
+    const bool wanted = sw == 1 ? false : sw == 2 ? true : m.depth >= 5;
+    Q.group = (wanted && Q.use_fused && m.planes_group && m.depth > 1 && !write_all_discrete &&
+               h.num_scans >= kFusedGroup && fused_lds(kFusedGroup, acc) <= kFusedLdsLimit)
+                  ? kFusedGroup : 1;
+    if (Q.group > 1) plan.any_group = true;
+  }
+  if (plan.any_fused) {
+    // The launch is ONE for all fused problems of the call: three scans of points as soon as any
+    // problem is grouped, the accumulators of the largest problem -- which need not be a grouped
+    // one.  Either fitted on its own; where the two together do not, nobody is grouped (every
+    // rotation summed on the level itself: same results, the sums are exact instead of bounds).
+    if (plan.any_group && fused_lds(kFusedGroup, plan.fused_acc) > kFusedLdsLimit) {
+      for (ProblemPlan& Q : plan.problems) Q.group = 1;
+      plan.any_group = false;
+    }
+    // (units of a launch: rotations, or groups of three; a batch that mixes both is sized for
+    // single rotations -- surplus workgroups of a grouped problem return at once)
+    bool all_group = true;
+    for (const ProblemPlan& Q : plan.problems) all_group = all_group && (!Q.use_fused || Q.group > 1);
+    plan.per_unit = all_group ? kFusedGroup : 1;
+    plan.fused_lds = static_cast<size_t>(fused_lds(plan.any_group ? kFusedGroup : 1, plan.fused_acc));
+    CMX_REQUIRE(plan.fused_lds <= static_cast<size_t>(kFusedLdsLimit),
+                "internal error: the fused front end planned %zu bytes of LDS", plan.fused_lds);
+  }
+  return plan;
+}
+
 // Uploads problem descriptors, carves scratch and runs the preparation +
 // lowest-resolution scoring kernels.  `d_xyz` is the device point cloud.
 void PrepareAndScoreCoarse(Workspace& ws, const Fast2DMatcher* const* matchers, int num,
@@ -1072,6 +1167,15 @@ void PrepareAndScoreCoarse(Workspace& ws, const Fast2DMatcher* const* matchers, 
   out->initial.resize(num);
   out->h_problems.resize(num);
 
+  std::vector<PlanMatcher> views(num);
+  for (int p = 0; p < num; ++p) views[p] = PlanMatcherOf(*matchers[p]);
+  const FrontEndPlan plan = PlanFrontEnd(views.data(), num, full_flags, full_submap, n, max_range_xy,
+                                         out->write_all_discrete);
+  out->plane_acc_cells = std::max(out->plane_acc_cells, plan.plane_acc_cells);
+  out->any_group = plan.any_group;
+  const long long fused_acc = plan.fused_acc;
+  const bool any_fused = plan.any_fused, any_unfused = plan.any_unfused;
+
   // Per-problem search parameters and scratch sizes.
   size_t discrete_total = 0, scans_total = 0, coarse_total = 0;
   // Rotation tables (host libm values, cached process-wide) of the distinct
@@ -1080,28 +1184,20 @@ void PrepareAndScoreCoarse(Workspace& ws, const Fast2DMatcher* const* matchers, 
   std::vector<Rotation> rotations;
   std::vector<int> rotation_of(num);
   size_t rotation_floats = 0;
-  const bool fused_enabled = FusedEnabled();
-  const int n_pad = (n + 63) & ~63;
-  long long fused_acc = 0;
-  bool any_fused = false, any_unfused = false;
   for (int p = 0; p < num; ++p) {
     const Fast2DMatcher& m = *matchers[p];
     const cmx_grid2d_limits& lim = m.limits();
-    HostSearch h;
+    const ProblemPlan& Q = plan.problems[p];
+    const HostSearch& h = Q.search;
     cmx_pose2d init;
     if (is_full(p)) {
       // SM2/fast_...2d.cc:213-222.
-      h = MakeSearch(1e6 * lim.resolution, M_PI, max_range_xy, lim.resolution);
       init.x = lim.max_x - 0.5 * lim.resolution * lim.num_y_cells;
       init.y = lim.max_y - 0.5 * lim.resolution * lim.num_x_cells;
       init.theta = 0.;
     } else {
-      h = MakeSearch(m.options().linear_search_window, m.options().angular_search_window,
-                     max_range_xy, lim.resolution);
       init = initial_or_null[p];
     }
-    CMX_REQUIRE(h.num_scans >= 1 && h.num_scans < (1 << 20), "unsupported number of scans %d",
-                h.num_scans);
     out->search[p] = h;
     out->initial[p] = init;
     int r = -1;
@@ -1116,56 +1212,15 @@ void PrepareAndScoreCoarse(Workspace& ws, const Fast2DMatcher* const* matchers, 
     rotation_of[p] = r;
     discrete_total += static_cast<size_t>(h.num_scans) * n;
     scans_total += h.num_scans + 1;
-    // Upper bound of lowest-resolution candidates per scan: the shrunk window
-    // never exceeds nx-1 plus the cell spread of the scan, nor 2*nl.
-    const int step = 1 << (m.depth() - 1);
-    const double spread_cells = 2.0 * (std::max(max_range_xy, 0.f) / lim.resolution + 2.0);
-    auto per_axis = [&](int cells) {
-      const double width = std::min(2.0 * h.nl, cells - 1 + spread_cells);
-      return static_cast<long long>(width / step) + 2;
-    };
-    const long long ax = per_axis(lim.num_x_cells), ay = per_axis(lim.num_y_cells);
-    const long long cap = ax * ay * h.num_scans;
-    CMX_REQUIRE(cap < (1ll << 30), "search too large: %lld lowest-resolution candidates", cap);
+    const long long cap = Q.ax * Q.ay * h.num_scans;
     Fast2DProblem& P = out->h_problems[p];
     P.coarse_capacity = static_cast<int>(cap);
-    P.coarse_stride = static_cast<int>(ax * ay);
-    P.use_planes = m.planes() != nullptr && ax * ay <= kMaxCoarsePerScan &&
-                   (ax + m.plane_i() - 1) * (ay + m.plane_j() - 1) <= kMaxBuckets &&
-                   ax + m.plane_i() - 1 <= 255 && ay + m.plane_j() - 1 <= 255 &&   // 8-bit bx, by
-                   (ax + 2 * m.plane_i() - 2) * (ay + 2 * m.plane_j() - 2) <= kMaxAccCells &&
-                   m.depth() > 1;
-    const long long acc = (ax + 2 * m.plane_i() - 2) * (ay + 2 * m.plane_j() - 2);
-    if (P.use_planes)
-      out->plane_acc_cells = std::max<long long>(out->plane_acc_cells, acc);
-    // Fused front end: 64-byte planes, the scan + the accumulators within the 64 KB of
-    // dynamic LDS a launch gets without opting in to more.
-    // (... and the lattice block of a point + 1 within 16 bits: the fused kernel's point words)
-    P.use_fused = fused_enabled && P.use_planes && m.plane_stride() == 64 &&
-                  n <= kFusedMaxPoints && 4ll * n_pad + 4 * (kFusedMisc + acc) + 1024 <= 64 * 1024 &&
-                  (ax + m.plane_i() - 2) * (ay + 2 * m.plane_j() - 2) + (ay + m.plane_j() - 1) <= 65535;
-    if (P.use_fused) {
-      any_fused = true;
-      fused_acc = std::max(fused_acc, acc);
-    } else {
-      any_unfused = true;
-    }
+    P.coarse_stride = static_cast<int>(Q.ax * Q.ay);
+    P.use_planes = Q.use_planes;
+    P.use_fused = Q.use_fused;
     P.write_all_discrete = out->write_all_discrete ? 1 : 0;
-    // Group bounds: three rotations per workgroup, one sum over the dilated level (the kernel's
-    // long comment).  Not for the callers that need every exact lowest-resolution score
-    // (introspection, depth 1), not where two cells of dilation are a large part of the
-    // lowest-resolution window (below 16 cells the bounds stop excluding anything).
-    // fast2d_group: 1 never, 2 whenever the planes exist.
-    {
-      const int sw = Debug().fast2d_group;
-      const bool wanted = sw == 1 ? false : sw == 2 ? true : m.depth() >= 5;
-      P.group = (wanted && P.use_fused && m.planes_group() != nullptr && m.depth() > 1 &&
-                 !out->write_all_discrete && h.num_scans >= kFusedGroup &&
-                 4ll * kFusedGroup * n_pad + 4 * (kFusedMisc + acc) + 1024 <= 64 * 1024)
-                    ? kFusedGroup : 1;
-      P.group_verify = Debug().fast2d_group_verify;
-      if (P.group > 1) out->any_group = true;
-    }
+    P.group = Q.group;
+    P.group_verify = Debug().fast2d_group_verify;
     P.timeline = nullptr;
     coarse_total += cap;
   }
@@ -1273,16 +1328,11 @@ void PrepareAndScoreCoarse(Workspace& ws, const Fast2DMatcher* const* matchers, 
     // Threads per block: with 192 (three waves) ten blocks fit a CU, i.e. a single search's
     // ~2300 rotations are all resident at once and the launch takes one block's latency;
     // batches run several rounds anyway and use full 256-thread blocks.
-    // (units of a launch: rotations, or groups of three; a batch that mixes both is sized for
-    // single rotations -- surplus workgroups of a grouped problem return at once)
-    bool all_group = true;
-    for (const Fast2DProblem& P : out->h_problems) all_group = all_group && (!P.use_fused || P.group > 1);
-    const int per_unit = all_group ? kFusedGroup : 1;
+    // (units and LDS of the launch: PlanFrontEnd)
+    const int per_unit = plan.per_unit;
     const int units = (out->max_scans + per_unit - 1) / per_unit;
     const long long blocks = static_cast<long long>(units) * num;
-    // pts | misc | candidate sums | 64 point words per wavefront (at most four)
-    const size_t lds = 4 * static_cast<size_t>(n_pad) * (out->any_group ? kFusedGroup : 1) +
-                       4 * static_cast<size_t>(kFusedMisc + fused_acc) + 4 * 256;
+    const size_t lds = plan.fused_lds;
     out->fused_lds = lds;
     out->fused_acc = static_cast<int>(fused_acc);
     out->d_xyz = d_xyz;

@@ -71,6 +71,43 @@ struct BatchResult {
 };
 
 // ---- fast_2d_coarse.hip
+// What the front end's planner reads of a matcher: of a Fast2DMatcher, or of a grid's geometry
+// alone (the plan entry of cartographer_mi355x_debug.h: no device needed).
+struct PlanMatcher {
+  cmx_grid2d_limits limits;
+  double linear_search_window, angular_search_window;
+  int depth;
+  bool planes, planes_group;       // the phase planes (of the level / of its dilation) exist
+  int plane_i, plane_j, plane_stride;
+};
+PlanMatcher PlanMatcherOf(const Fast2DMatcher& m);
+// (fast_2d_stack.hip: the planes a matcher of this grid and these options would build)
+PlanMatcher PlanMatcherOf(const cmx_fast2d_options& options, const cmx_grid2d_limits& limits);
+
+// The route of one problem through the front end ...
+struct ProblemPlan {
+  HostSearch search;
+  long long ax = 0, ay = 0;        // lowest-resolution candidates per scan and axis (upper bound)
+  long long acc = 0;               // padded LDS accumulators of the plane kernels
+  bool use_planes = false, use_fused = false;
+  int group = 1;                   // rotations per workgroup of the fused front end: 1 or kFusedGroup
+};
+// ... and the sizes of the launches of the call, which are maxima / "any" flags over its problems.
+struct FrontEndPlan {
+  std::vector<ProblemPlan> problems;
+  bool any_fused = false, any_unfused = false, any_group = false;
+  long long fused_acc = 0;         // accumulators of the fused launch (largest of its problems)
+  long long plane_acc_cells = 0;   // accumulators of the plane launches
+  int max_scans = 0;
+  int per_unit = 1;                // rotations per unit of the fused launch's grid
+  size_t fused_lds = 0;            // dynamic LDS of the fused launch, bytes (0: no fused problem)
+};
+// Every decision PrepareAndScoreCoarse takes before it launches; launches nothing itself.
+// `full_flags` (or null: `full_submap` for all) as there; `write_all_discrete`: the introspection
+// entry, which needs exact lowest-resolution sums (no group bounds).
+FrontEndPlan PlanFrontEnd(const PlanMatcher* matchers, int num, const int32_t* full_flags,
+                          bool full_submap, int n, float max_range_xy, bool write_all_discrete);
+
 // Uploads problem descriptors, carves scratch and runs the preparation +
 // lowest-resolution scoring kernels.  `d_xyz` is the device point cloud.
 void PrepareAndScoreCoarse(Workspace& ws, const Fast2DMatcher* const* matchers, int num,

@@ -18,6 +18,7 @@
 #include <functional>
 #include <vector>
 
+#include "../../include/cartographer_mi355x_debug.h"
 #include "fast_2d_internal.h"
 
 namespace cmx {
@@ -202,6 +203,9 @@ void MatchBatch(const cmx_fast2d* const* handles, int num, const cmx_pose2d* ini
     matchers[p] = handles[p]->impl.get();
     CMX_REQUIRE(matchers[p]->device() == matchers[0]->device(),
                 "all matchers of a batch must live on the same device");
+    // (the tree search walks the batch level by level; refused here, before anything is launched)
+    CMX_REQUIRE(matchers[p]->depth() == matchers[0]->depth(),
+                "all matchers of a batch must share branch_and_bound_depth");
   }
   const int device = matchers[0]->device();
   // Large batches (from 32 problems on; debug switch fast2d_fanout: 1 never, N > 1 from N on) as
@@ -507,6 +511,55 @@ cmx_status cmx_fast2d_debug_prepare(const cmx_fast2d* matcher,
       const std::vector<int> dense = cmx::DownloadDense(P, layout, P.coarse_sum);
       std::copy(dense.begin(), dense.end(), coarse_sums);
     }
+  });
+}
+
+cmx_status cmx_debug_fast2d_plan(const cmx_fast2d* const* matchers,
+                                 const cmx_grid2d_limits* limits,
+                                 const cmx_fast2d_options* options, int32_t num_matchers,
+                                 const int32_t* match_full_submap, int32_t num_points,
+                                 float max_range_xy, cmx_debug_fast2d_problem_plan* problems,
+                                 cmx_debug_fast2d_launch_plan* launch) {
+  return Guard([&] {
+    CMX_REQUIRE(num_matchers >= 1 && num_points >= 1 && problems && launch, "bad argument");
+    CMX_REQUIRE(matchers || (limits && options), "matchers, or limits and options");
+    std::vector<cmx::PlanMatcher> views(num_matchers);
+    for (int p = 0; p < num_matchers; ++p) {
+      if (matchers) {
+        CMX_REQUIRE(matchers[p] && matchers[p]->impl, "null matcher handle");
+        views[p] = cmx::PlanMatcherOf(*matchers[p]->impl);
+      } else {
+        // (what cmx_fast2d_create requires of them)
+        CMX_REQUIRE(options[p].branch_and_bound_depth >= 1 &&
+                        options[p].branch_and_bound_depth <= cmx::kMaxDepth,
+                    "branch_and_bound_depth %d outside [1,%d]", options[p].branch_and_bound_depth,
+                    cmx::kMaxDepth);
+        CMX_REQUIRE(limits[p].resolution > 0. && limits[p].num_x_cells >= 1 &&
+                        limits[p].num_y_cells >= 1 && limits[p].num_x_cells <= 16384 &&
+                        limits[p].num_y_cells <= 16384, "unsupported grid limits");
+        views[p] = cmx::PlanMatcherOf(options[p], limits[p]);
+      }
+    }
+    const cmx::FrontEndPlan plan = cmx::PlanFrontEnd(views.data(), num_matchers, match_full_submap,
+                                                     false, num_points, max_range_xy, false);
+    for (int p = 0; p < num_matchers; ++p) {
+      const cmx::ProblemPlan& Q = plan.problems[p];
+      cmx_debug_fast2d_problem_plan& out = problems[p];
+      out = cmx_debug_fast2d_problem_plan{};
+      out.use_planes = Q.use_planes ? 1 : 0;
+      out.plane_stride = views[p].planes ? views[p].plane_stride : 0;
+      out.use_fused = Q.use_fused ? 1 : 0;
+      out.group = Q.group;
+      out.num_scans = Q.search.num_scans;
+      out.acc = Q.acc;
+    }
+    *launch = cmx_debug_fast2d_launch_plan{};
+    launch->fused_lds = static_cast<int64_t>(plan.fused_lds);
+    launch->fused_acc = plan.fused_acc;
+    launch->plane_acc_cells = plan.plane_acc_cells;
+    launch->any_group = plan.any_group ? 1 : 0;
+    launch->max_scans = plan.max_scans;
+    launch->per_unit = plan.per_unit;
   });
 }
 

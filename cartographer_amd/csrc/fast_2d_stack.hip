@@ -126,6 +126,42 @@ __global__ void BuildQuadsKernel(const uint8_t* __restrict__ level, int wx, int 
 
 }  // namespace
 
+// The phase planes of the lowest-resolution level a matcher of this grid builds: PI x PJ lattice
+// cells per plane where the level is narrow enough for them, and the planes of the level dilated
+// by two cells (group bounds of the fused front end) where the dilated image still fits that
+// lattice.  Host arithmetic only: the constructor below and the front end's planner share it.
+PlanMatcher PlanMatcherOf(const cmx_fast2d_options& options, const cmx_grid2d_limits& limits) {
+  PlanMatcher pm{};
+  pm.limits = limits;
+  pm.linear_search_window = options.linear_search_window;
+  pm.angular_search_window = options.angular_search_window;
+  pm.depth = options.branch_and_bound_depth;
+  const int depth = pm.depth;
+  const int w = 1 << (depth - 1);
+  const int wx = limits.num_x_cells + w - 1, wy = limits.num_y_cells + w - 1;   // the top level
+  const int PI = (wx + w - 1) / w, PJ = (wy + w - 1) / w;
+  if (w <= kMaxPlaneWidth && PI * PJ <= kMaxPlaneCells) {
+    pm.planes = true;
+    pm.plane_i = PI;
+    pm.plane_j = PJ;
+    pm.plane_stride = (PI * PJ + 63) & ~63;
+    const int dwx = wx + 2 * kGroupDilation, dwy = wy + 2 * kGroupDilation;
+    pm.planes_group = pm.plane_stride == 64 && depth > 1 && dwx <= PI * w && dwy <= PJ * w;
+  }
+  return pm;
+}
+
+PlanMatcher PlanMatcherOf(const Fast2DMatcher& m) {
+  PlanMatcher pm = PlanMatcherOf(m.options(), m.limits());
+  // (what the matcher holds is what counts: an allocation that failed would have thrown)
+  pm.planes = m.planes() != nullptr;
+  pm.planes_group = m.planes_group() != nullptr;
+  pm.plane_i = m.plane_i();
+  pm.plane_j = m.plane_j();
+  pm.plane_stride = m.plane_stride();
+  return pm;
+}
+
 // ---------------------------------------------------------------------------
 // Fast2DMatcher (host)
 // ---------------------------------------------------------------------------
@@ -209,11 +245,12 @@ Fast2DMatcher::Fast2DMatcher(const cmx_fast2d_options& options, const cmx_grid2d
   {
     const int w = 1 << (depth - 1);
     const LevelDesc& top = levels_[depth - 1];
-    const int PI = (top.wx + w - 1) / w, PJ = (top.wy + w - 1) / w;
-    if (w <= kMaxPlaneWidth && PI * PJ <= kMaxPlaneCells) {
+    const PlanMatcher layout = PlanMatcherOf(options, limits);
+    if (layout.planes) {
+      const int PI = layout.plane_i, PJ = layout.plane_j;
       plane_i_ = PI;
       plane_j_ = PJ;
-      plane_stride_ = (PI * PJ + 63) & ~63;
+      plane_stride_ = layout.plane_stride;
       const size_t bytes = static_cast<size_t>(w * w + 1) * plane_stride_;
       CMX_HIP(hipMalloc(reinterpret_cast<void**>(&planes_), bytes));
       BuildPlanesKernel<<<w * w + 1, 64, 0, ws->stream>>>(top.cells, top.wx, top.wy, w, PI, PJ,
@@ -221,7 +258,7 @@ Fast2DMatcher::Fast2DMatcher(const cmx_fast2d_options& options, const cmx_grid2d
       // The same planes of the level dilated by two cells (group bounds of the fused front end),
       // where the dilated image still fits the planes' PI x PJ lattice cells.
       const int dwx = top.wx + 2 * kGroupDilation, dwy = top.wy + 2 * kGroupDilation;
-      if (plane_stride_ == 64 && depth > 1 && dwx <= PI * w && dwy <= PJ * w) {
+      if (layout.planes_group) {
         uint8_t* dilated = ws->dev[0].ReserveAs<uint8_t>(static_cast<size_t>(dwx) * dwy);
         DilateLevelKernel<<<dim3(DivUp(dwx, 256), dwy), 256, 0, ws->stream>>>(top.cells, top.wx,
                                                                              top.wy, dilated);

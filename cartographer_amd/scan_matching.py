@@ -326,6 +326,38 @@ class FastCorrelativeScanMatcher2D:
         return dict(num_scans=ns.value, step=step.value, scans=scans, bounds=bounds, sums=sums)
 
 
+def debug_plan(matchers, match_full_submap, point_cloud=None, num_points=None, max_range_xy=None):
+    """cmx_debug_fast2d_plan: the routes the fast 2D front end would give the problems of one
+    call and the sizes of its launches; nothing is launched.  `matchers` are
+    FastCorrelativeScanMatcher2D objects, or -- no device needed -- (Grid2DLimits, Fast2DOptions)
+    pairs of the matchers one would create; `match_full_submap` as in match_batch (None: all
+    windowed).  The cloud enters through its size and its largest xy range: pass it, or the two
+    numbers.  Returns (problems, launch): a list of dicts (use_planes, plane_stride, use_fused,
+    group, acc, num_scans) and a dict (fused_lds, fused_acc, any_group, plane_acc_cells,
+    max_scans, per_unit)."""
+    num = len(matchers)
+    if point_cloud is not None:
+        xyz, num_points = _cloud(point_cloud)
+        x, y = xyz[:, 0], xyz[:, 1]
+        max_range_xy = float(np.sqrt(x * x + y * y).max()) if num_points else 0.0   # f32, as the library
+    handles = limits = options = None
+    if all(isinstance(m, FastCorrelativeScanMatcher2D) for m in matchers):
+        handles = (C.c_void_p * num)(*[m._h for m in matchers])
+    else:
+        limits = (Grid2DLimits * num)(*[m[0] for m in matchers])
+        options = (Fast2DOptions * num)(*[m[1] for m in matchers])
+    full = None if match_full_submap is None else np.ascontiguousarray(match_full_submap, np.int32)
+    problems = (_lib.DebugFast2DProblemPlan * num)()
+    launch = _lib.DebugFast2DLaunchPlan()
+    check(_lib.lib().cmx_debug_fast2d_plan(
+        handles, limits, options, num, None if full is None else full.ctypes.data,
+        int(num_points), float(max_range_xy), problems, C.byref(launch)))
+
+    def as_dict(s_):
+        return {name: int(getattr(s_, name)) for name, _ in s_._fields_ if name != "reserved"}
+    return [as_dict(p) for p in problems], as_dict(launch)
+
+
 def match_full_submap_batch(matchers, point_cloud, min_score):
     """One scan against many submaps: the ConstraintBuilder2D fan-out
     (constraints/constraint_builder_2d.cc:97-137) as a single device batch.

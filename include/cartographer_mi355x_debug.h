@@ -20,6 +20,42 @@ cmx_status cmx_debug_set(const char* name, int32_t value);
 /* Every switch back to 0. */
 void cmx_debug_reset(void);
 
+/* The plan of the fast 2D front end for one call of cmx_fast2d_match / _match_full_submap /
+ * _match_batch: which of its routes every problem takes and how the launches of the call are
+ * sized.  The launch path asks the same function; this entry launches nothing.  Tests use it
+ * to show that a batch really mixes the routes it is meant to mix. */
+typedef struct cmx_debug_fast2d_problem_plan {
+  int32_t use_planes;     /* lowest resolution scored over phase planes (0: the generic kernel) */
+  int32_t plane_stride;   /* bytes per phase plane: 64, 128, 192 or 256 (0: no planes) */
+  int32_t use_fused;      /* preparation and scoring in the one fused launch */
+  int32_t group;          /* rotations per workgroup of the fused launch: 1, or 3 (group bounds) */
+  int32_t num_scans;
+  int32_t reserved;
+  int64_t acc;            /* padded LDS accumulators this problem asks of a plane kernel */
+} cmx_debug_fast2d_problem_plan;
+
+typedef struct cmx_debug_fast2d_launch_plan {
+  int64_t fused_lds;        /* dynamic LDS of the fused launch, bytes (0: no fused problem) */
+  int64_t fused_acc;        /* its accumulators: the largest `acc` of the fused problems */
+  int64_t plane_acc_cells;  /* accumulators of the separate plane launches */
+  int32_t any_group;
+  int32_t max_scans;
+  int32_t per_unit;         /* rotations per unit of the fused launch's grid: 3 if all are grouped */
+  int32_t reserved;
+} cmx_debug_fast2d_launch_plan;
+
+/* `matchers` [num_matchers], or -- with `matchers` null -- the grids and options matchers would be
+ * created from (`limits`, `options` [num_matchers]): the plan depends on their geometry only, so
+ * that form needs no device.  `match_full_submap` [num_matchers] as in cmx_fast2d_match_batch
+ * (null: all windowed); `max_range_xy`: the largest xy range of the cloud's `num_points` points.
+ * The switches above apply as they do to a match.  `problems` [num_matchers] and `launch` out. */
+cmx_status cmx_debug_fast2d_plan(const cmx_fast2d* const* matchers,
+                                 const cmx_grid2d_limits* limits,
+                                 const cmx_fast2d_options* options, int32_t num_matchers,
+                                 const int32_t* match_full_submap, int32_t num_points,
+                                 float max_range_xy, cmx_debug_fast2d_problem_plan* problems,
+                                 cmx_debug_fast2d_launch_plan* launch);
+
 #ifdef __cplusplus
 }
 #endif
