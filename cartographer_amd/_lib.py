@@ -183,13 +183,13 @@ EXPORTED_SYMBOLS = [
     "cmx_cloud_destroy", "cmx_fast2d_match_full_submap_batch_resident", "cmx_fast2d_level_dims",
     "cmx_fast2d_level_cells", "cmx_fast2d_debug_prepare", "cmx_rt3d_match", "cmx_fast3d_create",
     "cmx_fast3d_destroy", "cmx_fast3d_match", "cmx_fast3d_match_full_submap",
-    "cmx_fast3d_match_batch",
+    "cmx_fast3d_match_batch", "cmx_fast3d_match_pairs",
     "cmx_fast3d_level_info", "cmx_fast3d_level_cells", "cmx_fast3d_create_from_grids",
     "cmx_ceres2d_match", "cmx_ceres2d_match_grid", "cmx_fast2d_refine_batch", "cmx_ceres3d_match",
     "cmx_ceres2d_match_tsdf", "cmx_ceres2d_match_tsdf_grid", "cmx_ceres2d_refine_batch_tsdf",
     "cmx_ceres2d_tsdf_residuals",
     "cmx_ceres3d_match_grids", "cmx_rt2d_score_candidates", "cmx_rt3d_match_grid",
-    "cmx_fast3d_refine_batch",
+    "cmx_fast3d_refine_batch", "cmx_fast3d_refine_pairs",
     "cmx_comm_init", "cmx_comm_destroy", "cmx_comm_num_devices", "cmx_comm_device_of",
     "cmx_comm_uses_rccl", "cmx_sizeof_match_stats",
     "cmx_fast2d_match_sharded", "cmx_fast3d_match_sharded", "cmx_shard_range",
@@ -403,6 +403,13 @@ def lib():
     L.cmx_fast3d_match_batch.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
                                          C.c_void_p, C.c_void_p, P(NodeData3D), C.c_void_p,
                                          C.c_void_p, P(MatchStats)]
+    if hasattr(L, "cmx_fast3d_match_pairs"):   # (absent from an older library an A/B tool loads)
+        L.cmx_fast3d_match_pairs.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
+                                             C.c_void_p, C.c_void_p, P(P(NodeData3D)), C.c_void_p,
+                                             C.c_void_p, P(MatchStats)]
+        L.cmx_fast3d_refine_pairs.argtypes = [P(Ceres3DOptions), P(C.c_void_p), C.c_int32,
+                                              C.c_void_p, C.c_void_p, P(P(NodeData3D)),
+                                              C.c_void_p, C.c_void_p]
     L.cmx_fast3d_level_info.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
     L.cmx_fast3d_level_cells.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
     if hasattr(L, "cmx_debug_set"):        # (absent from the round-3 library the A/B tools load)

@@ -290,10 +290,11 @@ class ConstraintBuilder3D:
     filter on the GLOBAL poses (:84-87), the per-submap ``FixedRatioSampler`` (:88-93), one
     matcher per ``SubmapId`` resident in HBM until ``DeleteScanMatcher``, ``Match`` /
     ``MatchFullSubmap`` with the two thresholds (:218-255), results in the order the pairs were
-    added (``RunWhenDoneCallback``).  ``NotifyEndOfNode`` hands the node's pairs to
-    ``cmx_fast3d_match_batch`` (one chain of launches for all pairs) and, with ``ceres`` (a
-    ``scan_matching_3d.CeresScanMatcher3D`` with two occupied-space weights: the builder's
-    ``ceres_scan_matcher_``), the found ones to ``cmx_fast3d_refine_batch`` (:263-276) -- both
+    added (``RunWhenDoneCallback``).  ``NotifyEndOfNode`` hands the queued pairs (of one
+    node, or of all nodes queued since) to ``cmx_fast3d_match_pairs`` (one chain of launches for
+    all pairs) and, with ``ceres`` (a ``scan_matching_3d.CeresScanMatcher3D`` with two
+    occupied-space weights: the builder's ``ceres_scan_matcher_``), the found ones to
+    ``cmx_fast3d_refine_pairs`` (:263-276) -- both
     against grids that stay in HBM.  ``refine`` is a host callback instead, for experiments.
     """
 
@@ -373,40 +374,43 @@ class ConstraintBuilder3D:
                               node, sub, self._scan_matchers[submap_id]))
 
     def _flush(self):
-        """The queued pairs of a node share its constant data: one cmx_fast3d_match_batch per
-        node (pairs searched concurrently on the device), in the order they were added."""
-        from .scan_matching_3d import Rigid3d, fast3d_match_batch
+        """All queued pairs, of however many nodes, go to the device together: one
+        cmx_fast3d_match_pairs and one cmx_fast3d_refine_pairs call (pairs searched concurrently
+        on the builder's device; a node's constant data is uploaded once).  Pairs of a node stay
+        together, in the order they were added."""
+        from .scan_matching_3d import Rigid3d, fast3d_match_pairs
         pending, self._pending = self._pending, []
+        if not pending:
+            return
         groups: Dict[int, list] = {}
         for item in pending:
             groups.setdefault(id(item[3]), []).append(item)
-        for items in groups.values():
-            constant_data = items[0][3]
-            as_pose = lambda v, full: Rigid3d((0.0, 0.0, 0.0), tuple(v)) if full else v   # noqa: E731
-            results, self.last_batch_stats = fast3d_match_batch(
-                [i[7] for i in items],
-                [as_pose(i[5], i[4]) for i in items], [as_pose(i[6], i[4]) for i in items],
-                [i[4] for i in items],
-                [self.options.global_localization_min_score if i[4] else self.options.min_score
-                 for i in items], constant_data)
-            refined = None
-            if self.ceres is not None and any(r is not None for r in results):
-                identity = Rigid3d()
-                refined, self.last_refine_summaries = self.ceres.refine_batch(
-                    [i[7] for i in items], [r is not None for r in results],
-                    [r["pose_estimate"] if r is not None else identity for r in results],
-                    constant_data)
-            for k, ((slot, submap_id, node_id, _, full, node, sub, _m), result) in enumerate(
-                    zip(items, results)):
-                if result is None:
-                    continue                               # `return;` at :232 / :253
-                self.score_histogram.append(result["score"])
-                pose = result["pose_estimate"]             # already submap i <- node j
-                if refined is not None:
-                    pose = refined[k]                      # ceres_scan_matcher_.Match (:263-276)
-                elif self.refine is not None:
-                    pose = self.refine(pose, constant_data)
-                self._constraints[slot] = Constraint3D(
-                    submap_id, node_id, pose, self.options.loop_closure_translation_weight,
-                    self.options.loop_closure_rotation_weight, result["score"],
-                    result["rotational_score"], result["low_resolution_score"])
+        items = [item for group in groups.values() for item in group]
+        as_pose = lambda v, full: Rigid3d((0.0, 0.0, 0.0), tuple(v)) if full else v   # noqa: E731
+        results, self.last_batch_stats = fast3d_match_pairs(
+            [i[7] for i in items],
+            [as_pose(i[5], i[4]) for i in items], [as_pose(i[6], i[4]) for i in items],
+            [i[4] for i in items],
+            [self.options.global_localization_min_score if i[4] else self.options.min_score
+             for i in items], [i[3] for i in items])
+        refined = None
+        if self.ceres is not None and any(r is not None for r in results):
+            identity = Rigid3d()
+            refined, self.last_refine_summaries = self.ceres.refine_pairs(
+                [i[7] for i in items], [r is not None for r in results],
+                [r["pose_estimate"] if r is not None else identity for r in results],
+                [i[3] for i in items])
+        for k, ((slot, submap_id, node_id, constant_data, full, node, sub, _m), result) in \
+                enumerate(zip(items, results)):
+            if result is None:
+                continue                               # `return;` at :232 / :253
+            self.score_histogram.append(result["score"])
+            pose = result["pose_estimate"]             # already submap i <- node j
+            if refined is not None:
+                pose = refined[k]                      # ceres_scan_matcher_.Match (:263-276)
+            elif self.refine is not None:
+                pose = self.refine(pose, constant_data)
+            self._constraints[slot] = Constraint3D(
+                submap_id, node_id, pose, self.options.loop_closure_translation_weight,
+                self.options.loop_closure_rotation_weight, result["score"],
+                result["rotational_score"], result["low_resolution_score"])

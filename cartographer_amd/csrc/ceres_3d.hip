@@ -623,6 +623,105 @@ void WriteResult(const double* out, cmx_pose3d* pose_estimate, cmx_ceres_summary
   }
 }
 
+void CheckRefineOptions3D(const cmx_ceres3d_options& options) {
+  CheckOptions(options);
+  // {high-resolution cloud, high-resolution grid}, {low-resolution cloud, low-resolution grid}
+  CMX_REQUIRE(options.num_pairs == 2, "the constraint refinement uses two (cloud, grid) pairs");
+}
+
+void CheckNodeClouds3D(const cmx_node_data3d& data) {
+  CMX_REQUIRE(data.high_resolution_point_cloud && data.num_high_resolution_points >= 1 &&
+                  data.low_resolution_point_cloud && data.num_low_resolution_points >= 1 &&
+                  data.num_high_resolution_points <= (1 << 24) &&
+                  data.num_low_resolution_points <= (1 << 24),
+              "bad point clouds");
+}
+
+// cmx_fast3d_refine_batch / cmx_fast3d_refine_pairs: pair p refines pose_estimates_in[p] against
+// the grids matchers[p] keeps in HBM with the clouds of datas[p] (not null).
+void RefinePairs3D(const cmx_ceres3d_options& options, const cmx_fast3d* const* matchers,
+                   int num_pairs, const int32_t* found, const cmx_pose3d* pose_estimates_in,
+                   const cmx_node_data3d* const* datas, cmx_pose3d* pose_estimates_out,
+                   cmx_ceres_summary* summaries) {
+  CheckRefineOptions3D(options);
+  for (int p = 0; p < num_pairs; ++p)
+    if (p == 0 || datas[p] != datas[p - 1]) CheckNodeClouds3D(*datas[p]);
+  for (int p = 0; p < num_pairs; ++p) {
+    CMX_REQUIRE(matchers[p] != nullptr, "matcher %d is null", p);
+    pose_estimates_out[p] = pose_estimates_in[p];        // not found: passed through
+    if (summaries) summaries[p] = cmx_ceres_summary{};
+  }
+  // Pairs are grouped by the device their grids live on (a node's batch may span the GPUs
+  // of a cmx_comm); each group is one launch.
+  std::vector<int> order;
+  for (int p = 0; p < num_pairs; ++p)
+    if (!found || found[p]) order.push_back(p);
+  std::stable_sort(order.begin(), order.end(), [&](int a, int b) {
+    return Fast3DDevice(matchers[a]) < Fast3DDevice(matchers[b]);
+  });
+  for (size_t begin = 0; begin < order.size();) {
+    const int device = Fast3DDevice(matchers[order[begin]]);
+    size_t end = begin;
+    while (end < order.size() && Fast3DDevice(matchers[order[end]]) == device) ++end;
+    const int num = static_cast<int>(end - begin);
+    // The distinct nodes of the group, each one's clouds staged once: high | low, node after node.
+    std::vector<const cmx_node_data3d*> nodes;
+    std::vector<size_t> node_floats;                     // where a node's clouds begin
+    std::vector<int> node_of(num);
+    size_t cloud_floats = 0;
+    for (int k = 0; k < num; ++k) {
+      const cmx_node_data3d* data = datas[order[begin + k]];
+      size_t j = 0;
+      while (j < nodes.size() && nodes[j] != data) ++j;
+      node_of[k] = static_cast<int>(j);
+      if (j < nodes.size()) continue;
+      nodes.push_back(data);
+      node_floats.push_back(cloud_floats);
+      cloud_floats += 3 * (static_cast<size_t>(data->num_high_resolution_points) +
+                           data->num_low_resolution_points);
+    }
+    WorkspaceLease ws(device);
+    float* d_xyz = ws->dev[0].ReserveAs<float>(cloud_floats);
+    float* h_xyz = ws->pinned[0].ReserveAs<float>(cloud_floats);
+    for (size_t j = 0; j < nodes.size(); ++j) {
+      const int n_hi = nodes[j]->num_high_resolution_points;
+      const int n_lo = nodes[j]->num_low_resolution_points;
+      std::memcpy(h_xyz + node_floats[j], nodes[j]->high_resolution_point_cloud,
+                  3 * sizeof(float) * n_hi);
+      std::memcpy(h_xyz + node_floats[j] + 3 * static_cast<size_t>(n_hi),
+                  nodes[j]->low_resolution_point_cloud, 3 * sizeof(float) * n_lo);
+    }
+    std::vector<Ceres3DProblem> problems(num);
+    for (int k = 0; k < num; ++k) {
+      const int p = order[begin + k];
+      const int n_hi = nodes[node_of[k]]->num_high_resolution_points;
+      const int n_lo = nodes[node_of[k]]->num_low_resolution_points;
+      float* xyz = d_xyz + node_floats[node_of[k]];
+      Ceres3DProblem& P = problems[k];
+      SetOptions(options, &P);
+      Fast3DGrids(matchers[p], &P.pair[0].grid, &P.pair[0].resolution, &P.pair[1].grid,
+                  &P.pair[1].resolution);
+      P.pair[0].n = n_hi;
+      P.pair[0].xyz = xyz;
+      P.pair[0].scaling = options.occupied_space_weight[0] / std::sqrt(static_cast<double>(n_hi));
+      P.pair[1].n = n_lo;
+      P.pair[1].xyz = xyz + 3 * static_cast<size_t>(n_hi);
+      P.pair[1].scaling = options.occupied_space_weight[1] / std::sqrt(static_cast<double>(n_lo));
+      // Match(match_result->pose_estimate.translation(), match_result->pose_estimate, ...)
+      for (int a = 0; a < 3; ++a) P.target[a] = P.init[a] = pose_estimates_in[p].t[a];
+      for (int a = 0; a < 4; ++a) P.init[3 + a] = pose_estimates_in[p].q[a];
+    }
+    std::vector<double> out(12 * static_cast<size_t>(num));
+    SolveProblems(*ws, problems.data(), num, cloud_floats, h_xyz, d_xyz, out.data());
+    for (int k = 0; k < num; ++k) {
+      const int p = order[begin + k];
+      WriteResult(out.data() + 12 * static_cast<size_t>(k), pose_estimates_out + p,
+                  summaries ? summaries + p : nullptr);
+    }
+    begin = end;
+  }
+}
+
 }  // namespace
 }  // namespace cmx
 
@@ -813,7 +912,8 @@ extern "C" cmx_status cmx_ceres3d_match_grids_intensity(
 }
 
 // ConstraintBuilder3D::ComputeConstraint's refinement (constraints/constraint_builder_3d.cc:
-// 263-276) for a node's batch: one workgroup per found pair, grids already in HBM.
+// 263-276) for a node's batch: one workgroup per found pair, grids already in HBM.  The case
+// "all pairs share one data" of RefinePairs3D.
 extern "C" cmx_status cmx_fast3d_refine_batch(const cmx_ceres3d_options* options,
                                               const cmx_fast3d* const* matchers,
                                               int32_t num_pairs, const int32_t* found,
@@ -825,65 +925,36 @@ extern "C" cmx_status cmx_fast3d_refine_batch(const cmx_ceres3d_options* options
   return Guard([&] {
     CMX_REQUIRE(options && data && pose_estimates_in && pose_estimates_out, "null argument");
     CMX_REQUIRE(num_pairs >= 0 && (num_pairs == 0 || matchers), "bad matcher list");
-    CheckOptions(*options);
-    // {high-resolution cloud, high-resolution grid}, {low-resolution cloud, low-resolution grid}
-    CMX_REQUIRE(options->num_pairs == 2, "the constraint refinement uses two (cloud, grid) pairs");
-    CMX_REQUIRE(data->high_resolution_point_cloud && data->num_high_resolution_points >= 1 &&
-                    data->low_resolution_point_cloud && data->num_low_resolution_points >= 1 &&
-                    data->num_high_resolution_points <= (1 << 24) &&
-                    data->num_low_resolution_points <= (1 << 24),
-                "bad point clouds");
-    for (int p = 0; p < num_pairs; ++p) {
-      CMX_REQUIRE(matchers[p] != nullptr, "matcher %d is null", p);
-      pose_estimates_out[p] = pose_estimates_in[p];        // not found: passed through
-      if (summaries) summaries[p] = cmx_ceres_summary{};
+    if (num_pairs == 0) {                 // nothing to refine: the arguments are checked all the same
+      CheckRefineOptions3D(*options);
+      CheckNodeClouds3D(*data);
+      return;
     }
-    const int n_hi = data->num_high_resolution_points, n_lo = data->num_low_resolution_points;
-    const size_t cloud_floats = 3 * (static_cast<size_t>(n_hi) + n_lo);
-    // Pairs are grouped by the device their grids live on (a node's batch may span the GPUs
-    // of a cmx_comm); each group is one launch.
-    std::vector<int> order;
+    const std::vector<const cmx_node_data3d*> datas(num_pairs, data);
+    RefinePairs3D(*options, matchers, num_pairs, found, pose_estimates_in, datas.data(),
+                  pose_estimates_out, summaries);
+  });
+}
+
+// The same for pairs that bring their own nodes (cmx_fast3d_match_pairs; pose_graph_3d.cc:
+// 370-379): pair p against data[p]'s clouds, a node named by several pairs staged once.
+extern "C" cmx_status cmx_fast3d_refine_pairs(const cmx_ceres3d_options* options,
+                                              const cmx_fast3d* const* matchers,
+                                              int32_t num_pairs, const int32_t* found,
+                                              const cmx_pose3d* pose_estimates_in,
+                                              const cmx_node_data3d* const* data,
+                                              cmx_pose3d* pose_estimates_out,
+                                              cmx_ceres_summary* summaries) {
+  using namespace cmx;
+  return Guard([&] {
+    // (a matcher handle cannot exist without a device: say so, whatever the arguments are)
+    if (cmx_device_count() <= 0) UseDevice(0);
+    CMX_REQUIRE(num_pairs >= 1, "num_pairs must be at least 1");
+    CMX_REQUIRE(options && matchers && data && pose_estimates_in && pose_estimates_out,
+                "null argument");
     for (int p = 0; p < num_pairs; ++p)
-      if (!found || found[p]) order.push_back(p);
-    std::stable_sort(order.begin(), order.end(), [&](int a, int b) {
-      return Fast3DDevice(matchers[a]) < Fast3DDevice(matchers[b]);
-    });
-    for (size_t begin = 0; begin < order.size();) {
-      const int device = Fast3DDevice(matchers[order[begin]]);
-      size_t end = begin;
-      while (end < order.size() && Fast3DDevice(matchers[order[end]]) == device) ++end;
-      const int num = static_cast<int>(end - begin);
-      WorkspaceLease ws(device);
-      float* d_xyz = ws->dev[0].ReserveAs<float>(cloud_floats);
-      float* h_xyz = ws->pinned[0].ReserveAs<float>(cloud_floats);
-      std::memcpy(h_xyz, data->high_resolution_point_cloud, 3 * sizeof(float) * n_hi);
-      std::memcpy(h_xyz + 3 * static_cast<size_t>(n_hi), data->low_resolution_point_cloud,
-                  3 * sizeof(float) * n_lo);
-      std::vector<Ceres3DProblem> problems(num);
-      for (int k = 0; k < num; ++k) {
-        const int p = order[begin + k];
-        Ceres3DProblem& P = problems[k];
-        SetOptions(*options, &P);
-        Fast3DGrids(matchers[p], &P.pair[0].grid, &P.pair[0].resolution, &P.pair[1].grid,
-                    &P.pair[1].resolution);
-        P.pair[0].n = n_hi;
-        P.pair[0].xyz = d_xyz;
-        P.pair[0].scaling = options->occupied_space_weight[0] / std::sqrt(static_cast<double>(n_hi));
-        P.pair[1].n = n_lo;
-        P.pair[1].xyz = d_xyz + 3 * static_cast<size_t>(n_hi);
-        P.pair[1].scaling = options->occupied_space_weight[1] / std::sqrt(static_cast<double>(n_lo));
-        // Match(match_result->pose_estimate.translation(), match_result->pose_estimate, ...)
-        for (int a = 0; a < 3; ++a) P.target[a] = P.init[a] = pose_estimates_in[p].t[a];
-        for (int a = 0; a < 4; ++a) P.init[3 + a] = pose_estimates_in[p].q[a];
-      }
-      std::vector<double> out(12 * static_cast<size_t>(num));
-      SolveProblems(*ws, problems.data(), num, cloud_floats, h_xyz, d_xyz, out.data());
-      for (int k = 0; k < num; ++k) {
-        const int p = order[begin + k];
-        WriteResult(out.data() + 12 * static_cast<size_t>(k), pose_estimates_out + p,
-                    summaries ? summaries + p : nullptr);
-      }
-      begin = end;
-    }
+      CMX_REQUIRE(data[p] != nullptr, "the node data of pair %d is null", p);
+    RefinePairs3D(*options, matchers, num_pairs, found, pose_estimates_in, data,
+                  pose_estimates_out, summaries);
   });
 }

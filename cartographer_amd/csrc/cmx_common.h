@@ -120,6 +120,7 @@ cmx_status Guard(F&& body) {
   X(fast3d_no_families)   /* 1: one node per block in the 3D expansion */                          \
   X(fast3d_no_oct)        /* 1: no oct words (byte levels only) */                                 \
   X(fast3d_batch)         /* pairs per chain of launches */                                        \
+  X(fast3d_chunk_cells)   /* most discretised cells (sum of scans x points) per chain of launches (tests: splits a batch) */ \
   X(rt3d_legacy)          /* 1: real-time 3D on the exhaustive per-candidate kernel only */        \
   X(rt3d_no_tiles)        /* 1: bulk passes by memory gathers instead of LDS tiles */              \
   X(rt3d_verify)          /* 1: every bound checked on the device against what it bounds */        \

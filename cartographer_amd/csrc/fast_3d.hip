@@ -20,6 +20,7 @@
 #include <chrono>
 #include <thread>
 #include <algorithm>
+#include <unordered_map>
 #include <cmath>
 #include <cstdlib>
 
@@ -238,22 +239,51 @@ Grid3DCropKernel(GridPair3D source, Brick high, Brick level0, Brick low) {
 // ---------------------------------------------------------------------------
 // Scan discretisation (DiscretizeScan, :200-244: transform + GetCellIndex)
 // ---------------------------------------------------------------------------
-// grid (ceil(n / 256), scans of the whole batch): `pose_t[s]` = the translation of the scan's
-// problem, .w its grid resolution.
+// Point i of a cloud under one scan's pose: `t4` = the translation of the scan's problem, .w its
+// grid resolution.
+__device__ __forceinline__ int4 DiscretizePoint3D(const float* __restrict__ xyz, int i,
+                                                  const float4& q4, const float4& t4) {
+  const Quat q{q4.w, q4.x, q4.y, q4.z};
+  const F3 p{xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2]};
+  const F3 r = Rotate(q, p);
+  const F3 t{r.x + t4.x, r.y + t4.y, r.z + t4.z};
+  const int3 c = CellIndex3(t, t4.w);
+  return make_int4(c.x, c.y, c.z, 0);
+}
+
+// grid (ceil(n / 256), scans of the whole batch): every scan rotates the one cloud of the batch's
+// node.
 __global__ void __launch_bounds__(256)
 Discretize3DKernel(const float* __restrict__ xyz, int n, const float4* __restrict__ pose_q,
                    const float4* __restrict__ pose_t, int4* __restrict__ cells) {
   const int s = blockIdx.y;
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
+  cells[static_cast<size_t>(s) * n + i] = DiscretizePoint3D(xyz, i, pose_q[s], pose_t[s]);
+}
+
+// One rotated scan of a batch whose pairs bring their own nodes: where its node's cloud lies and
+// where its cells go (its problem's `cells` + scan * n).
+struct Scan3D {
+  const float* xyz;
+  int4* cells;
+  int n, pad;
+};
+
+// The same for a batch of several nodes, in one launch: grid (scans of the whole batch, tiles of
+// 256 points of the largest cloud, at most 65535 -- a block strides over what is left).  The scan
+// is blockIdx.x, whose range does not bound the batch; its descriptor is uniform per block (scalar
+// loads).
+__global__ void __launch_bounds__(256)
+Discretize3DNodesKernel(const Scan3D* __restrict__ scans, const float4* __restrict__ pose_q,
+                        const float4* __restrict__ pose_t) {
+  const unsigned s = blockIdx.x;
+  const Scan3D scan = scans[s];
   const float4 q4 = pose_q[s];
   const float4 t4 = pose_t[s];
-  const Quat q{q4.w, q4.x, q4.y, q4.z};
-  const F3 p{xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2]};
-  const F3 r = Rotate(q, p);
-  const F3 t{r.x + t4.x, r.y + t4.y, r.z + t4.z};
-  const int3 c = CellIndex3(t, t4.w);
-  cells[static_cast<size_t>(s) * n + i] = make_int4(c.x, c.y, c.z, 0);
+  for (long long i = static_cast<long long>(blockIdx.y) * blockDim.x + threadIdx.x; i < scan.n;
+       i += static_cast<long long>(gridDim.y) * blockDim.x)
+    scan.cells[i] = DiscretizePoint3D(scan.xyz, static_cast<int>(i), q4, t4);
 }
 
 // ---------------------------------------------------------------------------
@@ -1258,6 +1288,47 @@ struct YawSweep {
   }
 };
 
+// A node's constant data with what GenerateDiscreteScans (:246-295) needs of it on the host, made
+// once per call and node (NodeOf3D); the searches of one node name the same object.
+struct NodeHost3D {
+  const cmx_node_data3d* data;
+  float max_point;                   // norm of the farthest high-resolution point
+  std::vector<float> scan_hist;
+  h3::Q g_inv;
+  mutable int cloud = -1;            // RunSearches3D: its clouds' slot in the chain being staged
+};
+
+// Norm of the farthest high-resolution point (does not throw: runs on the host pool for batches).
+float FarthestPoint3D(const cmx_node_data3d& data) {
+  const float* hi = data.high_resolution_point_cloud;
+  float max_point = 0.f;
+  for (int i = 0; i < data.num_high_resolution_points; ++i)
+    max_point = std::max(h3::Norm({hi[3 * i], hi[3 * i + 1], hi[3 * i + 2]}), max_point);
+  return max_point;
+}
+
+// Everything of a node but `max_point` (FarthestPoint3D).
+NodeHost3D NodeOf3D(const cmx_node_data3d& data) {
+  CMX_REQUIRE(data.high_resolution_point_cloud && data.num_high_resolution_points >= 1,
+              "empty high-resolution point cloud");
+  CMX_REQUIRE(data.low_resolution_point_cloud && data.num_low_resolution_points >= 1,
+              "empty low-resolution point cloud");
+  CMX_REQUIRE(data.histogram_size >= 0 &&
+                  (data.histogram_size == 0 || data.rotational_scan_matcher_histogram != nullptr),
+              "null histogram");
+  NodeHost3D node;
+  node.data = &data;
+  node.max_point = 0.f;
+  if (data.histogram_size > 0)
+    node.scan_hist.assign(data.rotational_scan_matcher_histogram,
+                          data.rotational_scan_matcher_histogram + data.histogram_size);
+  const double* g = data.gravity_alignment;   // w, x, y, z
+  const double n2 = (g[1] * g[1] + g[3] * g[3]) + (g[2] * g[2] + g[0] * g[0]);
+  node.g_inv = h3::Q{static_cast<float>(g[0] / n2), static_cast<float>(-g[1] / n2),
+                     static_cast<float>(-g[2] / n2), static_cast<float>(-g[3] / n2)};
+  return node;
+}
+
 // One (node, submap) search of a batch: MatchWithSearchParameters' arguments (:172-198).
 struct Search3D {
   const Fast3DMatcher* m;
@@ -1265,10 +1336,11 @@ struct Search3D {
   double angular_search_window;
   h3::Rigid node, submap;
   float min_score;
+  const NodeHost3D* data;
 };
 
-void Match3DMany(const Search3D* searches, int num, const cmx_node_data3d& data, int32_t* found,
-                 cmx_result3d* results, cmx_match_stats* stats);
+void Match3DMany(const Search3D* searches, int num, int32_t* found, cmx_result3d* results,
+                 cmx_match_stats* stats);
 
 // Host side of one search: the yaw pre-filter and the candidate lattice.
 struct Prepared3D {
@@ -1277,28 +1349,180 @@ struct Prepared3D {
   h3::V3 pose_t;
   int S = 0;
   long long ncx = 0, ncz = 0, per_scan = 0, total = 0;
-  size_t scan_base = 0, coarse_base = 0;
+  // within the chain of launches the search runs in (RunSearches3D)
+  size_t scan_base = 0, coarse_base = 0, cells_base = 0;
 };
 
 void Match3D(const Fast3DMatcher& m, int wxy, int wz, double angular_search_window,
              const h3::Rigid& node, const h3::Rigid& submap, const cmx_node_data3d& data,
              float min_score, int32_t* found, cmx_result3d* result, cmx_match_stats* stats) {
-  const Search3D one{&m, wxy, wz, angular_search_window, node, submap, min_score};
-  Match3DMany(&one, 1, data, found, result, stats);
+  NodeHost3D node_data = NodeOf3D(data);
+  node_data.max_point = FarthestPoint3D(data);
+  const Search3D one{&m, wxy, wz, angular_search_window, node, submap, min_score, &node_data};
+  Match3DMany(&one, 1, found, result, stats);
 }
 
-// `num` searches of one node's data in ONE chain of launches: every kernel takes the array of
-// problems (blockIdx.y, or the index its nodes carry), frontier and leaf lists are shared.  All
-// searches must live on the same device.  The rare cases that need a second look at one
-// search -- a frontier overflow, distinct leaves tied for the best score -- are repeated one
-// search at a time (num == 1 owns the overflow retry and the exact tie resolution).
-void Match3DMany(const Search3D* searches, int num, const cmx_node_data3d& data, int32_t* found,
-                 cmx_result3d* results, cmx_match_stats* stats) {
+void AddStats3D(const cmx_match_stats& st, cmx_match_stats* total) {
+  total->candidates_scored += st.candidates_scored; total->coarse_candidates += st.coarse_candidates;
+  total->nodes_expanded += st.nodes_expanded; total->num_scans += st.num_scans;
+  total->device_ms += st.device_ms; total->dominant_kernel_ms += st.dominant_kernel_ms;
+  total->expansion_ms += st.expansion_ms; total->expansion_nodes += st.expansion_nodes;
+  total->expansion_lookups += st.expansion_lookups;
+  total->expansion_launches += st.expansion_launches;
+}
+
+// The high-resolution cloud only ever feeds integer sums (ScoreCandidates), which do
+// not depend on the order of the points.  It goes up sorted along a Morton curve: the
+// 64 points a wavefront gathers together then fall into neighbouring voxels, i.e. into
+// a handful of cache lines instead of 64 (the search is bound by that line traffic).
+void SortAlongMortonCurve(const float* hi, int n, float inv_cell, float* out) {
+  float lo3[3] = {hi[0], hi[1], hi[2]};
+  for (int i = 1; i < n; ++i)
+    for (int k = 0; k < 3; ++k) lo3[k] = std::min(lo3[k], hi[3 * i + k]);
+  auto spread = [](uint32_t v) {   // 10 bits -> every third bit
+    v &= 0x3ffu;
+    v = (v | (v << 16)) & 0x030000ffu;
+    v = (v | (v << 8)) & 0x0300f00fu;
+    v = (v | (v << 4)) & 0x030c30c3u;
+    v = (v | (v << 2)) & 0x09249249u;
+    return v;
+  };
+  std::vector<uint64_t> order(n);
+  for (int i = 0; i < n; ++i) {
+    uint32_t key = 0;
+    for (int k = 0; k < 3; ++k) {
+      const float cell = (hi[3 * i + k] - lo3[k]) * inv_cell;
+      const uint32_t c = cell >= 1023.f ? 1023u : (cell > 0.f ? static_cast<uint32_t>(cell) : 0u);
+      key |= spread(c) << k;
+    }
+    order[i] = (static_cast<uint64_t>(key) << 32) | static_cast<uint32_t>(i);
+  }
+  std::sort(order.begin(), order.end());
+  for (int i = 0; i < n; ++i) {
+    const uint32_t src = static_cast<uint32_t>(order[i]);
+    out[3 * i] = hi[3 * src]; out[3 * i + 1] = hi[3 * src + 1]; out[3 * i + 2] = hi[3 * src + 2];
+  }
+}
+
+void RunSearches3D(const Search3D* searches, Prepared3D* prep, int num, int32_t* found,
+                   cmx_result3d* results, cmx_match_stats* stats);
+
+// `num` searches, each of its own node's data (Search3D::data; equal pointers = one node, whose
+// clouds go up once per chain of launches).  All searches must live on the same device.  The
+// searches run in ONE chain of launches (RunSearches3D) unless the index ranges say otherwise:
+// then in consecutive sub-batches that fit, one after the other, statistics summed.
+void Match3DMany(const Search3D* searches, int num, int32_t* found, cmx_result3d* results,
+                 cmx_match_stats* stats) {
   CMX_REQUIRE(searches && num >= 1 && found && results, "null output");
-  CMX_REQUIRE(data.high_resolution_point_cloud && data.num_high_resolution_points >= 1,
-              "empty high-resolution point cloud");
-  CMX_REQUIRE(data.low_resolution_point_cloud && data.num_low_resolution_points >= 1,
-              "empty low-resolution point cloud");
+  const int device = searches[0].m->device;
+  int min_depth = kMaxDepth;
+  for (int p = 0; p < num; ++p) {
+    const Fast3DMatcher& m = *searches[p].m;
+    CMX_REQUIRE(searches[p].data != nullptr, "null node data");
+    const cmx_node_data3d& data = *searches[p].data->data;
+    CMX_REQUIRE(m.device == device, "the searches of a batch must share a device");
+    CMX_REQUIRE(data.histogram_size == static_cast<int>(m.histogram.size()),
+                "histogram size %d does not match the submap's %d", data.histogram_size,
+                static_cast<int>(m.histogram.size()));
+    CMX_REQUIRE(searches[p].wxy >= 0 && searches[p].wz >= 0 && searches[p].wxy < (1 << 20) &&
+                    searches[p].wz < (1 << 20),
+                "bad search window");
+    min_depth = std::min(min_depth, m.options.branch_and_bound_depth);
+    found[p] = 0;
+  }
+  if (num > 1 && min_depth < 2) {     // depth-1 stacks take the leaf-verification path: one by one
+    cmx_match_stats total{};
+    for (int p = 0; p < num; ++p) {
+      cmx_match_stats st{};
+      Match3DMany(searches + p, 1, found + p, results + p, &st);
+      AddStats3D(st, &total);
+    }
+    if (stats) *stats = total;
+    return;
+  }
+
+  // GenerateDiscreteScans (:246-295), host part of every search.
+  std::vector<Prepared3D> prep(num);
+  for (int p = 0; p < num; ++p) {
+    const Search3D& q = searches[p];
+    const Fast3DMatcher& m = *q.m;
+    Prepared3D& pr = prep[p];
+    const NodeHost3D& node = *q.data;
+    const float max_scan_range = std::max(node.max_point, 3.f * m.resolution);
+    const float kSafetyMargin = 1.f - 1e-2f;
+    const float step =
+        kSafetyMargin * std::acos(1.f - (m.resolution * (m.resolution * 1.f)) /
+                                            (2.f * (max_scan_range * (max_scan_range * 1.f))));
+    const int angular_window_size = static_cast<int>(std::lround(q.angular_search_window / step));
+    CMX_REQUIRE(angular_window_size >= 0 && angular_window_size < (1 << 20), "bad angular window");
+    const h3::Rigid node_to_submap = h3::Mul(h3::InverseRigid(q.submap), q.node);
+    const float initial_angle = h3::GetYaw(h3::Mul(node_to_submap.q, node.g_inv));
+    YawSweep sweep(m.histogram, node.scan_hist);
+    for (int rz = -angular_window_size; rz <= angular_window_size; ++rz) {
+      const float angle = rz * step;
+      const float sc = sweep.Score(initial_angle + angle);
+      if (sc < m.options.min_rotational_score) continue;
+      pr.pose_q.push_back(h3::Mul(h3::Mul(h3::Inverse(q.submap.q),
+                                          h3::FromAngleAxisVector({0.f, 0.f, angle})),
+                                  q.node.q));
+      pr.rotational_score.push_back(sc);
+    }
+    pr.S = static_cast<int>(pr.pose_q.size());
+    pr.pose_t = node_to_submap.t;
+    // Lowest-resolution candidates (:297-330).
+    const int depth = m.options.branch_and_bound_depth;
+    const int step_cells = 1 << (depth - 1);
+    pr.ncx = (2ll * q.wxy + step_cells) / step_cells;
+    pr.ncz = (2ll * q.wz + step_cells) / step_cells;
+    pr.per_scan = pr.ncx * pr.ncx * pr.ncz;
+    pr.total = pr.per_scan * pr.S;
+    CMX_REQUIRE(pr.total < (1ll << 30), "search too large: %lld lowest-resolution candidates",
+                pr.total);
+    // GetPoseFromCandidate (:369-375): Translation(res * offset) * pose renormalises
+    // the rotation; Identity * q is exact, the normalisation is not.
+    pr.scan_q.resize(pr.S);
+    for (int s = 0; s < pr.S; ++s)
+      pr.scan_q[s] = h3::Normalized(h3::Mul(h3::Q{1.f, 0.f, 0.f, 0.f}, pr.pose_q[s]));
+  }
+
+  // Sub-batches: consecutive searches while the lowest-resolution candidates and the discretised
+  // cells (scans x points, summed) of a chain of launches stay below 2^31 -- its 32-bit index
+  // ranges.  A search that exceeds them alone is an error there ("batch too large").  The debug
+  // switch fast3d_chunk_cells lowers the cap on the cells (tests).
+  const size_t kIndexRange = size_t(1) << 31;
+  const size_t cell_cap = Debug().fast3d_chunk_cells > 0
+                              ? std::min(static_cast<size_t>(Debug().fast3d_chunk_cells), kIndexRange)
+                              : kIndexRange;
+  cmx_match_stats total{};
+  for (int first = 0; first < num;) {
+    size_t coarse = 0, cells = 0;
+    int end = first;
+    for (; end < num; ++end) {
+      const size_t pair_cells = static_cast<size_t>(prep[end].S) *
+                                searches[end].data->data->num_high_resolution_points;
+      if (end > first && (coarse + static_cast<size_t>(prep[end].total) >= kIndexRange ||
+                          cells + pair_cells >= cell_cap))
+        break;
+      coarse += static_cast<size_t>(prep[end].total);
+      cells += pair_cells;
+    }
+    cmx_match_stats st{};
+    RunSearches3D(searches + first, prep.data() + first, end - first, found + first,
+                  results + first, &st);
+    if (first == 0 && end == num) total = st;      // (one chain: its statistics as they are)
+    else AddStats3D(st, &total);
+    first = end;
+  }
+  if (stats) *stats = total;
+}
+
+// One chain of launches for `num` prepared searches: every kernel takes the array of problems
+// (blockIdx.y, or the index its nodes carry), frontier and leaf lists are shared.  The rare cases
+// that need a second look at one search -- a frontier overflow, distinct leaves tied for the best
+// score -- are repeated one search at a time (num == 1 owns the overflow retry and the exact tie
+// resolution).
+void RunSearches3D(const Search3D* searches, Prepared3D* prep, int num, int32_t* found,
+                   cmx_result3d* results, cmx_match_stats* stats) {
   // Debug switch host_trace: wall-clock of the host phases (tools only).
   const bool host_trace = Debug().host_trace != 0;
   auto t_last = std::chrono::steady_clock::now();
@@ -1312,108 +1536,50 @@ void Match3DMany(const Search3D* searches, int num, const cmx_node_data3d& data,
     host_report += buf;
     t_last = now;
   };
-  const int n = data.num_high_resolution_points, n_low = data.num_low_resolution_points;
-  const float* hi = data.high_resolution_point_cloud;
   const int device = searches[0].m->device;
-  int max_depth = 0, min_depth = kMaxDepth;
-  for (int p = 0; p < num; ++p) {
-    const Fast3DMatcher& m = *searches[p].m;
-    CMX_REQUIRE(m.device == device, "the searches of a batch must share a device");
-    CMX_REQUIRE(data.histogram_size == static_cast<int>(m.histogram.size()),
-                "histogram size %d does not match the submap's %d", data.histogram_size,
-                static_cast<int>(m.histogram.size()));
-    CMX_REQUIRE(searches[p].wxy >= 0 && searches[p].wz >= 0 && searches[p].wxy < (1 << 20) &&
-                    searches[p].wz < (1 << 20),
-                "bad search window");
-    max_depth = std::max(max_depth, m.options.branch_and_bound_depth);
-    min_depth = std::min(min_depth, m.options.branch_and_bound_depth);
-    found[p] = 0;
-  }
-  CMX_REQUIRE(data.histogram_size == 0 || data.rotational_scan_matcher_histogram != nullptr,
-              "null histogram");
-  if (num > 1 && min_depth < 2) {     // depth-1 stacks take the leaf-verification path: one by one
-    cmx_match_stats total{};
-    for (int p = 0; p < num; ++p) {
-      cmx_match_stats st{};
-      Match3DMany(searches + p, 1, data, found + p, results + p, &st);
-      total.candidates_scored += st.candidates_scored; total.coarse_candidates += st.coarse_candidates;
-      total.nodes_expanded += st.nodes_expanded; total.num_scans += st.num_scans;
-      total.device_ms += st.device_ms; total.dominant_kernel_ms += st.dominant_kernel_ms;
-      total.expansion_ms += st.expansion_ms; total.expansion_nodes += st.expansion_nodes;
-      total.expansion_lookups += st.expansion_lookups;
-      total.expansion_launches += st.expansion_launches;
-    }
-    if (stats) *stats = total;
-    return;
-  }
-
-  // GenerateDiscreteScans (:246-295), host part.
-  float max_point = 0.f;
-  for (int i = 0; i < n; ++i)
-    max_point = std::max(h3::Norm({hi[3 * i], hi[3 * i + 1], hi[3 * i + 2]}), max_point);
-  const std::vector<float> scan_hist(
-      data.rotational_scan_matcher_histogram,
-      data.rotational_scan_matcher_histogram + data.histogram_size);
-  const double* g = data.gravity_alignment;   // w, x, y, z
-  const double n2 = (g[1] * g[1] + g[3] * g[3]) + (g[2] * g[2] + g[0] * g[0]);
-  const h3::Q g_inv{static_cast<float>(g[0] / n2), static_cast<float>(-g[1] / n2),
-                    static_cast<float>(-g[2] / n2), static_cast<float>(-g[3] / n2)};
-  std::vector<Prepared3D> prep(num);
-  size_t scans_total = 0, coarse_total = 0;
+  // The distinct nodes of this chain, in the order their first search comes: each one's clouds
+  // are staged once.
+  struct Cloud3D {
+    const cmx_node_data3d* data;
+    float inv_cell;                 // Morton cell of the sort: its first search's
+    size_t hi_floats, low_floats;   // where its clouds lie in the upload (in floats)
+  };
+  std::vector<Cloud3D> clouds;
+  std::vector<int> cloud_of(num);
+  int max_depth = 0, max_n = 0;
+  bool same_n = true;
+  size_t scans_total = 0, coarse_total = 0, cells_total = 0;
   long long max_total = 0;
   cmx_match_stats st{};
   for (int p = 0; p < num; ++p) {
-    const Search3D& q = searches[p];
-    const Fast3DMatcher& m = *q.m;
-    Prepared3D& pr = prep[p];
-    const float max_scan_range = std::max(max_point, 3.f * m.resolution);
-    const float kSafetyMargin = 1.f - 1e-2f;
-    const float step =
-        kSafetyMargin * std::acos(1.f - (m.resolution * (m.resolution * 1.f)) /
-                                            (2.f * (max_scan_range * (max_scan_range * 1.f))));
-    const int angular_window_size = static_cast<int>(std::lround(q.angular_search_window / step));
-    CMX_REQUIRE(angular_window_size >= 0 && angular_window_size < (1 << 20), "bad angular window");
-    const h3::Rigid node_to_submap = h3::Mul(h3::InverseRigid(q.submap), q.node);
-    const float initial_angle = h3::GetYaw(h3::Mul(node_to_submap.q, g_inv));
-    YawSweep sweep(m.histogram, scan_hist);
-    for (int rz = -angular_window_size; rz <= angular_window_size; ++rz) {
-      const float angle = rz * step;
-      const float sc = sweep.Score(initial_angle + angle);
-      if (sc < m.options.min_rotational_score) continue;
-      pr.pose_q.push_back(h3::Mul(h3::Mul(h3::Inverse(q.submap.q),
-                                          h3::FromAngleAxisVector({0.f, 0.f, angle})),
-                                  q.node.q));
-      pr.rotational_score.push_back(sc);
+    const NodeHost3D& node = *searches[p].data;
+    const cmx_node_data3d* data = node.data;
+    if (node.cloud < 0) {
+      node.cloud = static_cast<int>(clouds.size());
+      clouds.push_back(Cloud3D{data, 1.f / (2.f * searches[p].m->resolution), 0, 0});
     }
-    pr.S = static_cast<int>(pr.pose_q.size());
-    pr.pose_t = node_to_submap.t;
-    st.num_scans += pr.S;
-    // Lowest-resolution candidates (:297-330).
-    const int depth = m.options.branch_and_bound_depth;
-    const int step_cells = 1 << (depth - 1);
-    pr.ncx = (2ll * q.wxy + step_cells) / step_cells;
-    pr.ncz = (2ll * q.wz + step_cells) / step_cells;
-    pr.per_scan = pr.ncx * pr.ncx * pr.ncz;
-    pr.total = pr.per_scan * pr.S;
-    CMX_REQUIRE(pr.total < (1ll << 30), "search too large: %lld lowest-resolution candidates",
-                pr.total);
+    cloud_of[p] = node.cloud;
+    Prepared3D& pr = prep[p];
     pr.scan_base = scans_total;
     pr.coarse_base = coarse_total;
+    pr.cells_base = cells_total;
     scans_total += pr.S;
     coarse_total += static_cast<size_t>(pr.total);
+    cells_total += static_cast<size_t>(pr.S) * data->num_high_resolution_points;
     max_total = std::max(max_total, pr.total);
-    // GetPoseFromCandidate (:369-375): Translation(res * offset) * pose renormalises
-    // the rotation; Identity * q is exact, the normalisation is not.
-    pr.scan_q.resize(pr.S);
-    for (int s = 0; s < pr.S; ++s)
-      pr.scan_q[s] = h3::Normalized(h3::Mul(h3::Q{1.f, 0.f, 0.f, 0.f}, pr.pose_q[s]));
+    st.num_scans += pr.S;
+    max_depth = std::max(max_depth, searches[p].m->options.branch_and_bound_depth);
+    max_n = std::max(max_n, data->num_high_resolution_points);
+    same_n &= data->num_high_resolution_points == clouds[0].data->num_high_resolution_points;
   }
+  for (int p = 0; p < num; ++p) searches[p].data->cloud = -1;   // (the next chain stages anew)
   if (scans_total == 0) {
     if (stats) *stats = st;
     return;
   }
-  CMX_REQUIRE(coarse_total < (size_t(1) << 31) && scans_total * n < (size_t(1) << 31),
+  CMX_REQUIRE(coarse_total < (size_t(1) << 31) && cells_total < (size_t(1) << 31),
               "batch too large");
+  const bool one_node = clouds.size() == 1;
 
   lap("prepare");
   WorkspaceLease ws(device);
@@ -1426,13 +1592,23 @@ void Match3DMany(const Search3D* searches, int num, const cmx_node_data3d& data,
     }
   }
   // Everything the call uploads lives in ONE device buffer with ONE pinned mirror, in the order
-  //   high-resolution cloud | low-resolution cloud | per-scan poses | misc (counters, problems, states)
+  //   high-resolution clouds | low-resolution clouds | per-scan poses | misc (counters, problems, states)
   // and goes up in one transfer (they were four copy kernels in a chain of launches that is
   // latency from end to end); the Best3 records behind `misc` are only ever written on the device.
   const auto align256 = [](size_t bytes) { return (bytes + 255) & ~size_t(255); };
-  const size_t up_low = align256(3 * sizeof(float) * static_cast<size_t>(n));
-  const size_t up_q = up_low + align256(3 * sizeof(float) * static_cast<size_t>(n_low));
-  const size_t up_misc = up_q + align256(3 * sizeof(float4) * scans_total);
+  size_t up_low = 0;
+  for (Cloud3D& c : clouds) {
+    c.hi_floats = up_low / sizeof(float);
+    up_low += align256(3 * sizeof(float) * static_cast<size_t>(c.data->num_high_resolution_points));
+  }
+  size_t up_q = up_low;
+  for (Cloud3D& c : clouds) {
+    c.low_floats = up_q / sizeof(float);
+    up_q += align256(3 * sizeof(float) * static_cast<size_t>(c.data->num_low_resolution_points));
+  }
+  // (several nodes: one Scan3D per scan behind the poses, for Discretize3DNodesKernel)
+  const size_t up_scans = up_q + align256(3 * sizeof(float4) * scans_total);
+  const size_t up_misc = up_scans + (one_node ? 0 : align256(sizeof(Scan3D) * scans_total));
   // [Counters3 | problems | per problem: best bits, seed count | Best3 per problem]
   const size_t off_problems = sizeof(Counters3);
   const size_t off_state = off_problems + sizeof(Fast3DProblem) * num;
@@ -1442,13 +1618,12 @@ void Match3DMany(const Search3D* searches, int num, const cmx_node_data3d& data,
   static_assert(sizeof(Best3) % sizeof(unsigned) == 0, "Best3 is copied by dwords");
   char* d_up = static_cast<char*>(ws->dev[0].Reserve(up_misc + misc_bytes));
   char* h_up = static_cast<char*>(ws->pinned[0].Reserve(up_misc + misc_bytes));
-  float* d_hi = reinterpret_cast<float*>(d_up);
-  float* d_low = reinterpret_cast<float*>(d_up + up_low);
+  float* d_xyz = reinterpret_cast<float*>(d_up);       // (clouds at Cloud3D::hi_floats, low_floats)
   // per scan: pose rotation | rotation of GetPoseFromCandidate | translation + resolution
   float4* d_pose_q = reinterpret_cast<float4*>(d_up + up_q);
   float4* d_scan_q = d_pose_q + scans_total;
   float4* d_pose_t = d_scan_q + scans_total;
-  int4* d_cells = ws->dev[3].ReserveAs<int4>(scans_total * n);
+  int4* d_cells = ws->dev[3].ReserveAs<int4>(cells_total);
   float* d_coarse = ws->dev[4].ReserveAs<float>(coarse_total);
   // The debug switch frontier_capacity shrinks the frontier buffers (tests only): overflow ->
   // strict retry.
@@ -1467,6 +1642,7 @@ void Match3DMany(const Search3D* searches, int num, const cmx_node_data3d& data,
   Best3* d_best = reinterpret_cast<Best3*>(d_misc + off_best);
 
   float4* h_q = reinterpret_cast<float4*>(h_up + up_q);
+  Scan3D* h_scans = reinterpret_cast<Scan3D*>(h_up + up_scans);
   char* h_misc = h_up + up_misc;
   Counters3* h_counters = reinterpret_cast<Counters3*>(h_misc);
   Fast3DProblem* h_problems = reinterpret_cast<Fast3DProblem*>(h_misc + off_problems);
@@ -1476,8 +1652,13 @@ void Match3DMany(const Search3D* searches, int num, const cmx_node_data3d& data,
     const Search3D& q = searches[p];
     const Fast3DMatcher& m = *q.m;
     const Prepared3D& pr = prep[p];
+    const Cloud3D& cloud = clouds[cloud_of[p]];
+    const int n = cloud.data->num_high_resolution_points;
     for (int s = 0; s < pr.S; ++s) {
       const size_t k = pr.scan_base + s;
+      if (!one_node)
+        h_scans[k] = Scan3D{d_xyz + cloud.hi_floats,
+                            d_cells + pr.cells_base + static_cast<size_t>(s) * n, n, 0};
       h_q[k] = make_float4(pr.pose_q[s].x, pr.pose_q[s].y, pr.pose_q[s].z, pr.pose_q[s].w);
       h_q[scans_total + k] =
           make_float4(pr.scan_q[s].x, pr.scan_q[s].y, pr.scan_q[s].z, pr.scan_q[s].w);
@@ -1495,9 +1676,9 @@ void Match3DMany(const Search3D* searches, int num, const cmx_node_data3d& data,
     P.low_resolution = m.low_resolution;
     P.resolution = m.resolution;
     P.wxy = q.wxy; P.wz = q.wz;
-    P.num_scans = pr.S; P.n = n; P.n_low = n_low;
-    P.cells = d_cells + pr.scan_base * n;
-    P.low_xyz = d_low;
+    P.num_scans = pr.S; P.n = n; P.n_low = cloud.data->num_low_resolution_points;
+    P.cells = d_cells + pr.cells_base;
+    P.low_xyz = d_xyz + cloud.low_floats;
     P.scan_q = d_scan_q + pr.scan_base;
     P.pose_tx = pr.pose_t.x; P.pose_ty = pr.pose_t.y; P.pose_tz = pr.pose_t.z;
     P.min_score = q.min_score;
@@ -1511,44 +1692,18 @@ void Match3DMany(const Search3D* searches, int num, const cmx_node_data3d& data,
     P.index = p;
     h_problems[p] = P;
   }
-  // The high-resolution cloud only ever feeds integer sums (ScoreCandidates), which do
-  // not depend on the order of the points.  Upload it sorted along a Morton curve: the
-  // 64 points a wavefront gathers together then fall into neighbouring voxels, i.e. into
-  // a handful of cache lines instead of 64 (the search is bound by that line traffic).
-  float* h_hi = reinterpret_cast<float*>(h_up);
-  {
-    float lo3[3] = {hi[0], hi[1], hi[2]};
-    for (int i = 1; i < n; ++i)
-      for (int k = 0; k < 3; ++k) lo3[k] = std::min(lo3[k], hi[3 * i + k]);
-    const float inv_cell = 1.f / (2.f * searches[0].m->resolution);
-    auto spread = [](uint32_t v) {   // 10 bits -> every third bit
-      v &= 0x3ffu;
-      v = (v | (v << 16)) & 0x030000ffu;
-      v = (v | (v << 8)) & 0x0300f00fu;
-      v = (v | (v << 4)) & 0x030c30c3u;
-      v = (v | (v << 2)) & 0x09249249u;
-      return v;
-    };
-    std::vector<uint64_t> order(n);
-    for (int i = 0; i < n; ++i) {
-      uint32_t key = 0;
-      for (int k = 0; k < 3; ++k) {
-        const float cell = (hi[3 * i + k] - lo3[k]) * inv_cell;
-        const uint32_t c = cell >= 1023.f ? 1023u : (cell > 0.f ? static_cast<uint32_t>(cell) : 0u);
-        key |= spread(c) << k;
-      }
-      order[i] = (static_cast<uint64_t>(key) << 32) | static_cast<uint32_t>(i);
-    }
-    std::sort(order.begin(), order.end());
-    for (int i = 0; i < n; ++i) {
-      const uint32_t src = static_cast<uint32_t>(order[i]);
-      h_hi[3 * i] = hi[3 * src]; h_hi[3 * i + 1] = hi[3 * src + 1]; h_hi[3 * i + 2] = hi[3 * src + 2];
-    }
-  }
-  // One upload from the pinned mirror (the caller's low-resolution cloud is copied there
-  // first): a copy kernel while it is small (cmx_common.h: SmallCopyAsync).
-  float* h_low = reinterpret_cast<float*>(h_up + up_low);
-  std::memcpy(h_low, data.low_resolution_point_cloud, 3 * sizeof(float) * n_low);
+  // The clouds into the pinned mirror (the high-resolution ones sorted, the low-resolution ones
+  // as they are), then one upload: a copy kernel while it is small (cmx_common.h: SmallCopyAsync).
+  float* h_xyz = reinterpret_cast<float*>(h_up);
+  // (a sort is ~30 ns per point, serial host time that exceeds the device time of a batch of many
+  // nodes: several clouds are sorted on the host pool)
+  ParallelFor(static_cast<int>(clouds.size()), 3, [&](int k) {
+    const Cloud3D& c = clouds[k];
+    SortAlongMortonCurve(c.data->high_resolution_point_cloud, c.data->num_high_resolution_points,
+                         c.inv_cell, h_xyz + c.hi_floats);
+    std::memcpy(h_xyz + c.low_floats, c.data->low_resolution_point_cloud,
+                3 * sizeof(float) * c.data->num_low_resolution_points);
+  });
   SmallCopyAsync(d_up, h_up, up_misc + off_best, true, ws->stream);
 
   auto front = [&](int stage) {
@@ -1568,8 +1723,14 @@ void Match3DMany(const Search3D* searches, int num, const cmx_node_data3d& data,
   auto mark = [&](const char* name) { trace.Mark(name); };
   mark("begin");
   RecordEvent(ws->ev_begin, ws->stream);
-  Discretize3DKernel<<<dim3(DivUp(n, 256), static_cast<unsigned>(scans_total)), 256, 0,
-                       ws->stream>>>(d_hi, n, d_pose_q, d_pose_t, d_cells);
+  if (one_node)
+    Discretize3DKernel<<<dim3(DivUp(max_n, 256), static_cast<unsigned>(scans_total)), 256, 0,
+                         ws->stream>>>(d_xyz, max_n, d_pose_q, d_pose_t, d_cells);
+  else
+    Discretize3DNodesKernel<<<dim3(static_cast<unsigned>(scans_total),
+                                   std::min<unsigned>(DivUp(max_n, 256), 65535u)),
+                              256, 0, ws->stream>>>(
+        reinterpret_cast<const Scan3D*>(d_up + up_scans), d_pose_q, d_pose_t);
   dbg("discretize");
   mark("discretize");
   RecordEvent(ws->ev_k0, ws->stream);
@@ -1650,7 +1811,9 @@ void Match3DMany(const Search3D* searches, int num, const cmx_node_data3d& data,
     if (!strict) {
       // (the nodes the expansion kernel took off its lists and found at or above the bound)
       for (int k = 0; k < 16; ++k) st.expansion_nodes += static_cast<int64_t>(h_counters->expanded[k]);
-      st.expansion_lookups = st.expansion_nodes * (static_cast<int64_t>(n + 63) / 64 * 64);
+      // (per wave-wide gather: 64; searches of unlike clouds share the counters -- not reported)
+      st.expansion_lookups =
+          same_n ? st.expansion_nodes * (static_cast<int64_t>(max_n + 63) / 64 * 64) : 0;
     }
     if (!h_counters->overflow || num > 1) break;
     // Something was dropped.  Retry pruning ties (strict) with the bound lowered by one
@@ -1690,7 +1853,7 @@ void Match3DMany(const Search3D* searches, int num, const cmx_node_data3d& data,
     // The shared lists dropped nodes: every search again on its own (num == 1 owns the retry).
     for (int p = 0; p < num; ++p) {
       cmx_match_stats again{};
-      Match3DMany(searches + p, 1, data, found + p, results + p, &again);
+      Match3DMany(searches + p, 1, found + p, results + p, &again);
       st.candidates_scored += again.candidates_scored;
       st.nodes_expanded += again.nodes_expanded;
       st.device_ms += again.device_ms;
@@ -1794,7 +1957,7 @@ void Match3DMany(const Search3D* searches, int num, const cmx_node_data3d& data,
     }
   }
   lap("results");
-  if (host_trace) fprintf(stderr, "[cmx host] Match3DMany(%d):%s us\n", num, host_report.c_str());
+  if (host_trace) fprintf(stderr, "[cmx host] RunSearches3D(%d):%s us\n", num, host_report.c_str());
 }
 
 // CHECKs of PrecomputationGridStack3D (:60-61).
@@ -1879,6 +2042,79 @@ void Fast3DGrids(const cmx_fast3d* matcher, Brick* high, float* resolution, Bric
   *low = matcher->impl.low.desc;
   *low_resolution = matcher->impl.low_resolution;
 }
+
+namespace {
+// Match (:127-146) / MatchFullSubmap (:148-170) arguments of every pair, then one chain of
+// launches per device and `group` pairs (Match3DMany).  matchers[p] and datas[p] are not null.
+void MatchPairs3D(const cmx_fast3d* const* matchers, int num_pairs, const cmx_pose3d* node_poses,
+                  const cmx_pose3d* submap_poses, const int32_t* match_full_submap,
+                  const float* min_scores, const cmx_node_data3d* const* datas, int32_t* found,
+                  cmx_result3d* results, cmx_match_stats* stats) {
+  // The distinct nodes of the call (equal pointers = one node), each prepared once.
+  std::vector<NodeHost3D> nodes;
+  nodes.reserve(num_pairs);                              // (searches keep pointers into it)
+  std::unordered_map<const cmx_node_data3d*, const NodeHost3D*> node_of;
+  for (int p = 0; p < num_pairs; ++p) {
+    if (node_of.count(datas[p])) continue;
+    nodes.push_back(NodeOf3D(*datas[p]));
+    node_of[datas[p]] = &nodes.back();
+  }
+  ParallelFor(static_cast<int>(nodes.size()), 3,
+              [&](int k) { nodes[k].max_point = FarthestPoint3D(*nodes[k].data); });
+  std::vector<Search3D> searches(num_pairs);
+  for (int p = 0; p < num_pairs; ++p) {
+    const Fast3DMatcher& m = matchers[p]->impl;
+    Search3D& q = searches[p];
+    q.m = &m;
+    q.min_score = min_scores[p];
+    q.data = node_of[datas[p]];
+    if (match_full_submap[p]) {
+      // (MatchFullSubmap's window reaches as far as the node's farthest point)
+      const int window = (m.width_in_voxels + 1) / 2 +
+                         static_cast<int>(std::lround(q.data->max_point / m.resolution + 0.5f));
+      q.wxy = q.wz = window;
+      q.angular_search_window = M_PI;
+      q.node.q = {static_cast<float>(node_poses[p].q[0]), static_cast<float>(node_poses[p].q[1]),
+                  static_cast<float>(node_poses[p].q[2]), static_cast<float>(node_poses[p].q[3])};
+      q.submap.q = {static_cast<float>(submap_poses[p].q[0]),
+                    static_cast<float>(submap_poses[p].q[1]),
+                    static_cast<float>(submap_poses[p].q[2]),
+                    static_cast<float>(submap_poses[p].q[3])};
+    } else {
+      q.wxy = static_cast<int>(std::lround(m.options.linear_xy_search_window / m.resolution));
+      q.wz = static_cast<int>(std::lround(m.options.linear_z_search_window / m.resolution));
+      q.angular_search_window = m.options.angular_search_window;
+      q.node = h3::FromPose(node_poses[p]);
+      q.submap = h3::FromPose(submap_poses[p]);
+    }
+  }
+  // The debug switch fast3d_batch caps the searches per chain (tools / tests; 1 = one by one).
+  const int group = Debug().fast3d_batch > 0 ? Debug().fast3d_batch : 64;
+  cmx_match_stats total{};
+  std::vector<char> done(num_pairs, 0);
+  for (int first = 0; first < num_pairs; ++first) {
+    if (done[first]) continue;
+    // the not yet searched pairs on this pair's device, `group` at a time
+    std::vector<int> idx;
+    for (int p = first; p < num_pairs && static_cast<int>(idx.size()) < group; ++p)
+      if (!done[p] && searches[p].m->device == searches[first].m->device) idx.push_back(p);
+    std::vector<Search3D> part(idx.size());
+    std::vector<int32_t> part_found(idx.size(), 0);
+    std::vector<cmx_result3d> part_results(idx.size());
+    for (size_t k = 0; k < idx.size(); ++k) part[k] = searches[idx[k]];
+    cmx_match_stats st{};
+    Match3DMany(part.data(), static_cast<int>(part.size()), part_found.data(),
+                part_results.data(), &st);
+    for (size_t k = 0; k < idx.size(); ++k) {
+      done[idx[k]] = 1;
+      found[idx[k]] = part_found[k];
+      if (part_found[k]) results[idx[k]] = part_results[k];
+    }
+    AddStats3D(st, &total);
+  }
+  if (stats) *stats = total;
+}
+}  // namespace
 }  // namespace cmx
 
 extern "C" {
@@ -2084,78 +2320,45 @@ cmx_status cmx_fast3d_match_batch(const cmx_fast3d* const* matchers, int32_t num
                 "null argument");
     for (int p = 0; p < num_pairs; ++p) CMX_REQUIRE(matchers[p] != nullptr, "null matcher handle");
     const auto entry_time = std::chrono::steady_clock::now();
-    // Match (:127-146) / MatchFullSubmap (:148-170) arguments of every pair, then one chain of
-    // launches per device (Match3DMany).
-    CMX_REQUIRE(data->high_resolution_point_cloud && data->num_high_resolution_points >= 1,
-                "empty high-resolution point cloud");
-    float max_point_distance = 0.f;
-    for (int i = 0; i < data->num_high_resolution_points; ++i) {
-      const float* p = data->high_resolution_point_cloud + 3 * i;
-      max_point_distance = std::max(max_point_distance, h3::Norm({p[0], p[1], p[2]}));
-    }
-    std::vector<Search3D> searches(num_pairs);
-    for (int p = 0; p < num_pairs; ++p) {
-      const Fast3DMatcher& m = matchers[p]->impl;
-      Search3D& q = searches[p];
-      q.m = &m;
-      q.min_score = min_scores[p];
-      if (match_full_submap[p]) {
-        const int window = (m.width_in_voxels + 1) / 2 +
-                           static_cast<int>(std::lround(max_point_distance / m.resolution + 0.5f));
-        q.wxy = q.wz = window;
-        q.angular_search_window = M_PI;
-        q.node.q = {static_cast<float>(node_poses[p].q[0]), static_cast<float>(node_poses[p].q[1]),
-                    static_cast<float>(node_poses[p].q[2]), static_cast<float>(node_poses[p].q[3])};
-        q.submap.q = {static_cast<float>(submap_poses[p].q[0]),
-                      static_cast<float>(submap_poses[p].q[1]),
-                      static_cast<float>(submap_poses[p].q[2]),
-                      static_cast<float>(submap_poses[p].q[3])};
-      } else {
-        q.wxy = static_cast<int>(std::lround(m.options.linear_xy_search_window / m.resolution));
-        q.wz = static_cast<int>(std::lround(m.options.linear_z_search_window / m.resolution));
-        q.angular_search_window = m.options.angular_search_window;
-        q.node = h3::FromPose(node_poses[p]);
-        q.submap = h3::FromPose(submap_poses[p]);
-      }
-    }
-    // The debug switch fast3d_batch caps the searches per chain (tools / tests; 1 = one by one).
-    const int group = Debug().fast3d_batch > 0 ? Debug().fast3d_batch : 64;
-    cmx_match_stats total{};
-    std::vector<char> done(num_pairs, 0);
-    for (int first = 0; first < num_pairs; ++first) {
-      if (done[first]) continue;
-      // the not yet searched pairs on this pair's device, `group` at a time
-      std::vector<int> idx;
-      for (int p = first; p < num_pairs && static_cast<int>(idx.size()) < group; ++p)
-        if (!done[p] && searches[p].m->device == searches[first].m->device) idx.push_back(p);
-      std::vector<Search3D> part(idx.size());
-      std::vector<int32_t> part_found(idx.size(), 0);
-      std::vector<cmx_result3d> part_results(idx.size());
-      for (size_t k = 0; k < idx.size(); ++k) part[k] = searches[idx[k]];
-      cmx_match_stats st{};
-      Match3DMany(part.data(), static_cast<int>(part.size()), *data, part_found.data(),
-                  part_results.data(), &st);
-      for (size_t k = 0; k < idx.size(); ++k) {
-        done[idx[k]] = 1;
-        found[idx[k]] = part_found[k];
-        if (part_found[k]) results[idx[k]] = part_results[k];
-      }
-      total.candidates_scored += st.candidates_scored;
-      total.coarse_candidates += st.coarse_candidates;
-      total.nodes_expanded += st.nodes_expanded;
-      total.num_scans += st.num_scans;
-      total.device_ms += st.device_ms;
-      total.dominant_kernel_ms += st.dominant_kernel_ms;
-      total.expansion_ms += st.expansion_ms;
-      total.expansion_nodes += st.expansion_nodes;
-      total.expansion_lookups += st.expansion_lookups;
-      total.expansion_launches += st.expansion_launches;
-    }
-    if (stats) *stats = total;
+    // The case "all pairs share one data" of MatchPairs3D.
+    const std::vector<const cmx_node_data3d*> datas(num_pairs, data);
+    MatchPairs3D(matchers, num_pairs, node_poses, submap_poses, match_full_submap, min_scores,
+                 datas.data(), found, results, stats);
     if (Debug().host_trace)
       fprintf(stderr, "[cmx host] cmx_fast3d_match_batch(%d): %.0f us\n", num_pairs,
               std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() -
                                                         entry_time).count());
+  });
+}
+
+// The other half of PoseGraph3D::ComputeConstraintsForNode (pose_graph_3d.cc:370-379): a
+// finished submap against every old node, or any list of (node, submap) pairs -- pair p with
+// its own data[p].  One chain of launches as above; a node named by several pairs is staged once.
+cmx_status cmx_fast3d_match_pairs(const cmx_fast3d* const* matchers, int32_t num_pairs,
+                                  const cmx_pose3d* node_poses, const cmx_pose3d* submap_poses,
+                                  const int32_t* match_full_submap, const float* min_scores,
+                                  const cmx_node_data3d* const* data, int32_t* found,
+                                  cmx_result3d* results, cmx_match_stats* stats) {
+  using namespace cmx;
+  return Guard([&] {
+    // (a matcher handle cannot exist without a device: say so, whatever the arguments are)
+    if (cmx_device_count() <= 0) UseDevice(0);
+    CMX_REQUIRE(num_pairs >= 1, "num_pairs must be at least 1");
+    CMX_REQUIRE(matchers && node_poses && submap_poses && match_full_submap && min_scores &&
+                    data && found && results,
+                "null argument");
+    for (int p = 0; p < num_pairs; ++p) {
+      CMX_REQUIRE(matchers[p] != nullptr, "null matcher handle");
+      CMX_REQUIRE(data[p] != nullptr, "the node data of pair %d is null", p);
+      CMX_REQUIRE(matchers[p]->impl.device == matchers[0]->impl.device,
+                  "the matchers of a call must live on one device (pair %d)", p);
+      CMX_REQUIRE(data[p]->histogram_size == static_cast<int>(matchers[p]->impl.histogram.size()),
+                  "histogram size %d of pair %d does not match its submap's %d",
+                  data[p]->histogram_size, p,
+                  static_cast<int>(matchers[p]->impl.histogram.size()));
+    }
+    MatchPairs3D(matchers, num_pairs, node_poses, submap_poses, match_full_submap, min_scores,
+                 data, found, results, stats);
   });
 }
 

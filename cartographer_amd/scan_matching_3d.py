@@ -211,6 +211,36 @@ class CeresScanMatcher3D:
             C.byref(data), C.cast(poses_out, C.c_void_p), C.cast(summaries, C.c_void_p)))
         return [Rigid3d.from_c(p) for p in poses_out], [s.as_dict() for s in summaries]
 
+    def refine_pairs(self, matchers, found, pose_estimates, constant_datas):
+        """``refine_batch`` for pairs that bring their own nodes (the results of
+        ``fast3d_match_pairs``): entry i is refined with the clouds of ``constant_datas[i]``, one
+        launch.  Entries that are the same ``TrajectoryNodeData`` object are staged once."""
+        num = len(matchers)
+        assert self.options.num_pairs == 2 and len(constant_datas) == num
+        handles = (C.c_void_p * num)(*[m._h for m in matchers])
+        found = np.ascontiguousarray([1 if f else 0 for f in found], np.int32)
+        poses_in = (Pose3d * num)(*[p.to_c() for p in pose_estimates])
+        poses_out = (Pose3d * num)()
+        summaries = (CeresSummary * num)()
+        pointers, keep = _node_data_pointers(constant_datas)
+        check(_lib.lib().cmx_fast3d_refine_pairs(
+            C.byref(self.options), handles, num, found.ctypes.data, C.cast(poses_in, C.c_void_p),
+            pointers, C.cast(poses_out, C.c_void_p), C.cast(summaries, C.c_void_p)))
+        del keep
+        return [Rigid3d.from_c(p) for p in poses_out], [s.as_dict() for s in summaries]
+
+
+def _node_data_pointers(constant_datas):
+    """``const cmx_node_data3d* const*`` for a list of ``TrajectoryNodeData``: one C record per
+    distinct object, so that pairs of one node name one pointer.  Returns (array, records)."""
+    records = {}
+    for data in constant_datas:
+        if id(data) not in records:
+            records[id(data)] = data.to_c()
+    pointers = (C.POINTER(NodeData3D) * len(constant_datas))(
+        *[C.pointer(records[id(data)]) for data in constant_datas])
+    return pointers, records
+
 
 @dataclass
 class TrajectoryNodeData:
@@ -357,6 +387,43 @@ def fast3d_match_batch(matchers, node_poses, submap_poses, match_full_submap, mi
         handles, num, C.cast(nodes, C.c_void_p), C.cast(submaps, C.c_void_p), full.ctypes.data,
         thresholds.ctypes.data, C.byref(data), found.ctypes.data, C.cast(results, C.c_void_p),
         C.byref(stats)))
+    out = []
+    for p in range(num):
+        if not found[p]:
+            out.append(None)
+            continue
+        r = results[p]
+        out.append(dict(score=float(r.score), pose_estimate=Rigid3d.from_c(r.pose_estimate),
+                        rotational_score=float(r.rotational_score),
+                        low_resolution_score=float(r.low_resolution_score)))
+    return out, stats.as_dict()
+
+
+def fast3d_match_pairs(matchers, node_poses, submap_poses, match_full_submap, min_scores,
+                       constant_datas):
+    """Many nodes against submaps' matchers in one call (``cmx_fast3d_match_pairs``): the burst of
+    ``PoseGraph3D::ComputeConstraintsForNode`` when a submap finishes
+    (``mapping/internal/3d/pose_graph_3d.cc:370-379``), or several trajectories' nodes against a
+    shared set of submaps.  Pair p is ``constant_datas[p]`` against ``matchers[p]``; entries that
+    are the same ``TrajectoryNodeData`` object are one node, uploaded once.  Everything else as
+    ``fast3d_match_batch``; all matchers live on one device.
+    """
+    num = len(matchers)
+    handles = (C.c_void_p * num)(*[m._h for m in matchers])
+    nodes = (Pose3d * num)(*[p.to_c() for p in node_poses])
+    submaps = (Pose3d * num)(*[p.to_c() for p in submap_poses])
+    full = np.ascontiguousarray([1 if f else 0 for f in match_full_submap], np.int32)
+    thresholds = np.ascontiguousarray(min_scores, np.float32)
+    assert full.shape[0] == num and thresholds.shape[0] == num and len(constant_datas) == num
+    pointers, keep = _node_data_pointers(constant_datas)
+    found = np.zeros(num, np.int32)
+    results = (Result3D * num)()
+    stats = MatchStats()
+    check(_lib.lib().cmx_fast3d_match_pairs(
+        handles, num, C.cast(nodes, C.c_void_p), C.cast(submaps, C.c_void_p), full.ctypes.data,
+        thresholds.ctypes.data, pointers, found.ctypes.data, C.cast(results, C.c_void_p),
+        C.byref(stats)))
+    del keep
     out = []
     for p in range(num):
         if not found[p]:

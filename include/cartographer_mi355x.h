@@ -22,7 +22,7 @@
  *                                  the same method on a TSDF2D (.cc:83-90, the GridType::TSDF case)
  *   cmx_ceres2d_tsdf_residuals     TSDFMatchCostFunction2D::Evaluate,
  *                                  SM2/tsdf_match_cost_function_2d.cc:40-66
- *   cmx_ceres3d_match, cmx_fast3d_refine_batch
+ *   cmx_ceres3d_match, cmx_fast3d_refine_batch, cmx_fast3d_refine_pairs
  *                                  CeresScanMatcher3D::Match, SM3/ceres_scan_matcher_3d.cc:90-156
  *   cmx_rt3d_match                 RealTimeCorrelativeScanMatcher3D::Match
  *                                  SM3/real_time_correlative_scan_matcher_3d.h:47-50, .cc:34-53
@@ -704,6 +704,28 @@ cmx_status cmx_fast3d_match_batch(const cmx_fast3d* const* matchers, int32_t num
                                   const int32_t* match_full_submap, const float* min_scores,
                                   const cmx_node_data3d* data, int32_t* found,
                                   cmx_result3d* results, cmx_match_stats* stats);
+/* The other half of PoseGraph3D::ComputeConstraintsForNode (mapping/internal/3d/
+ * pose_graph_3d.cc:370-379: when a submap finishes, every old node is matched against it), and
+ * any other list of (node, submap) pairs: as cmx_fast3d_match_batch, but pair p brings its own
+ * data[p] -- clouds, histogram and gravity alignment.  found[p] / results[p] are bit for bit
+ * what cmx_fast3d_match (cmx_fast3d_match_full_submap where match_full_submap[p] != 0) returns
+ * for (matchers[p], data[p], node_poses[p], submap_poses[p], min_scores[p]).  Entries of `data`
+ * may repeat: equal pointers mean the same node, whose clouds go to the device once per chain
+ * of launches.  All matchers must live on one device; data[p]'s histogram size is checked
+ * against matchers[p]'s; num_pairs >= 1.  A list whose lowest-resolution candidates or rotated
+ * points (scans x points, summed) reach 2^31 runs as consecutive sub-batches that fit, one
+ * after the other (so does cmx_fast3d_match_batch); a single pair that large is
+ * CMX_INVALID_ARGUMENT.  The size of the scratch memory is no criterion of that split: a chain
+ * of launches asks the device for 16 bytes per rotated point, and a list that the device cannot
+ * hold fails with CMX_DEVICE_ERROR -- pass it in parts.  Without a HIP device the call is
+ * CMX_DEVICE_ERROR whatever its arguments are (no matcher can exist then).  *stats summed; stats->expansion_lookups is 0 for a chain of launches
+ * whose pairs differ in their number of high-resolution points (the expansion counters are
+ * shared by its pairs). */
+cmx_status cmx_fast3d_match_pairs(const cmx_fast3d* const* matchers, int32_t num_pairs,
+                                  const cmx_pose3d* node_poses, const cmx_pose3d* submap_poses,
+                                  const int32_t* match_full_submap, const float* min_scores,
+                                  const cmx_node_data3d* const* data, /* one per pair */
+                                  int32_t* found, cmx_result3d* results, cmx_match_stats* stats);
 /* ConstraintBuilder3D::ComputeConstraint's refinement (constraints/constraint_builder_3d.cc:
  * 263-276) for the results of cmx_fast3d_match_batch: pair i runs CeresScanMatcher3D::Match
  * (target translation = pose_estimates_in[i].t, initial pose = pose_estimates_in[i]) with
@@ -716,6 +738,16 @@ cmx_status cmx_fast3d_refine_batch(const cmx_ceres3d_options* options,
                                    const int32_t* found, const cmx_pose3d* pose_estimates_in,
                                    const cmx_node_data3d* data, cmx_pose3d* pose_estimates_out,
                                    cmx_ceres_summary* summaries);
+/* The same for the results of cmx_fast3d_match_pairs (pose_graph_3d.cc:370-379): pair i is
+ * refined with the clouds of data[i], bit for bit what cmx_fast3d_refine_batch returns for that
+ * pair alone.  Equal pointers in `data` mean the same node, staged once; one launch per device,
+ * one workgroup per pair; num_pairs >= 1 and no entry of `data` may be NULL.  Without a HIP
+ * device the call is CMX_DEVICE_ERROR whatever its arguments are. */
+cmx_status cmx_fast3d_refine_pairs(const cmx_ceres3d_options* options,
+                                   const cmx_fast3d* const* matchers, int32_t num_pairs,
+                                   const int32_t* found, const cmx_pose3d* pose_estimates_in,
+                                   const cmx_node_data3d* const* data,
+                                   cmx_pose3d* pose_estimates_out, cmx_ceres_summary* summaries);
 
 /* ---- upstream point preparation ---------------------------------------- */
 /* sensor::VoxelFilter(PointCloud, resolution) (sensor/internal/voxel_filter.cc:88-152): one
