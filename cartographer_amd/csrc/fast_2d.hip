@@ -133,15 +133,19 @@ struct SeedScratch {
   int hist[1024];
   int wave_total[4];
   int threshold_bin;
-  int found_scan;
+  int found_scan[4];
   int total;
 };
 
-__device__ __forceinline__ bool PickSeed(const Fast2DProblem& P, int n, int want,
-                                         SeedScratch* sh, int* scan_out) {
+// Seeds want0 .. want0 + wants - 1 (wants <= 4) into sh->found_scan[], -1 where there is no such
+// seed.  The numbering depends on the size of the workgroup: every dive kernel calls this with
+// 256 threads, so that they all start from the same seeds.
+__device__ __forceinline__ void PickSeeds(const Fast2DProblem& P, int n, int want0, int wants,
+                                          SeedScratch* sh) {
   const int tid = threadIdx.x, lane = tid & 63, T = blockDim.x;
   for (int i = tid; i < 1024; i += T) sh->hist[i] = 0;
-  if (tid == 0) { sh->found_scan = -1; sh->total = 0; }
+  if (tid < 4) sh->found_scan[tid] = -1;
+  if (tid == 0) sh->total = 0;
   __syncthreads();
   const int S = P.num_scans;
   const long long range = 255ll * n + 1;
@@ -175,7 +179,7 @@ __device__ __forceinline__ bool PickSeed(const Fast2DProblem& P, int n, int want
     const int b = best_of(s);
     if (b >= 0) atomicAdd(&sh->hist[static_cast<int>(b * 1024ll / range)], 1);
   }
-  if (want == 0) {
+  if (want0 == 0) {
     for (int s = tid; s < S; s += T) total += coarse_dims[s].x * coarse_dims[s].y;
     total = WaveSum(total);
     if (lane == 0 && total) atomicAdd(&sh->total, total);
@@ -232,25 +236,30 @@ __device__ __forceinline__ bool PickSeed(const Fast2DProblem& P, int n, int want
   __syncthreads();
   int before = incl - count;
   for (int w = 0; w < (tid >> 6); ++w) before += sh->wave_total[w];
-  if (want >= before && want < before + count) {
-    int k = before, found = -1;
+  const int want_end = want0 + wants;
+  if (want0 < before + count && want_end > before) {
+    int k = before;
 #pragma unroll
     for (int j = 0; j < kOwn; ++j) {
-      if (found < 0 && qualifies(own[j])) {
-        if (k == want) found = tid + j * T;
+      if (qualifies(own[j])) {
+        if (k >= want0 && k < want_end) sh->found_scan[k - want0] = tid + j * T;
         ++k;
       }
     }
-    for (int s = tid + kOwn * T; s < S && found < 0; s += T) {
+    for (int s = tid + kOwn * T; s < S && k < want_end; s += T) {
       if (!qualifies(best_of(s))) continue;
-      if (k == want) found = s;
+      if (k >= want0) sh->found_scan[k - want0] = s;
       ++k;
     }
-    sh->found_scan = found;
   }
   __syncthreads();
-  *scan_out = sh->found_scan;
-  return sh->found_scan >= 0;
+}
+
+__device__ __forceinline__ bool PickSeed(const Fast2DProblem& P, int n, int want,
+                                         SeedScratch* sh, int* scan_out) {
+  PickSeeds(P, n, want, 1, sh);
+  *scan_out = sh->found_scan[0];
+  return sh->found_scan[0] >= 0;
 }
 
 // Problem- and scan-invariant data a block keeps on chip while it works on
@@ -1288,6 +1297,197 @@ __device__ __forceinline__ bool Steal(const TreeQueue& Q, Counters* __restrict__
 constexpr int kChainCells = 16;     // cells per lane held in registers: clouds of up to 1024 points
 constexpr uint32_t kNoCell = 0x80008000u;   // (x, y) = (-32768, -32768): outside every level
 
+// ---- what a wavefront that walks a chain of nodes of ONE scan does per scan and per expansion
+// (TreeQueueKernel's chains and DiveWaveKernel's dives) ------------------------------------------
+// The scan's cells, point j * 64 + lane in cell[j]: stored (`discrete`) or re-derived (ScanCell).
+template <bool kRecompute>
+__device__ __forceinline__ void LoadChainCells(const Fast2DProblem& P, int n, int scan,
+                                               uint32_t (&cell)[kChainCells]) {
+  const int lane = threadIdx.x & 63;
+  const auto* pts = AsGlobal(P.discrete) + static_cast<size_t>(scan) * n;
+  if constexpr (kRecompute) {
+    // ScanCell is some hundred instructions with its exact fall-back: ONE copy of it in a loop
+    // that is not unrolled, its result put into its register by selects on the (uniform) index.
+    const float2 rot = P.scan_rot[scan];
+#pragma unroll
+    for (int u = 0; u < kChainCells; ++u) cell[u] = kNoCell;
+#pragma unroll 1
+    for (int j = 0; j * kWave < n; ++j) {
+      const int i = j * kWave + lane;
+      const uint32_t c = i < n ? ScanCell(P, rot, i) : kNoCell;
+#pragma unroll
+      for (int u = 0; u < kChainCells; ++u) cell[u] = u == j ? c : cell[u];
+    }
+  } else {
+#pragma unroll
+    for (int j = 0; j < kChainCells; ++j) {
+      const int i = j * kWave + lane;
+      cell[j] = kNoCell;
+      if (j * kWave < n) cell[j] = i < n ? pts[i] : kNoCell;
+    }
+  }
+}
+
+// The level the children of a node at (dx, dy) are scored on.  Everything about a node is
+// wavefront-uniform, and the compiler is TOLD so: a buffer resource it cannot prove uniform gets
+// every one of the sixteen gathers wrapped in a readfirstlane loop of thirty instructions.
+struct ChainLevel {
+  int qx, qy, qtx;
+  int half;                    // 1 << child_level
+  int ax, ay;                  // what a cell's coordinates are moved by: d + 2 half - 1
+  __amdgpu_buffer_rsrc_t quad_rsrc;
+};
+
+__device__ __forceinline__ ChainLevel MakeChainLevel(const Fast2DProblem& P, int child_level,
+                                                     int dx, int dy) {
+  const LevelDesc& Lm = P.level[child_level];
+  ChainLevel L;
+  L.half = 1 << child_level;
+  L.ax = dx + 2 * L.half - 1;
+  L.ay = dy + 2 * L.half - 1;
+  L.qx = __builtin_amdgcn_readfirstlane(Lm.qx);
+  L.qy = __builtin_amdgcn_readfirstlane(Lm.qy);
+  L.qtx = __builtin_amdgcn_readfirstlane(Lm.qtx);
+  const unsigned long long quads_address = reinterpret_cast<unsigned long long>(Lm.quads);
+  const unsigned long long quads_uniform =
+      static_cast<unsigned long long>(static_cast<unsigned>(
+          __builtin_amdgcn_readfirstlane(static_cast<unsigned>(quads_address)))) |
+      (static_cast<unsigned long long>(static_cast<unsigned>(
+           __builtin_amdgcn_readfirstlane(static_cast<unsigned>(quads_address >> 32)))) << 32);
+  const unsigned long long quad_bytes =
+      static_cast<unsigned long long>((L.qy + 3) >> 2) * static_cast<unsigned>(L.qtx) * 128ull;
+  // (levels beyond the 2 GB a buffer resource addresses do not come here: see ChainWalkPossible)
+  L.quad_rsrc = __builtin_amdgcn_make_buffer_rsrc(
+      reinterpret_cast<uint32_t*>(quads_uniform), 0, static_cast<int>(quad_bytes), 0x00020000);
+  return L;
+}
+
+// Quad gathers of cells [kFirst, kFirst + kCount) of the lane, all in flight at once, added to
+// packed 16-bit sums: even = (child 00 | child 10 << 16), odd = (child 01 | child 11 << 16); a
+// lane adds at most 16 x 255.  Children beyond the search bounds (`break`s at :356,361) are
+// summed like the others and dropped when the scores are formed.  seen_max: the sum of the
+// largest child of every point (the early-exit bound of the queue's chains; kWantMax = false, a
+// dive, which never gives up: not formed, seen_max untouched).
+template <int kFirst, int kCount, bool kWantMax>
+__device__ __forceinline__ void ChainGather(const ChainLevel& L, const uint32_t (&cell)[kChainCells],
+                                            uint32_t* even, uint32_t* odd, int* seen_max) {
+  typedef unsigned short Halves __attribute__((ext_vector_type(2)));
+  uint32_t v[kCount];
+#pragma unroll
+  for (int u = 0; u < kCount; ++u) {
+    const uint32_t p = cell[kFirst + u];
+    const unsigned X = static_cast<unsigned>(static_cast<short>(p & 0xffffu) + L.ax);
+    const unsigned Y = static_cast<unsigned>(static_cast<short>(p >> 16) + L.ay);
+    const bool inside = X < static_cast<unsigned>(L.qx) && Y < static_cast<unsigned>(L.qy);
+    // QuadOffset(X, Y, qtx) * 4, branch-free, the tile index by a 24-bit multiply-add
+    // (inside: Y >> 2 and qtx are far below 2^24)
+    const unsigned tile = __umul24(Y >> 2, static_cast<unsigned>(L.qtx)) + (X >> 3);
+    const unsigned byte = (tile << 7) | ((Y & 3u) << 5) | ((X & 7u) << 2);
+    v[u] = __builtin_amdgcn_raw_buffer_load_b32(L.quad_rsrc, inside ? byte : 0xfffffff0u, 0, 0);
+  }
+#pragma unroll
+  for (int u = 0; u < kCount; ++u) {
+    const uint32_t e = v[u] & 0x00ff00ffu, o = (v[u] >> 8) & 0x00ff00ffu;
+    *even += e;
+    *odd += o;
+    if constexpr (kWantMax) {
+      Halves eh, oh;
+      __builtin_memcpy(&eh, &e, 4);
+      __builtin_memcpy(&oh, &o, 4);
+      const Halves m = __builtin_elementwise_max(eh, oh);
+      *seen_max += static_cast<int>(max(m.x, m.y));
+    }
+  }
+}
+
+// The dive of DiveKernel, one per WAVEFRONT: the chain a worker of TreeQueueKernel walks, with
+// nothing pushed and no bound to give up at.  The scan's cells sit in registers, every gather of a
+// level is in flight at once, the children are summed and ranked by wavefront reductions: no LDS
+// and no barrier behind the seed selection.  A workgroup selects once (256 threads, so the seeds
+// are DiveKernel's) and dives into what it selected: the three rotations of ONE seed unit under
+// group bounds (the fourth wavefront leaves), four seeds otherwise.  Leaves, bound and work
+// counters as DiveKernel leaves them.
+__global__ void __launch_bounds__(256)
+DiveWaveKernel(const Fast2DProblem* __restrict__ problems, ProblemState* __restrict__ states, int n,
+               NodeList leaves, Counters* __restrict__ counters) {
+  const int problem = blockIdx.y;
+  const Fast2DProblem& P = problems[problem];
+  ProblemState& st = states[problem];
+  if (st.error) return;
+  __shared__ SeedScratch seed_scratch;
+  const bool grouped = P.group > 1;
+  const int seeds = grouped ? 1 : 4;
+  const int want0 = static_cast<int>(blockIdx.x) * seeds;
+  if (want0 >= kSeedsPerProblem) return;
+  PickSeeds(P, n, want0, seeds, &seed_scratch);
+  if (blockIdx.x == 0 && threadIdx.x == 0) st.coarse_total = seed_scratch.total;
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  if (grouped && wave >= kFusedGroup) return;
+  int seed_scan = __builtin_amdgcn_readfirstlane(seed_scratch.found_scan[grouped ? 0 : wave]);
+  if (seed_scan < 0) return;
+  if (grouped) {
+    seed_scan = seed_scan - seed_scan % kFusedGroup + wave;
+    if (seed_scan >= P.num_scans) return;
+  }
+  const Node2D seed = CoarseNode(P, problem, seed_scan, P.scan_best[seed_scan].y);
+  uint32_t cell[kChainCells];
+  // The front end has written this rotation's cells if it writes all of them, or (store_scans) if
+  // the rotation's OWN best candidate reaches the threshold -- the test it applies itself, on the
+  // sum it left in scan_best.  An outer rotation of a seed unit may miss it (its window need not
+  // hold the candidate its unit qualified by): its cells are re-derived, sixteen ScanCells a lane.
+  const bool stored =
+      !P.recompute_scans ||
+      (P.store_scans && !(ToScore(P, P.scan_best[seed_scan].x, n) < fmaxf(P.min_score, 0.f)));
+  if (__builtin_amdgcn_readfirstlane(stored ? 1 : 0)) LoadChainCells<false>(P, n, seed_scan, cell);
+  else LoadChainCells<true>(P, n, seed_scan, cell);
+  const int4 bd = P.bounds[seed_scan];
+  const int depth = P.depth;
+  int dx = __builtin_amdgcn_readfirstlane(seed.dx), dy = __builtin_amdgcn_readfirstlane(seed.dy);
+  float score = seed.score;
+  unsigned long long scored = 0;
+  for (int child_level = depth - 2; child_level >= 0; --child_level) {
+    const ChainLevel L = MakeChainLevel(P, child_level, dx, dy);
+    const bool vx = dx + L.half <= bd.y, vy = dy + L.half <= bd.w;
+    uint32_t even = 0, odd = 0;
+    if (n > 8 * kWave) ChainGather<0, 16, false>(L, cell, &even, &odd, nullptr);
+    else if (n > 4 * kWave) ChainGather<0, 8, false>(L, cell, &even, &odd, nullptr);
+    else ChainGather<0, 4, false>(L, cell, &even, &odd, nullptr);
+    const int total[4] = {WaveSum(static_cast<int>(even & 0xffffu)), WaveSum(static_cast<int>(odd & 0xffffu)),
+                          WaveSum(static_cast<int>(even >> 16)), WaveSum(static_cast<int>(odd >> 16))};
+    // child k = 2 * x-step + y-step (generation order: x outer, y inner); the dive goes on with
+    // the one the reference's stable descending sort puts first: the best, ties to the lower index
+    int kbest = 0, nvalid = 0;
+    float best_score = -1.f;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const bool valid = ((k >> 1) == 0 || vx) && ((k & 1) == 0 || vy);
+      const float sc = valid ? ToScore(P, total[k], n) : -1.f;
+      nvalid += valid ? 1 : 0;
+      if (sc >= 0.f && (k == 0 || sc > best_score)) { kbest = k; best_score = sc; }
+    }
+    kbest = __builtin_amdgcn_readfirstlane(kbest);
+    dx += (kbest >> 1) * L.half;
+    dy += (kbest & 1) * L.half;
+    score = best_score;
+    scored += nvalid;
+  }
+  if (lane == 0) {
+    if (score > P.min_score) {
+      Node2D leaf = seed;          // (rank 0 at every level: the path stays 0)
+      leaf.problem = problem;      // level 0
+      leaf.dx = dx;
+      leaf.dy = dy;
+      leaf.score = score;
+      RecordLeaf(leaf, leaves, counters);
+      atomicMax(&st.best_bits, __float_as_uint(score));
+    }
+    const int shard = (blockIdx.x * 4 + wave) & (kStatShards - 1);
+    atomicAdd(&st.scored_shard[shard], scored);
+    atomicAdd(&st.expanded_shard[shard], static_cast<unsigned long long>(depth - 1));
+  }
+}
+
 // One leaf record, stored so that the selecting workgroup of the SAME launch reads it.
 __device__ __forceinline__ void RecordLeafAgent(const Node2D& leaf, const NodeList& leaves,
                                                 int sub, Counters* __restrict__ counters) {
@@ -1405,48 +1605,19 @@ TreeQueueKernel(const Fast2DProblem* __restrict__ problems, ProblemState* __rest
     if (problem != stat_problem) { flush_stats(); stat_problem = problem; }
     ++q_chains;
     // the node's scan: 16 cells per lane, kept for the whole chain
-    const auto* pts = AsGlobal(P.discrete) + static_cast<size_t>(nd.scan) * n;
     uint32_t cell[kChainCells];
-#pragma unroll
-    for (int j = 0; j < kChainCells; ++j) {
-      const int i = j * kWave + lane;
-      cell[j] = kNoCell;
-      if (j * kWave < n) cell[j] = i < n ? pts[i] : kNoCell;
-    }
+    LoadChainCells<false>(P, n, nd.scan, cell);
     const int4 bd = P.bounds[nd.scan];
     const float min_score = P.min_score;
     for (;;) {                                           // the chain
-      // (everything about the node is wavefront-uniform, and the compiler is TOLD so: a buffer
-      // resource it cannot prove uniform gets every one of the sixteen gathers wrapped in a
-      // readfirstlane loop of thirty instructions)
       const int child_level = __builtin_amdgcn_readfirstlane(NodeLevel(nd) - 1);
-      const LevelDesc& Lm = P.level[child_level];
-      const int half = 1 << child_level;
       const int ndx = __builtin_amdgcn_readfirstlane(nd.dx), ndy = __builtin_amdgcn_readfirstlane(nd.dy);
+      const ChainLevel L = MakeChainLevel(P, child_level, ndx, ndy);
+      const int half = L.half;
       const bool vx = ndx + half <= bd.y, vy = ndy + half <= bd.w;
-      const int ax = ndx + 2 * half - 1, ay = ndy + 2 * half - 1;
       const int parent_ub = SumUpperBound(P, nd.score, n);
-      struct { int qx, qy, qtx; } L;
-      L.qx = __builtin_amdgcn_readfirstlane(Lm.qx);
-      L.qy = __builtin_amdgcn_readfirstlane(Lm.qy);
-      L.qtx = __builtin_amdgcn_readfirstlane(Lm.qtx);
-      const unsigned long long quads_address = reinterpret_cast<unsigned long long>(Lm.quads);
-      const unsigned long long quads_uniform =
-          static_cast<unsigned long long>(static_cast<unsigned>(
-              __builtin_amdgcn_readfirstlane(static_cast<unsigned>(quads_address)))) |
-          (static_cast<unsigned long long>(static_cast<unsigned>(
-               __builtin_amdgcn_readfirstlane(static_cast<unsigned>(quads_address >> 32)))) << 32);
-      const unsigned long long quad_bytes =
-          static_cast<unsigned long long>((L.qy + 3) >> 2) * static_cast<unsigned>(L.qtx) * 128ull;
-      // (levels beyond the 2 GB a buffer resource addresses do not come here: see queue_ok)
-      const __amdgpu_buffer_rsrc_t quad_rsrc = __builtin_amdgcn_make_buffer_rsrc(
-          reinterpret_cast<uint32_t*>(quads_uniform), 0, static_cast<int>(quad_bytes), 0x00020000);
-      // packed 16-bit sums: (child 00 | child 10 << 16) and (child 01 | child 11 << 16); a lane adds
-      // at most 16 x 255.  Children beyond the search bounds (`break`s at :356,361) are summed
-      // like the others and dropped when the scores are formed: the level-(l+1) cell is the
-      // maximum of all four level-l cells whatever the bounds say, so the early-exit bound below
-      // holds with them in it.
-      typedef unsigned short Halves __attribute__((ext_vector_type(2)));
+      // (the level-(l+1) cell is the maximum of all four level-l cells whatever the bounds say, so
+      // the early-exit bound below holds with the children beyond the search bounds summed)
       uint32_t even = 0, odd = 0;
       int seen_max = 0;
       bool dead = false;
@@ -1454,31 +1625,8 @@ TreeQueueKernel(const Fast2DProblem* __restrict__ problems, ProblemState* __rest
       // others in flight at once: two trips to memory per expansion at most (a check after every
       // 256 points was four).
       const auto gather = [&](auto first_tag, auto count_tag) {
-        constexpr int kFirst = decltype(first_tag)::value, kCount = decltype(count_tag)::value;
-        uint32_t v[kCount];
-#pragma unroll
-        for (int u = 0; u < kCount; ++u) {
-          const uint32_t p = cell[kFirst + u];
-          const unsigned X = static_cast<unsigned>(static_cast<short>(p & 0xffffu) + ax);
-          const unsigned Y = static_cast<unsigned>(static_cast<short>(p >> 16) + ay);
-          const bool inside = X < static_cast<unsigned>(L.qx) && Y < static_cast<unsigned>(L.qy);
-          // QuadOffset(X, Y, qtx) * 4, branch-free, the tile index by a 24-bit multiply-add
-          // (inside: Y >> 2 and qtx are far below 2^24)
-          const unsigned tile = __umul24(Y >> 2, static_cast<unsigned>(L.qtx)) + (X >> 3);
-          const unsigned byte = (tile << 7) | ((Y & 3u) << 5) | ((X & 7u) << 2);
-          v[u] = __builtin_amdgcn_raw_buffer_load_b32(quad_rsrc, inside ? byte : 0xfffffff0u, 0, 0);
-        }
-#pragma unroll
-        for (int u = 0; u < kCount; ++u) {
-          const uint32_t e = v[u] & 0x00ff00ffu, o = (v[u] >> 8) & 0x00ff00ffu;
-          even += e;
-          odd += o;
-          Halves eh, oh;
-          __builtin_memcpy(&eh, &e, 4);
-          __builtin_memcpy(&oh, &o, 4);
-          const Halves m = __builtin_elementwise_max(eh, oh);
-          seen_max += static_cast<int>(max(m.x, m.y));
-        }
+        ChainGather<decltype(first_tag)::value, decltype(count_tag)::value, true>(L, cell, &even,
+                                                                                  &odd, &seen_max);
       };
       gather(std::integral_constant<int, 0>{}, std::integral_constant<int, 4>{});
       gathers += 4;
@@ -1797,16 +1945,22 @@ void RunDepthOne(SearchRun& run) {
   run.FetchResults(false);
 }
 
-// Whether the work queue can take this batch: it holds a scan in registers (QueueSearchWanted), it
-// reads stored cells, and it gathers quads through buffer resources (2 GB per level).
-bool QueueSearchPossible(const SearchRun& run) {
-  bool queue_ok = QueueSearchWanted(run.n, run.num);
-  for (const Fast2DProblem& P : run.batch.h_problems) {
-    queue_ok = queue_ok && (P.recompute_scans == 0 || P.store_scans != 0);
+// Whether a wavefront can walk chains of this batch's nodes (LoadChainCells, ChainGather): it
+// holds a scan in registers and gathers quads through buffer resources (2 GB per level).
+bool ChainWalkPossible(const SearchRun& run) {
+  bool chain_ok = run.n <= kChainCells * kWave;
+  for (const Fast2DProblem& P : run.batch.h_problems)
     for (int l = 0; l + 1 < run.depth; ++l)
-      queue_ok = queue_ok && static_cast<unsigned long long>((P.level[l].qy + 3) >> 2) *
+      chain_ok = chain_ok && static_cast<unsigned long long>((P.level[l].qy + 3) >> 2) *
                                      static_cast<unsigned>(P.level[l].qtx) * 128ull < (1ull << 31);
-  }
+  return chain_ok;
+}
+
+// Whether the work queue can take this batch: its wavefronts walk chains, of stored cells.
+bool QueueSearchPossible(const SearchRun& run) {
+  bool queue_ok = QueueSearchWanted(run.n, run.num) && ChainWalkPossible(run);
+  for (const Fast2DProblem& P : run.batch.h_problems)
+    queue_ok = queue_ok && (P.recompute_scans == 0 || P.store_scans != 0);
   return queue_ok;
 }
 
@@ -1999,8 +2153,16 @@ void RunBranchAndBound(Workspace& ws, const PreparedBatch& batch, BatchResult* r
   } else {
     // (the launches of the search proper: one turn from the dive to the tree launch)
     std::unique_ptr<LaunchTurn> turn(new LaunchTurn);
-    DiveKernel<<<dim3(kSeedsPerProblem * (batch.any_group ? kFusedGroup : 1), num), 256, 0, ws.stream>>>(
-        batch.d_problems, batch.d_states, run.n, run.leaf_list, run.d_counters);
+    // A wavefront per dive wherever a wavefront can hold the scan; a workgroup per dive for larger
+    // clouds and as the parity partner (debug switch fast2d_dive).
+    if (Debug().fast2d_dive != 1 && ChainWalkPossible(run)) {
+      DiveWaveKernel<<<dim3(batch.any_group ? kSeedsPerProblem : kSeedsPerProblem / 4, num), 256, 0,
+                       ws.stream>>>(batch.d_problems, batch.d_states, run.n, run.leaf_list,
+                                    run.d_counters);
+    } else {
+      DiveKernel<<<dim3(kSeedsPerProblem * (batch.any_group ? kFusedGroup : 1), num), 256, 0, ws.stream>>>(
+          batch.d_problems, batch.d_states, run.n, run.leaf_list, run.d_counters);
+    }
     run.Mark("seed+dive");
     bool searched = false;
     if (QueueSearchPossible(run)) {

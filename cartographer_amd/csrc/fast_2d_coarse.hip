@@ -604,6 +604,13 @@ __device__ __forceinline__ void FusedPass(const Fast2DProblem& P, ProblemState* 
   for (int j = 0; j < 4; ++j) {
     const int cell = min(4 * sub + j, PIJ - 1);
     lane_const[j] = (cell % PI + dims.x + PI - 2) * pitch + (cell / PI + dims.y + PJ - 2);
+    // (opaque from here on: the flush behind the loop otherwise re-derives the constant from its
+    // terms, which then stay live across the loop -- two of them in scratch memory, the gather
+    // loop filling the 64 registers).  This steers the register allocator, it does not bind it:
+    // after any edit to this function or a compiler change, run tools/kernel_isa_diff.py again
+    // and look for private = 0 and vgpr <= 64 on both instantiations of PrepScoreFusedKernel
+    // (profiles/fast2d_wave_dive_isa.txt is the last such reading, not a check).
+    asm volatile("" : "+v"(lane_const[j]));
   }
   // Four 32-bit running sums, one per plane cell of the lane's dword (round 4's per-chunk stamps:
   // a step of this loop is ~15 issued instructions on a SIMD shared by 4.5 wavefronts -- 1.9 of a
