@@ -61,7 +61,7 @@ __device__ __forceinline__ float ValueToProbabilityDev(unsigned raw) {
 
 // ConvertToPrecomputationGrid (SM3/precomputation_grid_3d.cc:49-62): the uint8 value level 0 of
 // the precomputation stack holds for a raw HybridGrid value (0 -> 0).  Shared by the voxel-list
-// scatter (rt_3d.hip) and the crop of a resident grid (fast_3d.hip).
+// scatter (rt_3d.hip) and the crop of a resident grid (fast_3d_stack.hip).
 __device__ __forceinline__ uint8_t PrecomputationValueDev(unsigned raw) {
   const float kMinP = 0.1f;
   const float kMaxP = 1.f - kMinP;
@@ -179,7 +179,7 @@ void BuildBrickFromVoxels(Workspace& ws, const cmx_voxel* voxels, int64_t n, int
                           DeviceBrick* out);
 // DynamicGrid growth rule (hybrid_grid.h:259,381-398).
 int GridSizeOf(const cmx_voxel* voxels, int64_t n);
-// fast_3d.hip: device and raw (uint16) grids of a 3D matcher.
+// fast_3d_stack.hip: device and raw (uint16) grids of a 3D matcher.
 int Fast3DDevice(const cmx_fast3d* matcher);
 void Fast3DGrids(const cmx_fast3d* matcher, Brick* high, float* resolution, Brick* low,
                  float* low_resolution);

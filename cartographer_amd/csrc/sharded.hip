@@ -26,7 +26,7 @@
 
 struct cmx_fast3d;
 namespace cmx {
-int Fast3DDevice(const cmx_fast3d* matcher);   // fast_3d.hip
+int Fast3DDevice(const cmx_fast3d* matcher);   // fast_3d_stack.hip
 namespace {
 
 // The few RCCL entry points used, with the types of rccl.h (ncclComm_t is an opaque pointer,
