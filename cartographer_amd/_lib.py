@@ -179,6 +179,9 @@ EXPORTED_SYMBOLS = [
     "cmx_grid3d_download",
     "cmx_fast2d_create", "cmx_fast2d_create_from_grid", "cmx_fast2d_destroy", "cmx_fast2d_match",
     "cmx_fast2d_match_full_submap", "cmx_fast2d_match_batch",
+    "cmx_fast2d_match_pairs", "cmx_fast2d_match_pairs_resident",
+    "cmx_fast2d_refine_pairs", "cmx_fast2d_refine_pairs_resident",
+    "cmx_ceres2d_refine_pairs_tsdf",
     "cmx_fast2d_match_full_submap_batch", "cmx_cloud_upload",
     "cmx_cloud_destroy", "cmx_fast2d_match_full_submap_batch_resident", "cmx_fast2d_level_dims",
     "cmx_fast2d_level_cells", "cmx_fast2d_debug_prepare", "cmx_rt3d_match", "cmx_fast3d_create",
@@ -326,6 +329,21 @@ def lib():
     L.cmx_ceres2d_refine_batch_tsdf.argtypes = [P(Ceres2DOptions), P(C.c_void_p), C.c_int32,
                                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
                                                 C.c_void_p, C.c_void_p]
+    if hasattr(L, "cmx_fast2d_match_pairs"):   # (absent from an older library an A/B tool loads)
+        L.cmx_fast2d_match_pairs.argtypes = [P(C.c_void_p), C.c_int32, C.c_void_p, C.c_void_p,
+                                             C.c_void_p, P(C.c_void_p), C.c_void_p, C.c_void_p,
+                                             C.c_void_p, C.c_void_p, P(MatchStats)]
+        L.cmx_fast2d_match_pairs_resident.argtypes = [P(C.c_void_p), C.c_int32, C.c_void_p,
+                                                      C.c_void_p, C.c_void_p, P(C.c_void_p),
+                                                      C.c_void_p, C.c_void_p, C.c_void_p,
+                                                      P(MatchStats)]
+        L.cmx_fast2d_refine_pairs.argtypes = [P(Ceres2DOptions), P(C.c_void_p), C.c_int32,
+                                              C.c_void_p, C.c_void_p, P(C.c_void_p), C.c_void_p,
+                                              C.c_void_p, C.c_void_p]
+        L.cmx_fast2d_refine_pairs_resident.argtypes = [P(Ceres2DOptions), P(C.c_void_p), C.c_int32,
+                                                       C.c_void_p, C.c_void_p, P(C.c_void_p),
+                                                       C.c_void_p, C.c_void_p]
+        L.cmx_ceres2d_refine_pairs_tsdf.argtypes = L.cmx_fast2d_refine_pairs.argtypes
     L.cmx_ceres2d_tsdf_residuals.argtypes = [P(Grid2DLimits), C.c_void_p, C.c_void_p, C.c_float,
                                              C.c_float, C.c_double, C.c_void_p, C.c_void_p,
                                              C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,

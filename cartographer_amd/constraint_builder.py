@@ -8,7 +8,10 @@ Same entry points, argument meaning and filtering rules (``MaybeAddConstraint``:
 thread-pool task per (node, submap) pair (:97-111); here the pairs of a node are collected and
 ``NotifyEndOfNode`` searches them in ONE device batch (``cmx_fast2d_match_batch``), against
 precomputation stacks that stay resident in HBM, keyed by ``SubmapId``, until
-``DeleteScanMatcher`` (:307-316) frees them.
+``DeleteScanMatcher`` (:307-316) frees them.  With ``pairs=True`` everything pending -- the
+pairs of however many nodes, as in the burst of ``PoseGraph2D::ComputeConstraintsForNode`` when a
+submap finishes (``pose_graph_2d.cc:383-393``) -- goes out in one ``cmx_fast2d_match_pairs``
+call and, with ``ceres``, one ``cmx_fast2d_refine_pairs`` launch.
 
 Not built: the Ceres refinement of :240-249.  ``refine`` may be given a
 callable ``(pose_estimate, point_cloud, grid) -> Rigid2d`` standing in for it; by default the
@@ -111,13 +114,16 @@ class _Pending:
 
 class ConstraintBuilder2D:
     def __init__(self, options: ConstraintBuilderOptions, device: int = 0,
-                 refine: Optional[Callable] = None, ceres=None):
+                 refine: Optional[Callable] = None, ceres=None, pairs: bool = False):
         # `ceres`: a scan_matching.CeresScanMatcher2D, the builder's ceres_scan_matcher_; the
         # found pairs of a node are refined by one cmx_fast2d_refine_batch launch.
+        # `pairs`: everything pending goes out in one cmx_fast2d_match_pairs call (and one
+        # cmx_fast2d_refine_pairs launch) instead of one batch per node; same constraints.
         self.options = options
         self.device = device
         self.refine = refine
         self.ceres = ceres
+        self.pairs = pairs
         self.last_refine_summaries = None
         self._scan_matchers: Dict[SubmapId, FastCorrelativeScanMatcher2D] = {}
         self._samplers: Dict[SubmapId, FixedRatioSampler] = {}
@@ -192,22 +198,47 @@ class ConstraintBuilder2D:
         groups: Dict[int, List[_Pending]] = {}
         for item in pending:                      # one batch per point cloud (= per node)
             groups.setdefault(item.cloud_key, []).append(item)
+        if self.pairs:
+            if pending:                           # the pairs of a node stay together, in order
+                self._match_pairs([item for items in groups.values() for item in items],
+                                  {key: items[0].point_cloud for key, items in groups.items()})
+            return
         for items in groups.values():
             self._match_group(items[0].point_cloud, items)
 
-    def _match_group(self, xyz, items):
+    def _search_arguments(self, items):
         num = len(items)
-        handles = (C.c_void_p * num)(*[i.matcher._h for i in items])
-        initial = (Pose2d * num)()
+        initial = [None] * num
         full = np.zeros(num, np.int32)
         min_scores = np.zeros(num, np.float32)
         for k, item in enumerate(items):
             # ComputeConstraint (:196-197): initial_pose = ComputeSubmapPose(submap) * relative.
-            init = multiply(item.submap.local_pose, item.initial_relative_pose)
-            initial[k] = Pose2d(init.x, init.y, init.theta)
+            initial[k] = multiply(item.submap.local_pose, item.initial_relative_pose)
             full[k] = 1 if item.match_full_submap else 0
             min_scores[k] = (self.options.global_localization_min_score if item.match_full_submap
                              else self.options.min_score)
+        return initial, full, min_scores
+
+    def _match_pairs(self, items, cloud_of):
+        """All pending pairs in one cmx_fast2d_match_pairs call, the found ones in one
+        cmx_fast2d_refine_pairs launch; pairs of one node name one array (one upload)."""
+        from .scan_matching import match_pairs
+        initial, full, min_scores = self._search_arguments(items)
+        clouds = [cloud_of[i.cloud_key] for i in items]
+        matchers = [i.matcher for i in items]
+        found, scores, poses, self.last_batch_stats = match_pairs(matchers, initial, full,
+                                                                  min_scores, clouds)
+        refined = None
+        if self.ceres is not None and found.any():
+            refined, self.last_refine_summaries = self.ceres.refine_pairs(matchers, found, poses,
+                                                                          clouds)
+        self._store(items, found, scores, poses, refined)
+
+    def _match_group(self, xyz, items):
+        num = len(items)
+        handles = (C.c_void_p * num)(*[i.matcher._h for i in items])
+        poses_in, full, min_scores = self._search_arguments(items)
+        initial = (Pose2d * num)(*[Pose2d(p.x, p.y, p.theta) for p in poses_in])
         found = np.zeros(num, np.int32)
         scores = np.zeros(num, np.float32)
         poses = (Pose2d * num)()
@@ -222,6 +253,9 @@ class ConstraintBuilder2D:
             refined, self.last_refine_summaries = self.ceres.refine_batch(
                 [i.matcher for i in items], found,
                 [Rigid2d(p.x, p.y, p.theta) for p in poses], xyz)
+        self._store(items, found, scores, poses, refined)
+
+    def _store(self, items, found, scores, poses, refined):
         for k, item in enumerate(items):
             if not found[k]:
                 continue                                   # `return;` at :219 / :232

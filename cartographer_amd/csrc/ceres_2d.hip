@@ -536,6 +536,11 @@ struct RefineItem {
   double target[2];
   cmx_pose2d initial;
   int skip;
+  // The item's cloud: in HBM already (device_xyz), or staged with the call (host_xyz; items that
+  // name the same host array share one staged copy).
+  const float* host_xyz;
+  const float* device_xyz;
+  int n;
 };
 
 void CheckOptions(const cmx_ceres2d_options* o) {
@@ -547,23 +552,34 @@ void CheckOptions(const cmx_ceres2d_options* o) {
   CMX_REQUIRE(o->max_num_iterations > 0, "max_num_iterations must be > 0");
 }
 
-// One launch for `num` problems sharing one point cloud; device_xyz may be null (host_xyz is
-// uploaded then).
-void RefineBatch(const cmx_ceres2d_options* options, const RefineItem* items, int num,
-                 const float* host_xyz, int n, int device, cmx_pose2d* poses,
-                 cmx_ceres_summary* summaries) {
+// One launch, one result copy and one synchronisation for `num` problems, each with the cloud
+// its item names: the one-cloud entry points are the case of all items naming the same array.
+void RefineBatch(const cmx_ceres2d_options* options, const RefineItem* items, int num, int device,
+                 cmx_pose2d* poses, cmx_ceres_summary* summaries) {
   CheckOptions(options);
   CMX_REQUIRE(items && num >= 1 && poses, "null argument");
   const bool tsdf = items[0].tsdf != 0;
-  // A TSDF takes an empty cloud: S == 0 then fails the initial evaluation, as in the reference.
-  CMX_REQUIRE((host_xyz != nullptr || (tsdf && n == 0)) && n >= (tsdf ? 0 : 1) && n <= (1 << 24),
-              "bad point cloud");
-  WorkspaceLease ws(device);
-  // Staging: problems | cloud | host grids.
+  // Staging: problems | distinct host clouds | host grids.
   const auto align = [](size_t v) { return (v + 255) & ~static_cast<size_t>(255); };
   size_t bytes = align(sizeof(Ceres2DProblem) * num);
-  const size_t off_xyz = bytes;
-  bytes += align(12 * static_cast<size_t>(n));
+  struct Staged { size_t offset; int n; };
+  std::map<const float*, Staged> staged;
+  std::vector<size_t> off_xyz(num, bytes);
+  for (int p = 0; p < num; ++p) {
+    const RefineItem& it = items[p];
+    // A TSDF takes an empty cloud: S == 0 then fails the initial evaluation, as in the reference.
+    CMX_REQUIRE((it.host_xyz != nullptr || it.device_xyz != nullptr || (tsdf && it.n == 0)) &&
+                    it.n >= (tsdf ? 0 : 1) && it.n <= (1 << 24),
+                "bad point cloud");
+    if (it.device_xyz || it.n == 0) continue;
+    const auto seen = staged.emplace(it.host_xyz, Staged{bytes, it.n});
+    CMX_REQUIRE(seen.first->second.n == it.n,
+                "entry %d names a cloud of an earlier entry with another num_points (%d, there %d)",
+                p, it.n, seen.first->second.n);
+    off_xyz[p] = seen.first->second.offset;
+    if (seen.second) bytes += align(12 * static_cast<size_t>(it.n));
+  }
+  WorkspaceLease ws(device);
   std::vector<size_t> off_cells(num, 0), off_weights(num, 0);
   for (int p = 0; p < num; ++p) {
     const cmx_grid2d_limits& lim = items[p].limits;
@@ -590,7 +606,8 @@ void RefineBatch(const cmx_ceres2d_options* options, const RefineItem* items, in
   char* d_in = ws->dev[0].ReserveAs<char>(bytes);
   double* d_out = ws->dev[1].ReserveAs<double>(8 * static_cast<size_t>(num));
   double* h_out = ws->pinned[1].ReserveAs<double>(8 * static_cast<size_t>(num));
-  if (n > 0) std::memcpy(h_in + off_xyz, host_xyz, 12 * static_cast<size_t>(n));
+  for (const auto& cloud : staged)
+    std::memcpy(h_in + cloud.second.offset, cloud.first, 12 * static_cast<size_t>(cloud.second.n));
   Ceres2DProblem* h_prob = reinterpret_cast<Ceres2DProblem*>(h_in);
   for (int p = 0; p < num; ++p) {
     const RefineItem& it = items[p];
@@ -613,11 +630,11 @@ void RefineBatch(const cmx_ceres2d_options* options, const RefineItem* items, in
     P.nx = it.limits.num_x_cells; P.ny = it.limits.num_y_cells;
     P.res = it.limits.resolution; P.max_x = it.limits.max_x; P.max_y = it.limits.max_y;
     P.min_cc = it.limits.min_correspondence_cost; P.max_cc = it.limits.max_correspondence_cost;
-    P.xyz = reinterpret_cast<const float*>(d_in + off_xyz);
-    P.n = n;
+    P.xyz = it.device_xyz ? it.device_xyz : reinterpret_cast<const float*>(d_in + off_xyz[p]);
+    P.n = it.n;
     P.init[0] = it.initial.x; P.init[1] = it.initial.y; P.init[2] = it.initial.theta;
     P.target_x = it.target[0]; P.target_y = it.target[1];
-    P.occupied_scaling = options->occupied_space_weight / std::sqrt(static_cast<double>(n));
+    P.occupied_scaling = options->occupied_space_weight / std::sqrt(static_cast<double>(it.n));
     P.translation_weight = options->translation_weight;
     P.rotation_weight = options->rotation_weight;
     P.use_nonmonotonic_steps = options->use_nonmonotonic_steps ? 1 : 0;
@@ -750,7 +767,9 @@ cmx_status cmx_ceres2d_match(const cmx_ceres2d_options* options, const cmx_grid2
     item.target[0] = target_translation_xy[0];
     item.target[1] = target_translation_xy[1];
     item.initial = *initial_pose_estimate;
-    cmx::RefineBatch(options, &item, 1, point_cloud_xyz, num_points, device, pose_estimate, summary);
+    item.host_xyz = point_cloud_xyz;
+    item.n = num_points;
+    cmx::RefineBatch(options, &item, 1, device, pose_estimate, summary);
   });
 }
 
@@ -768,7 +787,9 @@ cmx_status cmx_ceres2d_match_grid(const cmx_ceres2d_options* options, const cmx_
     item.target[0] = target_translation_xy[0];
     item.target[1] = target_translation_xy[1];
     item.initial = *initial_pose_estimate;
-    cmx::RefineBatch(options, &item, 1, point_cloud_xyz, num_points, device, pose_estimate, summary);
+    item.host_xyz = point_cloud_xyz;
+    item.n = num_points;
+    cmx::RefineBatch(options, &item, 1, device, pose_estimate, summary);
   });
 }
 
@@ -802,11 +823,13 @@ cmx_status cmx_fast2d_refine_batch(const cmx_ceres2d_options* options,
         it.target[0] = pose_estimates_in[p].x;
         it.target[1] = pose_estimates_in[p].y;
         it.skip = found && !found[p] ? 1 : 0;
+        it.host_xyz = point_cloud_xyz;
+        it.n = num_points;
       }
       std::vector<cmx_pose2d> poses(m);
       std::vector<cmx_ceres_summary> sums(m);
-      cmx::RefineBatch(options, items.data(), m, point_cloud_xyz, num_points, group.first,
-                       poses.data(), summaries ? sums.data() : nullptr);
+      cmx::RefineBatch(options, items.data(), m, group.first, poses.data(),
+                       summaries ? sums.data() : nullptr);
       for (int k = 0; k < m; ++k) {
         pose_estimates_out[idx[k]] = poses[k];
         if (summaries) summaries[idx[k]] = sums[k];
@@ -829,7 +852,9 @@ cmx_status cmx_ceres2d_match_tsdf(const cmx_ceres2d_options* options,
     item.target[0] = target_translation_xy[0];
     item.target[1] = target_translation_xy[1];
     item.initial = *initial_pose_estimate;
-    cmx::RefineBatch(options, &item, 1, point_cloud_xyz, num_points, device, pose_estimate, summary);
+    item.host_xyz = point_cloud_xyz;
+    item.n = num_points;
+    cmx::RefineBatch(options, &item, 1, device, pose_estimate, summary);
   });
 }
 
@@ -846,7 +871,9 @@ cmx_status cmx_ceres2d_match_tsdf_grid(const cmx_ceres2d_options* options, const
     item.target[0] = target_translation_xy[0];
     item.target[1] = target_translation_xy[1];
     item.initial = *initial_pose_estimate;
-    cmx::RefineBatch(options, &item, 1, point_cloud_xyz, num_points, device, pose_estimate, summary);
+    item.host_xyz = point_cloud_xyz;
+    item.n = num_points;
+    cmx::RefineBatch(options, &item, 1, device, pose_estimate, summary);
   });
 }
 
@@ -882,16 +909,142 @@ cmx_status cmx_ceres2d_refine_batch_tsdf(const cmx_ceres2d_options* options,
         it.target[0] = pose_estimates_in[p].x;
         it.target[1] = pose_estimates_in[p].y;
         it.skip = found && !found[p] ? 1 : 0;
+        it.host_xyz = point_cloud_xyz;
+        it.n = num_points;
       }
       std::vector<cmx_pose2d> poses(m);
       std::vector<cmx_ceres_summary> sums(m);
-      cmx::RefineBatch(options, items.data(), m, point_cloud_xyz, num_points, group.first,
-                       poses.data(), summaries ? sums.data() : nullptr);
+      cmx::RefineBatch(options, items.data(), m, group.first, poses.data(),
+                       summaries ? sums.data() : nullptr);
       for (int k = 0; k < m; ++k) {
         pose_estimates_out[idx[k]] = poses[k];
         if (summaries) summaries[idx[k]] = sums[k];
       }
     }
+  });
+}
+
+}  // extern "C"
+
+namespace cmx {
+namespace {
+
+// The refinement of a list of (node, submap) pairs: `items` carry grid and cloud of every pair,
+// all on `device`; one RefineBatch, hence one launch, for the whole list.
+void RefinePairs(const cmx_ceres2d_options* options, std::vector<RefineItem>* items, int device,
+                 const int32_t* found, const cmx_pose2d* pose_estimates_in,
+                 cmx_pose2d* pose_estimates_out, cmx_ceres_summary* summaries) {
+  CMX_REQUIRE(pose_estimates_in && pose_estimates_out, "null argument");
+  const int num = static_cast<int>(items->size());
+  for (int p = 0; p < num; ++p) {
+    RefineItem& it = (*items)[p];
+    // constraint_builder_2d.cc:245-249: Match(pose_estimate.translation(), pose_estimate, ...)
+    it.initial = pose_estimates_in[p];
+    it.target[0] = pose_estimates_in[p].x;
+    it.target[1] = pose_estimates_in[p].y;
+    it.skip = found && !found[p] ? 1 : 0;
+  }
+  RefineBatch(options, items->data(), num, device, pose_estimates_out, summaries);
+}
+
+// The matcher's own copy of its grid as the item of pair p; all matchers on one device.
+std::vector<RefineItem> MatcherItems(const cmx_fast2d* const* matchers, int num_pairs,
+                                     int* device) {
+  CMX_REQUIRE(matchers != nullptr, "null argument");
+  std::vector<RefineItem> items(num_pairs);
+  for (int p = 0; p < num_pairs; ++p) {
+    CMX_REQUIRE(matchers[p] && matchers[p]->impl, "null matcher handle (pair %d)", p);
+    const Fast2DMatcher& matcher = *matchers[p]->impl;
+    if (p == 0) *device = matcher.device();
+    CMX_REQUIRE(matcher.device() == *device,
+                "the matchers of a call must live on one device (pair %d)", p);
+    items[p].device_cells = matcher.grid_cells();
+    items[p].limits = matcher.limits();
+  }
+  return items;
+}
+
+}  // namespace
+}  // namespace cmx
+
+extern "C" {
+
+cmx_status cmx_fast2d_refine_pairs(const cmx_ceres2d_options* options,
+                                   const cmx_fast2d* const* matchers, int32_t num_pairs,
+                                   const int32_t* found, const cmx_pose2d* pose_estimates_in,
+                                   const float* const* point_clouds_xyz,
+                                   const int32_t* num_points, cmx_pose2d* pose_estimates_out,
+                                   cmx_ceres_summary* summaries) {
+  return Guard([&] {
+    // (a matcher handle cannot exist without a device: say so, whatever the arguments are)
+    if (cmx_device_count() <= 0) cmx::UseDevice(0);
+    CMX_REQUIRE(num_pairs >= 1, "num_pairs must be at least 1");
+    CMX_REQUIRE(point_clouds_xyz && num_points, "null argument");
+    int device = 0;
+    std::vector<cmx::RefineItem> items = cmx::MatcherItems(matchers, num_pairs, &device);
+    for (int p = 0; p < num_pairs; ++p) {
+      CMX_REQUIRE(point_clouds_xyz[p] != nullptr, "the point cloud of pair %d is null", p);
+      items[p].host_xyz = point_clouds_xyz[p];
+      items[p].n = num_points[p];
+    }
+    cmx::RefinePairs(options, &items, device, found, pose_estimates_in, pose_estimates_out,
+                     summaries);
+  });
+}
+
+cmx_status cmx_fast2d_refine_pairs_resident(const cmx_ceres2d_options* options,
+                                            const cmx_fast2d* const* matchers, int32_t num_pairs,
+                                            const int32_t* found,
+                                            const cmx_pose2d* pose_estimates_in,
+                                            const cmx_cloud* const* clouds,
+                                            cmx_pose2d* pose_estimates_out,
+                                            cmx_ceres_summary* summaries) {
+  return Guard([&] {
+    if (cmx_device_count() <= 0) cmx::UseDevice(0);
+    CMX_REQUIRE(num_pairs >= 1, "num_pairs must be at least 1");
+    CMX_REQUIRE(clouds != nullptr, "null argument");
+    int device = 0;
+    std::vector<cmx::RefineItem> items = cmx::MatcherItems(matchers, num_pairs, &device);
+    for (int p = 0; p < num_pairs; ++p) {
+      CMX_REQUIRE(clouds[p] != nullptr, "the point cloud of pair %d is null", p);
+      CMX_REQUIRE(clouds[p]->device == device,
+                  "cloud and matcher are on different devices (pair %d)", p);
+      items[p].device_xyz = clouds[p]->xyz;
+      items[p].n = clouds[p]->num_points;
+    }
+    cmx::RefinePairs(options, &items, device, found, pose_estimates_in, pose_estimates_out,
+                     summaries);
+  });
+}
+
+cmx_status cmx_ceres2d_refine_pairs_tsdf(const cmx_ceres2d_options* options,
+                                         const cmx_tsdf2d* const* grids, int32_t num_pairs,
+                                         const int32_t* found,
+                                         const cmx_pose2d* pose_estimates_in,
+                                         const float* const* point_clouds_xyz,
+                                         const int32_t* num_points,
+                                         cmx_pose2d* pose_estimates_out,
+                                         cmx_ceres_summary* summaries) {
+  return Guard([&] {
+    if (cmx_device_count() <= 0) cmx::UseDevice(0);
+    CMX_REQUIRE(num_pairs >= 1, "num_pairs must be at least 1");
+    CMX_REQUIRE(grids && point_clouds_xyz && num_points, "null argument");
+    int device = 0;
+    std::vector<cmx::RefineItem> items(num_pairs);
+    for (int p = 0; p < num_pairs; ++p) {
+      CMX_REQUIRE(grids[p] != nullptr, "null grid handle (pair %d)", p);
+      int device_p = 0;
+      items[p] = cmx::ResidentTsdfItem(grids[p], &device_p);
+      if (p == 0) device = device_p;
+      CMX_REQUIRE(device_p == device, "the grids of a call must live on one device (pair %d)", p);
+      // (an empty cloud is accepted, as by cmx_ceres2d_refine_batch_tsdf: FAILURE, pose untouched)
+      CMX_REQUIRE(point_clouds_xyz[p] != nullptr || num_points[p] == 0,
+                  "the point cloud of pair %d is null", p);
+      items[p].host_xyz = point_clouds_xyz[p];
+      items[p].n = num_points[p];
+    }
+    cmx::RefinePairs(options, &items, device, found, pose_estimates_in, pose_estimates_out,
+                     summaries);
   });
 }
 

@@ -3,6 +3,7 @@
 //   fast_2d_coarse.hip   scan preparation + lowest-resolution scoring (the front end)
 //   fast_2d.hip          branch and bound
 //   fast_2d_match.hip    MatchBatch, tie resolution, C ABI
+//   fast_2d_pairs.hip    lists of (node, submap) pairs: grouping into MatchBatch calls, C ABI
 // Every unit owns its kernels and exposes the host functions declared here; no kernel is launched
 // from another file than the one that defines it.
 #ifndef CMX_FAST_2D_INTERNAL_H_
@@ -129,6 +130,22 @@ void ReserveSearchScratch(Workspace& ws, int num, PreparedBatch* batch);
 void RunBranchAndBound(Workspace& ws, const PreparedBatch& batch, BatchResult* result);
 // Nanoseconds this thread's current call has spent in the final synchronisation (host_trace).
 extern thread_local long long g_host_wait_ns;
+
+// ---- fast_2d_match.hip
+// max ||p.xy|| over a host cloud, in f32 as SearchParameters computes it.
+float MaxRangeXY(const float* xyz, int n);
+// One cloud (`host_xyz`, uploaded here, or `cloud`, resident) of n points against `num` matchers
+// of ONE depth, entry p windowed around initial[p] or a full-submap search (`full_flags`, or
+// null: `full_submap` for all) against min_scores[p] (or null: `min_score` for all).
+// `allow_fanout`: a batch of 32 and more full-submap searches may go out as independent searches
+// over the host pool; false for a call that is itself an item of such a fan-out.
+void MatchBatch(const cmx_fast2d* const* handles, int num, const cmx_pose2d* initial,
+                bool full_submap, const float* host_xyz, const cmx_cloud* cloud, int n,
+                float min_score, int32_t* found, float* scores, cmx_pose2d* poses,
+                cmx_match_stats* stats, const int32_t* full_flags = nullptr,
+                const float* min_scores = nullptr, bool allow_fanout = true);
+// The sum of two calls' statistics, as the fan-out of a batch reports it.
+void AddMatchStats(const cmx_match_stats& part, cmx_match_stats* total);
 
 }  // namespace cmx
 

@@ -3,6 +3,8 @@
 //   fast_2d_stack.hip    precomputation-grid stack construction
 //   fast_2d_coarse.hip   scan preparation, lowest-resolution scoring
 //   fast_2d.hip          the batched branch and bound
+// Lists of (node, submap) pairs, each with its own cloud, are split into MatchBatch calls by
+// fast_2d_pairs.hip.
 // (shared declarations: fast_2d_internal.h, shared device helpers: fast_2d_device.h).
 //
 // Reference behaviour being replaced:
@@ -22,7 +24,6 @@
 #include "fast_2d_internal.h"
 
 namespace cmx {
-namespace {
 
 float MaxRangeXY(const float* xyz, int n) {
   float m = 0.f;
@@ -32,6 +33,8 @@ float MaxRangeXY(const float* xyz, int n) {
   }
   return m;
 }
+
+namespace {
 
 // Exact tie resolution.  When several leaves share the best score the
 // reference returns the one its depth-first search meets first, and at the top
@@ -186,11 +189,26 @@ void CheckProblemErrors(const BatchResult& r) {
 // (debug switch host_trace: where a caller's wall clock goes -- tools only)
 std::atomic<long long> g_host_calls{0}, g_host_total_ns{0}, g_host_waited_ns{0};
 
+}  // namespace
+
+void AddMatchStats(const cmx_match_stats& part, cmx_match_stats* total) {
+  total->candidates_scored += part.candidates_scored;
+  total->coarse_candidates += part.coarse_candidates;
+  total->nodes_expanded += part.nodes_expanded;
+  total->num_scans += part.num_scans;
+  total->device_ms += part.device_ms;                      // (sums over concurrent searches)
+  total->dominant_kernel_ms += part.dominant_kernel_ms;
+  total->expansion_ms += part.expansion_ms;
+  total->expansion_launches += part.expansion_launches;
+  total->expansion_nodes += part.expansion_nodes;
+  total->expansion_lookups += part.expansion_lookups;
+}
+
 void MatchBatch(const cmx_fast2d* const* handles, int num, const cmx_pose2d* initial,
                 bool full_submap, const float* host_xyz, const cmx_cloud* cloud, int n,
                 float min_score, int32_t* found, float* scores, cmx_pose2d* poses,
-                cmx_match_stats* stats, const int32_t* full_flags = nullptr,
-                const float* min_scores = nullptr) {
+                cmx_match_stats* stats, const int32_t* full_flags, const float* min_scores,
+                bool allow_fanout) {
   CMX_REQUIRE(handles != nullptr && num >= 1, "no matchers given");
   CMX_REQUIRE(num < (1 << 24), "too many matchers in one batch");
   CMX_REQUIRE(found != nullptr && scores != nullptr && poses != nullptr,
@@ -222,26 +240,15 @@ void MatchBatch(const cmx_fast2d* const* handles, int num, const cmx_pose2d* ini
   // them is cheaper in the batch's few launches than in five launches each)
   bool all_full = true;
   for (int p = 0; p < num && all_full; ++p) all_full = full_flags ? full_flags[p] != 0 : full_submap;
-  if (num >= fanout_from && all_full && OverrideStream(device) == nullptr) {
+  if (allow_fanout && num >= fanout_from && all_full && OverrideStream(device) == nullptr) {
     std::vector<cmx_match_stats> part(num);
     ParallelFor(num, 2, [&](int p) {
       MatchBatch(handles + p, 1, initial ? initial + p : nullptr, full_submap, host_xyz, cloud, n,
                  min_scores ? min_scores[p] : min_score, found + p, scores + p, poses + p, &part[p],
-                 full_flags ? full_flags + p : nullptr, nullptr);
+                 full_flags ? full_flags + p : nullptr, nullptr, /*allow_fanout=*/false);
     });
     cmx_match_stats total{};
-    for (const cmx_match_stats& st : part) {
-      total.candidates_scored += st.candidates_scored;
-      total.coarse_candidates += st.coarse_candidates;
-      total.nodes_expanded += st.nodes_expanded;
-      total.num_scans += st.num_scans;
-      total.device_ms += st.device_ms;                      // (sums over concurrent searches)
-      total.dominant_kernel_ms += st.dominant_kernel_ms;
-      total.expansion_ms += st.expansion_ms;
-      total.expansion_launches += st.expansion_launches;
-      total.expansion_nodes += st.expansion_nodes;
-      total.expansion_lookups += st.expansion_lookups;
-    }
+    for (const cmx_match_stats& st : part) AddMatchStats(st, &total);
     if (stats) *stats = total;
     return;
   }
@@ -331,7 +338,6 @@ void MatchBatch(const cmx_fast2d* const* handles, int num, const cmx_pose2d* ini
   if (stats) *stats = total;
 }
 
-}  // namespace
 }  // namespace cmx
 
 // ---------------------------------------------------------------------------

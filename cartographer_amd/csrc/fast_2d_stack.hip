@@ -22,11 +22,8 @@ constexpr int kMaxPlaneWidth = 128;    // w; plane index fits 14 bits
 // Level 0: ComputeCellValue(1 - |cost|)  (SM2/fast_...2d.cc:107-108,163-169)
 // with the per-grid cost table of mapping/value_conversion_tables.cc:29-51
 // evaluated arithmetically (same f32 expression the table is built from).
-__global__ void BuildLevel0Kernel(const uint16_t* __restrict__ cells, int count, float min_cc,
-                                  float max_cc, uint8_t* __restrict__ out) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= count) return;
-  const unsigned v = cells[i] & 0x7fffu;
+__device__ __forceinline__ uint8_t Level0Value(uint16_t cell, float min_cc, float max_cc) {
+  const unsigned v = cell & 0x7fffu;
   float cost;
   if (v == 0) {
     cost = max_cc;
@@ -38,7 +35,28 @@ __global__ void BuildLevel0Kernel(const uint16_t* __restrict__ cells, int count,
   const float min_s = 1.f - max_cc, max_s = 1.f - min_cc;
   int value = LRoundF32((probability - min_s) * (255.f / (max_s - min_s)));
   value = min(max(value, 0), 255);
-  out[i] = static_cast<uint8_t>(value);
+  return static_cast<uint8_t>(value);
+}
+
+__global__ void BuildLevel0Kernel(const uint16_t* __restrict__ cells, int count, float min_cc,
+                                  float max_cc, uint8_t* __restrict__ out) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= count) return;
+  out[i] = Level0Value(cells[i], min_cc, max_cc);
+}
+
+// The same from a grid plane resident in HBM: one pass reads the plane and writes the matcher's
+// own copy of the cells (the grid may be inserted into or destroyed once the matcher exists) and
+// level 0.
+__global__ void CopyCellsBuildLevel0Kernel(const uint16_t* __restrict__ cells, int count,
+                                           float min_cc, float max_cc,
+                                           uint16_t* __restrict__ copy,
+                                           uint8_t* __restrict__ out) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= count) return;
+  const uint16_t cell = cells[i];
+  copy[i] = cell;
+  out[i] = Level0Value(cell, min_cc, max_cc);
 }
 
 // Level w from level w/2: a w x w window is the union of four (w/2) x (w/2)
@@ -166,7 +184,7 @@ PlanMatcher PlanMatcherOf(const Fast2DMatcher& m) {
 // Fast2DMatcher (host)
 // ---------------------------------------------------------------------------
 Fast2DMatcher::Fast2DMatcher(const cmx_fast2d_options& options, const cmx_grid2d_limits& limits,
-                             const uint16_t* cells, int device)
+                             const uint16_t* cells, int device, bool cells_on_device)
     : options_(options), limits_(limits), device_(device) {
   // CHECKs of the reference: SM2/fast_...2d.cc:100-102,174; map_limits.h:45-47;
   // grid_2d.cc:73.
@@ -202,12 +220,17 @@ Fast2DMatcher::Fast2DMatcher(const cmx_fast2d_options& options, const cmx_grid2d
 
   const size_t count = static_cast<size_t>(nx) * ny;
   CMX_HIP(hipMalloc(reinterpret_cast<void**>(&grid_cells_), count * sizeof(uint16_t)));
-  uint16_t* d_cells = grid_cells_;
-  CMX_HIP(hipMemcpyAsync(d_cells, cells, count * sizeof(uint16_t), hipMemcpyHostToDevice,
-                         ws->stream));
-  BuildLevel0Kernel<<<DivUp(count, 256), 256, 0, ws->stream>>>(
-      d_cells, static_cast<int>(count), limits.min_correspondence_cost,
-      limits.max_correspondence_cost, const_cast<uint8_t*>(levels_[0].cells));
+  if (cells_on_device) {
+    CopyCellsBuildLevel0Kernel<<<DivUp(count, 256), 256, 0, ws->stream>>>(
+        cells, static_cast<int>(count), limits.min_correspondence_cost,
+        limits.max_correspondence_cost, grid_cells_, const_cast<uint8_t*>(levels_[0].cells));
+  } else {
+    CMX_HIP(hipMemcpyAsync(grid_cells_, cells, count * sizeof(uint16_t), hipMemcpyHostToDevice,
+                           ws->stream));
+    BuildLevel0Kernel<<<DivUp(count, 256), 256, 0, ws->stream>>>(
+        grid_cells_, static_cast<int>(count), limits.min_correspondence_cost,
+        limits.max_correspondence_cost, const_cast<uint8_t*>(levels_[0].cells));
+  }
   for (int i = 1; i < depth; ++i) {
     const LevelDesc& prev = levels_[i - 1];
     const LevelDesc& cur = levels_[i];
@@ -279,6 +302,16 @@ Fast2DMatcher::~Fast2DMatcher() {
   if (planes_) (void)hipFree(planes_);
   if (planes_group_) (void)hipFree(planes_group_);
   if (grid_cells_) (void)hipFree(grid_cells_);
+}
+
+// The matcher of a grid plane that lies in HBM on `device` (grid_2d.hip, tsdf_2d.hip): built
+// where the plane lies; the matcher keeps a copy of its own.
+cmx_fast2d* CreateFast2DFromDeviceCells(const cmx_fast2d_options& options,
+                                        const cmx_grid2d_limits& limits,
+                                        const uint16_t* device_cells, int device) {
+  std::unique_ptr<cmx_fast2d> h(new cmx_fast2d);
+  h->impl.reset(new Fast2DMatcher(options, limits, device_cells, device, /*cells_on_device=*/true));
+  return h.release();
 }
 
 }  // namespace cmx

@@ -517,13 +517,13 @@ extern "C" cmx_status cmx_fast2d_create_from_grid(const cmx_fast2d_options* opti
                                                   const cmx_grid2d* grid, cmx_fast2d** out) {
   return Guard([&] {
     CMX_REQUIRE(options && grid && out, "null argument");
-    // The finished submap's cells come back once; the stack is built on the device.
-    std::vector<uint16_t> cells(static_cast<size_t>(grid->nx) * grid->ny);
-    cmx::UseDevice(grid->device);
-    CMX_HIP(hipMemcpy(cells.data(), grid->cells, cells.size() * 2, hipMemcpyDeviceToHost));
+    // The stack is built from the cells where they lie: the matcher takes its own copy
+    // on the device (the grid may be inserted into or destroyed afterwards), nothing comes back
+    // to the host.  Every call that changes the grid has synchronised before it returned.
+    *out = nullptr;
     cmx_grid2d_limits limits;
-    cmx_status st = cmx_grid2d_get_limits(grid, &limits);
-    if (st == CMX_OK) st = cmx_fast2d_create(options, &limits, cells.data(), grid->device, out);
+    const cmx_status st = cmx_grid2d_get_limits(grid, &limits);
     if (st != CMX_OK) throw cmx::HipError{st};           // last error already set
+    *out = cmx::CreateFast2DFromDeviceCells(*options, limits, grid->cells, grid->device);
   });
 }

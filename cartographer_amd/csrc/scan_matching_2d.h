@@ -129,8 +129,10 @@ struct BestLeaf {           // per problem, device → host
 
 class Fast2DMatcher {
  public:
+  // `cells`: the grid on the host, or (cells_on_device) in HBM on `device`; either way the matcher
+  // keeps a copy of its own.
   Fast2DMatcher(const cmx_fast2d_options& options, const cmx_grid2d_limits& limits,
-                const uint16_t* cells, int device);
+                const uint16_t* cells, int device, bool cells_on_device = false);
   ~Fast2DMatcher();
   int device() const { return device_; }
   const cmx_fast2d_options& options() const { return options_; }
@@ -307,6 +309,13 @@ void Rt2DMatch(const cmx_rt_options* options, const cmx_grid2d_limits* limits,
 struct cmx_fast2d {
   std::unique_ptr<cmx::Fast2DMatcher> impl;
 };
+
+namespace cmx {
+// fast_2d_stack.hip: the matcher of a grid plane resident in HBM, built without a host copy.
+cmx_fast2d* CreateFast2DFromDeviceCells(const cmx_fast2d_options& options,
+                                        const cmx_grid2d_limits& limits,
+                                        const uint16_t* device_cells, int device);
+}  // namespace cmx
 
 struct cmx_cloud {
   int device = 0;

@@ -407,6 +407,59 @@ def match_batch(matchers, initial_pose_estimates, match_full_submap, min_scores,
     return found, scores, [Rigid2d(p.x, p.y, p.theta) for p in poses], stats.as_dict()
 
 
+def _pair_clouds(point_clouds):
+    """The clouds of a list of pairs as (resident, pointer array, counts, keep-alive list): all
+    arrays or all PointCloudOnDevice; an object that repeats in the list (one node in several
+    pairs) becomes a repeated pointer, so that the library sees one node."""
+    num = len(point_clouds)
+    resident = [isinstance(c, PointCloudOnDevice) for c in point_clouds]
+    if any(resident) and not all(resident):
+        raise ValueError("the clouds of a call are all arrays or all PointCloudOnDevice")
+    if num and all(resident):
+        pointers = (C.c_void_p * num)(*[c._h for c in point_clouds])
+        return True, pointers, None, list(point_clouds)
+    converted = {}
+    for c in point_clouds:
+        if id(c) not in converted:
+            converted[id(c)] = _cloud(c)[0]
+    arrays = [converted[id(c)] for c in point_clouds]
+    pointers = (C.c_void_p * num)(*[a.ctypes.data if a.shape[0] else None for a in arrays])
+    counts = np.array([a.shape[0] for a in arrays], np.int32)
+    return False, pointers, counts, arrays
+
+
+def match_pairs(matchers, initial_pose_estimates, match_full_submap, min_scores, point_clouds):
+    """cmx_fast2d_match_pairs[_resident]: a list of (node, submap) pairs, pair p its own cloud
+    point_clouds[p] against matchers[p] -- the burst of PoseGraph2D::ComputeConstraintsForNode
+    when a submap finishes (pose_graph_2d.cc:383-393), or any other list.  Entries as in
+    match_batch; `point_clouds` are arrays or PointCloudOnDevice (one kind per call), and an object
+    named by several pairs is one node.  `initial_pose_estimates` may be None when every pair is a
+    full-submap search.  Returns (found[int32], scores[float32], poses[list of Rigid2d],
+    stats dict); every pair's result is what the single call returns for it."""
+    num = len(matchers)
+    handles = (C.c_void_p * num)(*[m._h for m in matchers])
+    initial = None
+    if initial_pose_estimates is not None:
+        initial = (Pose2d * num)(*[p.to_c() for p in initial_pose_estimates])
+    full = np.ascontiguousarray(match_full_submap, np.int32)
+    thresholds = np.ascontiguousarray(min_scores, np.float32)
+    resident, pointers, counts, keep = _pair_clouds(point_clouds)
+    found = np.zeros(num, np.int32)
+    scores = np.zeros(num, np.float32)
+    poses = (Pose2d * num)()
+    stats = MatchStats()
+    L = _lib.lib()
+    head = (handles, num, None if initial is None else C.cast(initial, C.c_void_p),
+            full.ctypes.data, thresholds.ctypes.data, pointers)
+    tail = (found.ctypes.data, scores.ctypes.data, C.cast(poses, C.c_void_p), C.byref(stats))
+    if resident:
+        check(L.cmx_fast2d_match_pairs_resident(*head, *tail))
+    else:
+        check(L.cmx_fast2d_match_pairs(*head, counts.ctypes.data, *tail))
+    del keep
+    return found, scores, [Rigid2d(p.x, p.y, p.theta) for p in poses], stats.as_dict()
+
+
 class CeresScanMatcher2D:
     """CeresScanMatcher2D(options).Match(target_translation, initial_pose_estimate, point_cloud,
     grid) -> (pose_estimate, summary)  (ceres_scan_matcher_2d.h:44-56).  `grid` is a Grid2D or a
@@ -485,6 +538,45 @@ class CeresScanMatcher2D:
             C.cast(poses_out, C.c_void_p), C.cast(summaries, C.c_void_p)))
         return ([Rigid2d(p.x, p.y, p.theta) for p in poses_out],
                 [s_.as_dict() for s_ in summaries])
+
+
+    def _refine_pairs(self, entry, resident_entry, handles_of, found, pose_estimates,
+                      point_clouds):
+        num = len(handles_of)
+        handles = (C.c_void_p * num)(*[h._h for h in handles_of])
+        found = None if found is None else np.ascontiguousarray(found, np.int32)
+        poses_in = (Pose2d * num)(*[p.to_c() for p in pose_estimates])
+        poses_out = (Pose2d * num)()
+        summaries = (CeresSummary * num)()
+        resident, pointers, counts, keep = _pair_clouds(point_clouds)
+        head = (C.byref(self.options), handles, num, None if found is None else found.ctypes.data,
+                C.cast(poses_in, C.c_void_p), pointers)
+        tail = (C.cast(poses_out, C.c_void_p), C.cast(summaries, C.c_void_p))
+        if resident:
+            if resident_entry is None:
+                raise ValueError("this refinement takes host clouds")
+            check(resident_entry(*head, *tail))
+        else:
+            check(entry(*head, counts.ctypes.data, *tail))
+        del keep
+        return ([Rigid2d(p.x, p.y, p.theta) for p in poses_out],
+                [s_.as_dict() for s_ in summaries])
+
+    def refine_pairs(self, matchers, found, pose_estimates, point_clouds):
+        """cmx_fast2d_refine_pairs[_resident]: refine_batch for the results of match_pairs, pair
+        p with its own cloud point_clouds[p] (arrays or PointCloudOnDevice, one kind per call;
+        an object named by several pairs is staged once), in ONE launch for the whole list.
+        found[p] == 0 passes through; found=None refines every pair."""
+        L = _lib.lib()
+        return self._refine_pairs(L.cmx_fast2d_refine_pairs, L.cmx_fast2d_refine_pairs_resident,
+                                  matchers, found, pose_estimates, point_clouds)
+
+    def refine_pairs_tsdf(self, grids, found, pose_estimates, point_clouds):
+        """cmx_ceres2d_refine_pairs_tsdf: the same against finished TSDF submaps kept in HBM
+        (TSDF2DOnDevice), pair p with its own host cloud; an empty cloud ends with FAILURE and
+        the pose untouched, as in refine_batch_tsdf."""
+        return self._refine_pairs(_lib.lib().cmx_ceres2d_refine_pairs_tsdf, None, grids, found,
+                                  pose_estimates, point_clouds)
 
 
 def tsdf_match_residuals(grid, residual_scaling_factor, pose, point_cloud, device=0):

@@ -462,6 +462,73 @@ cmx_status cmx_ceres2d_refine_batch_tsdf(const cmx_ceres2d_options* options,
                                          const float* point_cloud_xyz, int32_t num_points,
                                          cmx_pose2d* pose_estimates_out,
                                          cmx_ceres_summary* summaries);
+
+/* ---- many nodes against 2D submaps: lists of (node, submap) pairs ------------------------- */
+/* The other half of PoseGraph2D::ComputeConstraintsForNode (pose_graph_2d.cc:383-393: when a
+ * submap finishes, every old node is matched against it) and any other list of (node, submap)
+ * pairs: as cmx_fast2d_match_batch, but pair p brings its own cloud.  num_pairs >= 1.
+ *   - found[p], scores[p] and pose_estimates[p] are bit for bit what cmx_fast2d_match returns for
+ *     (matchers[p], cloud p, initial_pose_estimates[p], min_scores[p]) -- where
+ *     match_full_submap[p] != 0, what cmx_fast2d_match_full_submap returns.
+ *     initial_pose_estimates may be NULL only if every pair is a full-submap search.
+ *   - Entries of point_clouds_xyz / clouds may repeat: equal pointers are the same node, and a
+ *     host cloud is uploaded once per distinct pointer, not once per pair.  The num_points of
+ *     equal pointers must agree (else CMX_INVALID_ARGUMENT).  A null or empty cloud is
+ *     CMX_INVALID_ARGUMENT, as in the single calls.
+ *   - Matchers of different branch_and_bound_depth may appear in one list.
+ *   - All matchers (and clouds) of a call live on one device; a mixed list is
+ *     CMX_INVALID_ARGUMENT before anything is launched.
+ *   - The pairs are grouped by (cloud, depth).  A group is one cmx_fast2d_match_batch: the pairs
+ *     of a node share that node's launches.  Several groups run concurrently, each on a stream
+ *     of its own; under a cmx_set_stream override of the calling thread they run one after the
+ *     other on that stream.  Pairs of different clouds do not share launches.
+ *   - The first error by pair index is the call's error.  *stats is the sum over the pairs.
+ *   - Without a HIP device: CMX_DEVICE_ERROR ("no CPU fallback"), whatever the arguments.
+ * The _resident entry takes clouds uploaded by cmx_cloud_upload and uploads nothing. */
+cmx_status cmx_fast2d_match_pairs(const cmx_fast2d* const* matchers, int32_t num_pairs,
+                                  const cmx_pose2d* initial_pose_estimates,
+                                  const int32_t* match_full_submap, const float* min_scores,
+                                  const float* const* point_clouds_xyz, const int32_t* num_points,
+                                  int32_t* found, float* scores, cmx_pose2d* pose_estimates,
+                                  cmx_match_stats* stats);
+cmx_status cmx_fast2d_match_pairs_resident(const cmx_fast2d* const* matchers, int32_t num_pairs,
+                                           const cmx_pose2d* initial_pose_estimates,
+                                           const int32_t* match_full_submap,
+                                           const float* min_scores,
+                                           const cmx_cloud* const* clouds, int32_t* found,
+                                           float* scores, cmx_pose2d* pose_estimates,
+                                           cmx_match_stats* stats);
+/* The refinement of those results (constraint_builder_2d.cc:245-249) in ONE launch, one result
+ * copy and one synchronisation for the whole list: entry p is bit for bit what
+ * cmx_fast2d_refine_batch (cmx_ceres2d_refine_batch_tsdf for the _tsdf entry) returns for that
+ * pair alone, the pass-through of found[p] == 0 included (found may be NULL: every pair is
+ * refined).  Clouds may repeat as above (a host cloud is staged once per distinct pointer), all
+ * matchers / grids (and clouds) live on one device, num_pairs >= 1; a null or empty cloud is
+ * CMX_INVALID_ARGUMENT, except that the TSDF entry accepts num_points[p] == 0 as
+ * cmx_ceres2d_refine_batch_tsdf does (FAILURE, the pose untouched).  Without a HIP device:
+ * CMX_DEVICE_ERROR ("no CPU fallback"), whatever the arguments. */
+cmx_status cmx_fast2d_refine_pairs(const cmx_ceres2d_options* options,
+                                   const cmx_fast2d* const* matchers, int32_t num_pairs,
+                                   const int32_t* found, const cmx_pose2d* pose_estimates_in,
+                                   const float* const* point_clouds_xyz,
+                                   const int32_t* num_points, cmx_pose2d* pose_estimates_out,
+                                   cmx_ceres_summary* summaries);
+cmx_status cmx_fast2d_refine_pairs_resident(const cmx_ceres2d_options* options,
+                                            const cmx_fast2d* const* matchers, int32_t num_pairs,
+                                            const int32_t* found,
+                                            const cmx_pose2d* pose_estimates_in,
+                                            const cmx_cloud* const* clouds,
+                                            cmx_pose2d* pose_estimates_out,
+                                            cmx_ceres_summary* summaries);
+cmx_status cmx_ceres2d_refine_pairs_tsdf(const cmx_ceres2d_options* options,
+                                         const cmx_tsdf2d* const* grids, int32_t num_pairs,
+                                         const int32_t* found,
+                                         const cmx_pose2d* pose_estimates_in,
+                                         const float* const* point_clouds_xyz,
+                                         const int32_t* num_points,
+                                         cmx_pose2d* pose_estimates_out,
+                                         cmx_ceres_summary* summaries);
+
 cmx_status cmx_ceres2d_tsdf_residuals(const cmx_grid2d_limits* limits, const uint16_t* tsd_cells,
                                       const uint16_t* weight_cells, float truncation_distance,
                                       float max_weight, double residual_scaling_factor,
