@@ -198,6 +198,13 @@ Fast2DMatcher::Fast2DMatcher(const cmx_fast2d_options& options, const cmx_grid2d
               "grid larger than 16384 cells per side is unsupported");
   CMX_REQUIRE(limits.min_correspondence_cost < limits.max_correspondence_cost,
               "min_correspondence_cost must be < max_correspondence_cost");
+  // The search orders scores by their f32 bit patterns and marks "no candidate" with a negative
+  // value: both need every score, 1 - max_correspondence_cost at the least, to be >= 0.
+  CMX_REQUIRE(limits.max_correspondence_cost <= 1.f,
+              "max_correspondence_cost %g > 1 is unsupported: scores down to %g would be "
+              "negative, which the search cannot represent",
+              static_cast<double>(limits.max_correspondence_cost),
+              1. - static_cast<double>(limits.max_correspondence_cost));
   WorkspaceLease ws(device);
   const int nx = limits.num_x_cells, ny = limits.num_y_cells;
   const int depth = options.branch_and_bound_depth;

@@ -198,7 +198,9 @@ cmx_status cmx_rt2d_score_candidates(const cmx_rt_options* options,
 /* The active submap's ProbabilityGrid kept in HBM: LocalTrajectoryBuilder2D's per-scan
  * pair Match() -> InsertRangeData() (mapping/internal/2d/local_trajectory_builder_2d.cc:
  * 78-80, :288-289) then moves only the scan across PCIe.
- *   cmx_grid2d_create     ProbabilityGrid(limits) (all unknown) or a copy of `cells`
+ *   cmx_grid2d_create     ProbabilityGrid(limits) (all unknown) or a copy of `cells`; the cost
+ *                         bounds of `limits` are ignored, the grid always has the probability
+ *                         range (so cmx_fast2d_create_from_grid never meets another one)
  *   cmx_grid2d_insert     ProbabilityGridRangeDataInserter2D::Insert + FinishUpdate
  *                         (mapping/2d/probability_grid_range_data_inserter_2d.cc:33-96,
  *                          mapping/internal/2d/ray_to_pixel_mask.cc:34-156); grows the
@@ -267,7 +269,8 @@ cmx_status cmx_rt2d_match_grid_batch_resident(const cmx_rt_options* options,
  *   cmx_tsdf2d_crop       grid = grid->ComputeCroppedGrid() (tsdf_2d.cc:118-135)
  *   cmx_rt2d_match_tsdf_grid  cmx_rt2d_match_tsdf with the planes read from HBM
  *   cmx_fast2d_create_from_tsdf  FastCorrelativeScanMatcher2D of the tsd plane over the cost
- *                         range [-truncation, truncation] */
+ *                         range [-truncation, truncation]; truncation > 1 is
+ *                         CMX_INVALID_ARGUMENT (see cmx_fast2d_create) */
 /* proto::TSDFRangeDataInserterOptions2D with its proto::NormalEstimationOptions2D
  * (num_normal_samples > 0 and sample_radius > 0, normal_estimation_2d.cc:64-74). */
 typedef struct cmx_tsdf_inserter_options_2d {
@@ -327,7 +330,14 @@ cmx_status cmx_fast2d_create_from_tsdf(const cmx_fast2d_options* options, const 
 
 /* ---- fast 2D (branch and bound) ---------------------------------------- */
 /* Uploads the grid and builds the PrecomputationGridStack2D on `device`
- * (SM2/fast_correlative_scan_matcher_2d.cc:171-186). */
+ * (SM2/fast_correlative_scan_matcher_2d.cc:171-186).
+ * This call and _from_tsdf above take any cost range with
+ * min_correspondence_cost < max_correspondence_cost <= 1 (_from_grid always gets the probability
+ * range of a cmx_grid2d).  A range with
+ * max_correspondence_cost > 1 (a TSDF2D whose truncation distance exceeds 1 m) is
+ * CMX_INVALID_ARGUMENT: scores go down to 1 - max_correspondence_cost, and the search cannot
+ * represent negative scores.  Scores above 1 are fine (a TSDF's perfect hit is 1.00118 at
+ * truncation distance 0.3), and so is a negative min_score. */
 cmx_status cmx_fast2d_create(const cmx_fast2d_options* options, const cmx_grid2d_limits* limits,
                              const uint16_t* cells, int32_t device, cmx_fast2d** out);
 cmx_status cmx_fast2d_create_from_grid(const cmx_fast2d_options* options, const cmx_grid2d* grid,

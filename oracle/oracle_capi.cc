@@ -169,6 +169,19 @@ void* orc_fast2d_create(const uint16_t* cells, int nx, int ny, double res, doubl
       MakeView(f->cells.data(), nx, ny, res, max_x, max_y), depth, lin, ang));
   return f;
 }
+// The same over a Grid2D with other correspondence-cost bounds (a TSDF2D's tsd plane:
+// min = -truncation_distance, max = truncation_distance).
+void* orc_fast2d_create_range(const uint16_t* cells, int nx, int ny, double res, double max_x,
+                              double max_y, int depth, double lin, double ang, float min_cc,
+                              float max_cc) {
+  auto* f = new Fast2D;
+  f->cells.assign(cells, cells + static_cast<size_t>(nx) * ny);
+  ProbabilityGridView view = MakeView(f->cells.data(), nx, ny, res, max_x, max_y);
+  view.min_correspondence_cost = min_cc;
+  view.max_correspondence_cost = max_cc;
+  f->matcher.reset(new FastCorrelativeScanMatcher2D(view, depth, lin, ang));
+  return f;
+}
 void orc_fast2d_destroy(void* h) { delete static_cast<Fast2D*>(h); }
 
 void orc_fast2d_level_dims(void* h, int level, int* wx, int* wy) {

@@ -71,6 +71,10 @@ def _declare(L):
     L.orc_fast2d_create.argtypes = [_u16p, C.c_int, C.c_int, C.c_double, C.c_double,
                                     C.c_double, C.c_int, C.c_double, C.c_double]
     L.orc_fast2d_create.restype = C.c_void_p
+    L.orc_fast2d_create_range.argtypes = [_u16p, C.c_int, C.c_int, C.c_double, C.c_double,
+                                          C.c_double, C.c_int, C.c_double, C.c_double, C.c_float,
+                                          C.c_float]
+    L.orc_fast2d_create_range.restype = C.c_void_p
     L.orc_fast2d_destroy.argtypes = [C.c_void_p]
     L.orc_fast2d_level_dims.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int),
                                         C.POINTER(C.c_int)]
@@ -94,7 +98,10 @@ _REF = os.path.join(_HERE, "_ref", "libref.so")
 _ref_lib = None
 
 
-def build_ref(reference="/root/reference"):
+REFERENCE = "/root/reference"
+
+
+def build_ref(reference=REFERENCE):
     """`make -C oracle ref` when the reference tree is present (it is not on the GPU box)."""
     if os.path.isdir(os.path.join(reference, "cartographer")):
         subprocess.check_call(["make", "-C", _HERE, "ref", f"REFERENCE={reference}"],
@@ -106,7 +113,7 @@ _REF_CERES = os.path.join(_HERE, "_ref", "libref_ceres.so")
 _ref_ceres_lib = None
 
 
-def build_ref_ceres(reference="/root/reference"):
+def build_ref_ceres(reference=REFERENCE):
     """`make -C oracle ref_ceres` when the reference tree is present."""
     if os.path.isdir(os.path.join(reference, "cartographer")):
         subprocess.check_call(["make", "-C", _HERE, "ref_ceres", f"REFERENCE={reference}"],
@@ -148,7 +155,9 @@ def ref_lib():
     """The reference's own probability_values / value_conversion_tables / ray_to_pixel_mask
     code, or None when it has not been built (no /root/reference)."""
     global _ref_lib
-    if _ref_lib is None and (os.path.exists(_REF) or build_ref()):
+    # (make first wherever the reference tree is: a library that is there already may be older
+    # than ref_wrapper.cc, and a failing build must not pass for "no reference")
+    if _ref_lib is None and build_ref():
         L = C.CDLL(_REF)
         L.ref_ray_to_pixel_mask.argtypes = [C.c_int] * 5 + [_i32p, C.c_int]
         L.ref_value_tables.argtypes = [_f32p, _f32p]
@@ -163,6 +172,12 @@ def ref_lib():
         L.ref_fast2d_create.argtypes = [_u16p, C.c_int, C.c_int, C.c_double, C.c_double,
                                         C.c_double, C.c_int, C.c_double, C.c_double]
         L.ref_fast2d_create.restype = C.c_void_p
+        # (a prebuilt library on a machine without the reference tree may predate this one)
+        if hasattr(L, "ref_fast2d_create_tsdf"):
+            L.ref_fast2d_create_tsdf.argtypes = [_u16p, _u16p, C.c_int, C.c_int, C.c_double,
+                                                 C.c_double, C.c_double, C.c_float, C.c_float,
+                                                 C.c_int, C.c_double, C.c_double]
+            L.ref_fast2d_create_tsdf.restype = C.c_void_p
         L.ref_fast2d_destroy.argtypes = [C.c_void_p]
         L.ref_fast2d_match.argtypes = [C.c_void_p, C.c_int, _f64p, _f32p, C.c_int, C.c_float,
                                        C.POINTER(C.c_float), _f64p]
@@ -357,6 +372,21 @@ class ReferenceFastCorrelativeScanMatcher2D:
         ny, nx = cells.shape
         self._h = ref_lib().ref_fast2d_create(cells, nx, ny, res, max_x, max_y, depth,
                                               linear_search_window, angular_search_window)
+
+    @classmethod
+    def over_tsdf(cls, tsd_cells, weight_cells, res, max_x, max_y, truncation_distance,
+                  max_weight, depth, linear_search_window=7.0,
+                  angular_search_window=float(np.deg2rad(30.0))):
+        """The same matcher over the reference's own TSDF2D (two uint16 planes)."""
+        tsd = np.ascontiguousarray(tsd_cells, np.uint16)
+        wgt = np.ascontiguousarray(weight_cells, np.uint16)
+        assert tsd.shape == wgt.shape
+        ny, nx = tsd.shape
+        self = cls.__new__(cls)
+        self._h = ref_lib().ref_fast2d_create_tsdf(tsd, wgt, nx, ny, res, max_x, max_y,
+                                                   truncation_distance, max_weight, depth,
+                                                   linear_search_window, angular_search_window)
+        return self
 
     def __del__(self):
         if getattr(self, "_h", None):
@@ -594,12 +624,22 @@ class FastCorrelativeScanMatcher2D:
     """Oracle twin of fast_correlative_scan_matcher_2d.h:114-136."""
 
     def __init__(self, cells, res, max_x, max_y, depth, linear_search_window=7.0,
-                 angular_search_window=np.deg2rad(30.0)):
+                 angular_search_window=np.deg2rad(30.0), min_correspondence_cost=None,
+                 max_correspondence_cost=None):
+        """With both bounds None the grid is a probability grid; otherwise `cells` is a Grid2D
+        plane with those correspondence-cost bounds (a TSDF2D's tsd plane: -truncation_distance,
+        truncation_distance)."""
         cells = np.ascontiguousarray(cells, np.uint16)
         self.ny, self.nx = cells.shape
         self.depth = depth
-        self._h = lib().orc_fast2d_create(cells, self.nx, self.ny, res, max_x, max_y, depth,
-                                          linear_search_window, angular_search_window)
+        if min_correspondence_cost is None and max_correspondence_cost is None:
+            self._h = lib().orc_fast2d_create(cells, self.nx, self.ny, res, max_x, max_y, depth,
+                                              linear_search_window, angular_search_window)
+        else:
+            assert min_correspondence_cost is not None and max_correspondence_cost is not None
+            self._h = lib().orc_fast2d_create_range(
+                cells, self.nx, self.ny, res, max_x, max_y, depth, linear_search_window,
+                angular_search_window, min_correspondence_cost, max_correspondence_cost)
 
     def __del__(self):
         if getattr(self, "_h", None):

@@ -142,7 +142,7 @@ std::unique_ptr<cm::TSDF2D> MakeTsdf(const uint16_t* cells, const uint16_t* weig
 
 struct RefFast2D {
   cm::ValueConversionTables tables;
-  std::unique_ptr<cm::ProbabilityGrid> grid;
+  std::unique_ptr<cm::Grid2D> grid;
   std::unique_ptr<sm::FastCorrelativeScanMatcher2D> matcher;
   sm::proto::FastCorrelativeScanMatcherOptions2D options;
 };
@@ -156,6 +156,21 @@ void* ref_fast2d_create(const uint16_t* cells, int nx, int ny, double resolution
                         double angular_search_window) {
   auto* f = new RefFast2D;
   f->grid = MakeProbabilityGrid(cells, nx, ny, resolution, max_x, max_y, &f->tables);
+  f->options.set_linear_search_window(linear_search_window);
+  f->options.set_angular_search_window(angular_search_window);
+  f->options.set_branch_and_bound_depth(depth);
+  f->matcher.reset(new sm::FastCorrelativeScanMatcher2D(*f->grid, f->options));
+  return f;
+}
+// The same over the reference's TSDF2D: the matcher takes any Grid2D and reads its
+// correspondence-cost bounds, -truncation_distance and truncation_distance here.
+void* ref_fast2d_create_tsdf(const uint16_t* cells, const uint16_t* weight_cells, int nx, int ny,
+                             double resolution, double max_x, double max_y,
+                             float truncation_distance, float max_weight, int depth,
+                             double linear_search_window, double angular_search_window) {
+  auto* f = new RefFast2D;
+  f->grid = MakeTsdf(cells, weight_cells, nx, ny, resolution, max_x, max_y, truncation_distance,
+                     max_weight, &f->tables);
   f->options.set_linear_search_window(linear_search_window);
   f->options.set_angular_search_window(angular_search_window);
   f->options.set_branch_and_bound_depth(depth);

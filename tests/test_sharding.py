@@ -124,3 +124,39 @@ def test_c_abi_partition_and_key_equal_the_python_rules():
             fb, sb = np.ascontiguousarray(found[b:e]), np.ascontiguousarray(scores[b:e])
             keys.append(L.cmx_pack_best_key(fb.ctypes.data, sb.ctypes.data, e - b, b))
         assert max(keys) == whole and sharding.unpack_best_key(whole)[1] == 2
+
+
+@pytest.mark.parametrize("score", [0.0, 0.7, 1.0011765])
+def test_key_roundtrip_of_scores_outside_the_probability_range(score):
+    """Scores of a fast 2D search over a TSDF's tsd plane: 0.0 (everything outside, truncation
+    distance 1.0), 0.7 (the floor at truncation distance 0.3) and 1.0011765 (a perfect hit there,
+    0.7 + 128 * 0.6 / 255 > 1).  Both implementations of the key keep the f32 bits and the index,
+    a found 0.0 stays distinct from "nothing found", and a larger score wins the max."""
+    import ctypes as C
+    from cartographer_amd import _lib
+    L = _lib.lib()
+    s = np.array([score], np.float32)
+    one = np.array([1], np.int32)
+    key = sharding.pack_best_key(one, s, 17)
+    assert key == L.cmx_pack_best_key(one.ctypes.data, s.ctypes.data, 1, 17)
+    assert key > sharding.NOT_FOUND
+    got, gid = sharding.unpack_best_key(key)
+    assert gid == 17 and np.float32(got).view(np.uint32) == s.view(np.uint32)[0]
+    f, sc, g = C.c_int32(), C.c_float(), C.c_int64()
+    L.cmx_unpack_best_key(key, C.byref(f), C.byref(sc), C.byref(g))
+    assert f.value == 1 and g.value == 17
+    assert np.float32(sc.value).view(np.uint32) == s.view(np.uint32)[0]
+    # a larger score wins the max whatever the indices; the next f32 up is enough
+    for larger in (np.nextafter(s[0], np.float32(2.0)), np.float32(1.3)):
+        big = np.array([larger], np.float32)
+        for low_id, high_id in ((3, 900), (900, 3)):
+            a = L.cmx_pack_best_key(one.ctypes.data, s.ctypes.data, 1, low_id)
+            b = L.cmx_pack_best_key(one.ctypes.data, big.ctypes.data, 1, high_id)
+            assert b == sharding.pack_best_key(one, big, high_id)
+            assert max(a, b) == b and sharding.unpack_best_key(max(a, b))[1] == high_id
+    # within one call: [score, larger, score] picks the middle one
+    three = np.array([score, 1.3, score], np.float32)
+    found = np.array([1, 1, 1], np.int32)
+    key = L.cmx_pack_best_key(found.ctypes.data, three.ctypes.data, 3, 40)
+    assert key == sharding.pack_best_key(found, three, 40)
+    assert sharding.unpack_best_key(key) == (pytest.approx(float(np.float32(1.3))), 41)

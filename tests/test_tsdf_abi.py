@@ -74,3 +74,21 @@ def test_insert_golden_regenerates_identically(oracle):
     assert sorted(fresh) == sorted(stored.files)
     for key, value in fresh.items():
         np.testing.assert_array_equal(np.asarray(value), stored[key], err_msg=key)
+
+
+def test_fast2d_refuses_a_cost_range_with_negative_scores():
+    """cmx_fast2d_create checks the range before it touches the device: max_correspondence_cost
+    > 1 (a TSDF2D truncated beyond 1 m) would give scores down to 1 - max < 0, which the search
+    cannot represent.  CMX_INVALID_ARGUMENT with the reason, with or without a device."""
+    from cartographer_amd import _lib
+    L = _lib.lib()
+    cells = np.zeros((16, 16), np.uint16)
+    options = _lib.Fast2DOptions(1.0, 0.3, 3)
+    for max_cc in (1.5, float(np.nextafter(np.float32(1.0), np.float32(2.0)))):
+        lim = _lib.Grid2DLimits(0.05, 1.0, 1.0, 16, 16, -max_cc, max_cc)
+        h = C.c_void_p()
+        assert L.cmx_fast2d_create(C.byref(options), C.byref(lim), cells.ctypes.data, 0,
+                                   C.byref(h)) == _lib.INVALID_ARGUMENT
+        assert not h
+        message = L.cmx_last_error().decode()
+        assert "max_correspondence_cost" in message and "negative" in message
