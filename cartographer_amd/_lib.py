@@ -45,6 +45,13 @@ class Fast2DOptions(C.Structure):
                 ("branch_and_bound_depth", C.c_int32)]
 
 
+class Fast2DSource(C.Structure):
+    """cmx_fast2d_source: one submap of cmx_fast2d_create_batch; exactly one of (limits, cells),
+    grid, tsdf is set."""
+    _fields_ = [("limits", C.POINTER(Grid2DLimits)), ("cells", C.c_void_p), ("grid", C.c_void_p),
+                ("tsdf", C.c_void_p)]
+
+
 class TSDFInserterOptions2D(C.Structure):
     """cmx_tsdf_inserter_options_2d = proto::TSDFRangeDataInserterOptions2D (+ the
     NormalEstimationOptions2D it holds)."""
@@ -177,7 +184,8 @@ EXPORTED_SYMBOLS = [
     "cmx_rt2d_match_grid_batch", "cmx_rt2d_match_grid_batch_resident",
     "cmx_grid3d_create", "cmx_grid3d_destroy", "cmx_grid3d_insert", "cmx_grid3d_info",
     "cmx_grid3d_download",
-    "cmx_fast2d_create", "cmx_fast2d_create_from_grid", "cmx_fast2d_destroy", "cmx_fast2d_match",
+    "cmx_fast2d_create", "cmx_fast2d_create_from_grid", "cmx_fast2d_create_batch",
+    "cmx_fast2d_destroy", "cmx_fast2d_match",
     "cmx_fast2d_match_full_submap", "cmx_fast2d_match_batch",
     "cmx_fast2d_match_pairs", "cmx_fast2d_match_pairs_resident",
     "cmx_fast2d_refine_pairs", "cmx_fast2d_refine_pairs_resident",
@@ -298,6 +306,9 @@ def lib():
     L.cmx_fast2d_create_from_tsdf.argtypes = [P(Fast2DOptions), C.c_void_p, P(C.c_void_p)]
     L.cmx_fast2d_create.argtypes = [P(Fast2DOptions), P(Grid2DLimits), C.c_void_p, C.c_int32,
                                     P(C.c_void_p)]
+    if hasattr(L, "cmx_fast2d_create_batch"):   # (absent from an older library an A/B tool loads)
+        L.cmx_fast2d_create_batch.argtypes = [P(Fast2DOptions), P(Fast2DSource), C.c_int32,
+                                              C.c_int32, P(C.c_void_p)]
     L.cmx_fast2d_destroy.argtypes = [C.c_void_p]
     L.cmx_fast2d_destroy.restype = None
     L.cmx_fast2d_match.argtypes = [C.c_void_p, P(Pose2d), C.c_void_p, C.c_int32, C.c_float,

@@ -11,7 +11,10 @@ precomputation stacks that stay resident in HBM, keyed by ``SubmapId``, until
 ``DeleteScanMatcher`` (:307-316) frees them.  With ``pairs=True`` everything pending -- the
 pairs of however many nodes, as in the burst of ``PoseGraph2D::ComputeConstraintsForNode`` when a
 submap finishes (``pose_graph_2d.cc:383-393``) -- goes out in one ``cmx_fast2d_match_pairs``
-call and, with ``ceres``, one ``cmx_fast2d_refine_pairs`` launch.
+call and, with ``ceres``, one ``cmx_fast2d_refine_pairs`` launch.  With ``batch_create=True`` the
+matchers the pending pairs still lack are built at the flush by one ``cmx_fast2d_create_batch``
+call (``DispatchScanMatcherConstruction``, :165-186, for every new submap at once) instead of
+one constructor call per submap when its first pair is added.
 
 Not built: the Ceres refinement of :240-249.  ``refine`` may be given a
 callable ``(pose_estimate, point_cloud, grid) -> Rigid2d`` standing in for it; by default the
@@ -114,7 +117,12 @@ class _Pending:
 
 class ConstraintBuilder2D:
     def __init__(self, options: ConstraintBuilderOptions, device: int = 0,
-                 refine: Optional[Callable] = None, ceres=None, pairs: bool = False):
+                 refine: Optional[Callable] = None, ceres=None, pairs: bool = False,
+                 batch_create: bool = False):
+        # `batch_create`: a submap's matcher is not built when its first pair is added but with
+        # all the other missing ones of the pending list, in one cmx_fast2d_create_batch call,
+        # right before the searches (a node's first global constraint against every finished
+        # submap: one chain of launches instead of one constructor per submap); same constraints.
         # `ceres`: a scan_matching.CeresScanMatcher2D, the builder's ceres_scan_matcher_; the
         # found pairs of a node are refined by one cmx_fast2d_refine_batch launch.
         # `pairs`: everything pending goes out in one cmx_fast2d_match_pairs call (and one
@@ -124,6 +132,7 @@ class ConstraintBuilder2D:
         self.refine = refine
         self.ceres = ceres
         self.pairs = pairs
+        self.batch_create = batch_create
         self.last_refine_summaries = None
         self._scan_matchers: Dict[SubmapId, FastCorrelativeScanMatcher2D] = {}
         self._samplers: Dict[SubmapId, FixedRatioSampler] = {}
@@ -182,10 +191,12 @@ class ConstraintBuilder2D:
         self._constraints.append(None)
         # DispatchScanMatcherConstruction (:165-186): one matcher per submap id, built once.
         if submap_id not in self._scan_matchers:
-            self._scan_matchers[submap_id] = FastCorrelativeScanMatcher2D(
-                submap.grid, self.options.branch_and_bound_depth,
-                self.options.linear_search_window, self.options.angular_search_window,
-                device=self.device)
+            # (batch_create: the entry marks the submap, _flush builds its matcher)
+            self._scan_matchers[submap_id] = None if self.batch_create else \
+                FastCorrelativeScanMatcher2D(
+                    submap.grid, self.options.branch_and_bound_depth,
+                    self.options.linear_search_window, self.options.angular_search_window,
+                    device=self.device)
         # Pairs that share the caller's point-cloud object (one node's constant data) go
         # into the same device batch.
         xyz, _ = _cloud(point_cloud)
@@ -193,8 +204,33 @@ class ConstraintBuilder2D:
                                       id(point_cloud), full, initial_relative_pose,
                                       self._scan_matchers[submap_id]))
 
+    def _create_missing(self, pending):
+        """batch_create: the matchers the pending pairs still lack, in one call.  A submap whose
+        entry was deleted since (delete_scan_matcher) gets a matcher for its scheduled pairs only,
+        as the reference keeps a scheduled pair's matcher alive."""
+        missing: Dict[SubmapId, Submap2D] = {}
+        for item in pending:
+            if item.matcher is None and self._scan_matchers.get(item.submap_id) is None:
+                missing.setdefault(item.submap_id, item.submap)
+        if missing:
+            built = FastCorrelativeScanMatcher2D.create_batch(
+                [submap.grid for submap in missing.values()],
+                self.options.branch_and_bound_depth, self.options.linear_search_window,
+                self.options.angular_search_window, device=self.device)
+            built = dict(zip(missing.keys(), built))
+            for submap_id in built:
+                if submap_id in self._scan_matchers:
+                    self._scan_matchers[submap_id] = built[submap_id]
+        else:
+            built = {}
+        for item in pending:
+            if item.matcher is None:
+                item.matcher = self._scan_matchers.get(item.submap_id) or built[item.submap_id]
+
     def _flush(self):
         pending, self._pending = self._pending, []
+        if self.batch_create:
+            self._create_missing(pending)
         groups: Dict[int, List[_Pending]] = {}
         for item in pending:                      # one batch per point cloud (= per node)
             groups.setdefault(item.cloud_key, []).append(item)

@@ -127,6 +127,13 @@ struct BestLeaf {           // per problem, device → host
   int pad0, pad1;
 };
 
+// One submap of Fast2DMatcher::BuildBatch: what the single constructor takes.
+struct Fast2DSource {
+  cmx_grid2d_limits limits;
+  const uint16_t* cells;           // host, or (cells_on_device) in HBM on the call's device
+  bool cells_on_device;
+};
+
 class Fast2DMatcher {
  public:
   // `cells`: the grid on the host, or (cells_on_device) in HBM on `device`; either way the matcher
@@ -134,6 +141,17 @@ class Fast2DMatcher {
   Fast2DMatcher(const cmx_fast2d_options& options, const cmx_grid2d_limits& limits,
                 const uint16_t* cells, int device, bool cells_on_device = false);
   ~Fast2DMatcher();
+  Fast2DMatcher(const Fast2DMatcher&) = delete;
+  Fast2DMatcher& operator=(const Fast2DMatcher&) = delete;
+  // The argument checks of the constructor (CMX_REQUIRE); the device is not touched.
+  static void CheckArguments(const cmx_fast2d_options& options, const cmx_grid2d_limits& limits,
+                             const uint16_t* cells);
+  // The matchers of `num` submaps, bit for bit what the constructor builds for each, by chains of
+  // launches over tables of submaps (fast_2d_stack.hip "batch build").  Every matcher owns one
+  // device allocation of its own.  The sources have passed CheckArguments.
+  static std::vector<std::unique_ptr<Fast2DMatcher>> BuildBatch(const cmx_fast2d_options& options,
+                                                                const Fast2DSource* sources,
+                                                                int num, int device);
   int device() const { return device_; }
   const cmx_fast2d_options& options() const { return options_; }
   const cmx_grid2d_limits& limits() const { return limits_; }
@@ -152,9 +170,18 @@ class Fast2DMatcher {
   float score_scale() const { return score_scale_; }
 
  private:
+  // A matcher of BuildBatch: the geometry of every region, laid out in ONE allocation (`slab_`);
+  // nothing is built yet.
+  struct BatchTag {};
+  Fast2DMatcher(BatchTag, const cmx_fast2d_options& options, const cmx_grid2d_limits& limits,
+                int device);
+
   cmx_fast2d_options options_;
   cmx_grid2d_limits limits_;
   int device_;
+  // The constructor gives every region an allocation of its own; BuildBatch one `slab_` that the
+  // five pointers below point into (the destructor then frees the slab alone).
+  void* slab_ = nullptr;
   void* stack_mem_ = nullptr;      // all levels, contiguous
   void* quads_mem_ = nullptr;      // quad layouts of levels 0 .. depth-2, contiguous
   uint8_t* planes_ = nullptr;      // phase planes of the lowest-resolution level (or null)

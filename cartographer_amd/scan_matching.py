@@ -271,6 +271,46 @@ class FastCorrelativeScanMatcher2D:
         check(create(C.byref(self.options), device_grid._h, C.byref(self._h)))
         return self
 
+    @classmethod
+    def create_batch(cls, grids, branch_and_bound_depth, linear_search_window=7.0,
+                     angular_search_window=float(np.deg2rad(30.0)), device=0):
+        """cmx_fast2d_create_batch: the matchers of many submaps in one call (a loaded map, the
+        first global constraint of a node against every finished submap).  `grids` mixes Grid2D
+        (host cells), ProbabilityGridOnDevice and TSDF2DOnDevice (resident on `device`); returns
+        ordinary matcher objects, each what the constructor / from_device_grid builds."""
+        from .grid_2d import ProbabilityGridOnDevice, TSDF2DOnDevice
+        grids = list(grids)
+        num = len(grids)
+        options = Fast2DOptions(linear_search_window, angular_search_window,
+                                branch_and_bound_depth)
+        sources = (_lib.Fast2DSource * max(num, 1))()
+        keep = []                                   # limits and cell arrays the sources point at
+        for k, grid in enumerate(grids):
+            if isinstance(grid, TSDF2DOnDevice):
+                sources[k].tsdf = grid._h
+            elif isinstance(grid, ProbabilityGridOnDevice):
+                sources[k].grid = grid._h
+            else:
+                limits = grid.limits_c()
+                cells = np.ascontiguousarray(grid.cells, np.uint16)
+                keep.append((limits, cells))
+                sources[k].limits = C.pointer(limits)
+                sources[k].cells = cells.ctypes.data
+        handles = (C.c_void_p * max(num, 1))()
+        check(_lib.lib().cmx_fast2d_create_batch(C.byref(options), sources, num, device, handles))
+        del keep
+        matchers = []
+        for k, grid in enumerate(grids):
+            self = cls.__new__(cls)
+            self.grid = grid
+            self.options = Fast2DOptions(linear_search_window, angular_search_window,
+                                         branch_and_bound_depth)
+            self.device = device
+            self.last_stats = None
+            self._h = C.c_void_p(handles[k])
+            matchers.append(self)
+        return matchers
+
     def __del__(self):
         if getattr(self, "_h", None):
             _lib.lib().cmx_fast2d_destroy(self._h)

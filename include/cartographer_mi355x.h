@@ -11,6 +11,9 @@
  *   cmx_rt2d_match_tsdf            the same method on a TSDF2D grid (.cc:38-59, :159-167)
  *   cmx_fast2d_create / _destroy   FastCorrelativeScanMatcher2D ctor / dtor
  *                                  SM2/fast_correlative_scan_matcher_2d.h:114-118, .cc:188-196
+ *   cmx_fast2d_create_batch        the same ctor for many submaps in one call (the
+ *                                  DispatchScanMatcherConstruction of a loaded map or of a first
+ *                                  global constraint, constraints/constraint_builder_2d.cc:165-186)
  *   cmx_fast2d_match               FastCorrelativeScanMatcher2D::Match        .h:124-126, .cc:198-208
  *   cmx_fast2d_match_full_submap   FastCorrelativeScanMatcher2D::MatchFullSubmap .h:132-133, .cc:210-225
  *   cmx_fast2d_match_batch, cmx_fast2d_match_full_submap_batch
@@ -342,6 +345,32 @@ cmx_status cmx_fast2d_create(const cmx_fast2d_options* options, const cmx_grid2d
                              const uint16_t* cells, int32_t device, cmx_fast2d** out);
 cmx_status cmx_fast2d_create_from_grid(const cmx_fast2d_options* options, const cmx_grid2d* grid,
                                        cmx_fast2d** out);
+/* One submap of a cmx_fast2d_create_batch call.  Exactly one source is set:
+ * (limits, cells) = the arguments of cmx_fast2d_create (host memory), or grid
+ * (cmx_fast2d_create_from_grid), or tsdf (cmx_fast2d_create_from_tsdf). */
+typedef struct cmx_fast2d_source {
+  const cmx_grid2d_limits* limits;
+  const uint16_t* cells;
+  const cmx_grid2d* grid;
+  const cmx_tsdf2d* tsdf;
+} cmx_fast2d_source;
+/* The matchers of `num_sources` submaps on `device` -- a loaded map, or the first global
+ * constraint of a node against every finished submap (constraints/constraint_builder_2d.cc:113-137,
+ * :165-186) -- in ONE call: out[k] is, bit for bit, the matcher the single create of sources[k]
+ * returns (sources may differ in kind, size, resolution, origin and cost range; `options` holds
+ * for all, as a ConstraintBuilder2D has one set).  The number of launches does not grow with
+ * num_sources: one chain of launches builds the whole list (a list too large for the scratch
+ * memory, a launch grid or a 32-bit count: consecutive chains), one synchronisation per chain.
+ * Every matcher owns its memory, is used like any other and is destroyed with
+ * cmx_fast2d_destroy, in any order; the sources are free once the call returns.
+ * All or nothing: every argument check of the single creates is made for every source before
+ * the device is touched -- a failing one is CMX_INVALID_ARGUMENT and cmx_last_error names the
+ * index of the source; so are num_sources < 1, a source with no kind or more than one kind set,
+ * and a resident source on another device.  On any error (a device allocation that fails
+ * half-way included) nothing is left allocated and every out[k] is NULL. */
+cmx_status cmx_fast2d_create_batch(const cmx_fast2d_options* options,
+                                   const cmx_fast2d_source* sources, int32_t num_sources,
+                                   int32_t device, cmx_fast2d** out /* num_sources */);
 void cmx_fast2d_destroy(cmx_fast2d* matcher);
 
 cmx_status cmx_fast2d_match(const cmx_fast2d* matcher, const cmx_pose2d* initial_pose_estimate,
