@@ -572,6 +572,7 @@ def _ceres3d_compare(sm3, oracle, pairs, target, init, weights, tw, rw, **kw):
     assert abs(summary["initial_cost"] - ref["initial_cost"]) <= 1e-9 * max(1.0, ref["initial_cost"])
     assert abs(summary["final_cost"] - ref["final_cost"]) <= 1e-6 * max(1.0, ref["final_cost"])
     assert summary["num_successful_steps"] == ref["num_successful_steps"]
+    assert summary["num_unsuccessful_steps"] == ref["num_unsuccessful_steps"]
     assert summary["termination"] == ref["termination"]
     return ref, pose, summary
 
@@ -635,6 +636,7 @@ def test_ceres3d_with_the_intensity_cost_function_equals_the_oracle(sm3, oracle,
     assert abs(summary["initial_cost"] - ref["initial_cost"]) <= 1e-9 * max(1.0, ref["initial_cost"])
     assert abs(summary["final_cost"] - ref["final_cost"]) <= 1e-6 * max(1.0, ref["final_cost"])
     assert summary["num_successful_steps"] == ref["num_successful_steps"]
+    assert summary["num_unsuccessful_steps"] == ref["num_unsuccessful_steps"]
     assert summary["termination"] == ref["termination"]
     # the block is there: the match without it ends elsewhere
     plain, _ = m.match(init_t, sm3.Rigid3d(tuple(init[:3]), tuple(init[3:])),

@@ -468,6 +468,7 @@ def test_ceres3d_on_the_resident_grids(synth, oracle):
     np.testing.assert_allclose(list(pose.translation) + list(pose.rotation), ref["pose"],
                                rtol=0, atol=1e-6)
     assert summary["num_successful_steps"] == ref["num_successful_steps"] >= 1
+    assert summary["num_unsuccessful_steps"] == ref["num_unsuccessful_steps"]
     empty = grid_3d.HybridGridOnDevice(0.1)
     one = sm3.CeresScanMatcher3D([1.0], 5.0, 4e2, max_num_iterations=12)
     stay, stay_summary = one.match_grids(init_t, first, [(hi, empty)])
