@@ -70,6 +70,16 @@ class Fast3DOptions(C.Structure):
                 ("angular_search_window", C.c_double)]
 
 
+class Fast3DSource(C.Structure):
+    """cmx_fast3d_source: one submap of cmx_fast3d_create_batch; either the voxel lists (with
+    resolution, grid_size, low_resolution) or the two resident grids are set."""
+    _fields_ = [("resolution", C.c_float), ("grid_size", C.c_int32), ("voxels", C.c_void_p),
+                ("num_voxels", C.c_int64), ("low_resolution", C.c_float),
+                ("low_resolution_voxels", C.c_void_p), ("num_low_resolution_voxels", C.c_int64),
+                ("high_resolution_grid", C.c_void_p), ("low_resolution_grid", C.c_void_p),
+                ("rotational_scan_matcher_histogram", C.c_void_p), ("histogram_size", C.c_int32)]
+
+
 class MatchStats(C.Structure):
     _fields_ = [("candidates_scored", C.c_int64), ("coarse_candidates", C.c_int64),
                 ("nodes_expanded", C.c_int64), ("num_scans", C.c_int32), ("expansion_launches", C.c_int32),
@@ -196,6 +206,7 @@ EXPORTED_SYMBOLS = [
     "cmx_fast3d_destroy", "cmx_fast3d_match", "cmx_fast3d_match_full_submap",
     "cmx_fast3d_match_batch", "cmx_fast3d_match_pairs",
     "cmx_fast3d_level_info", "cmx_fast3d_level_cells", "cmx_fast3d_create_from_grids",
+    "cmx_fast3d_create_batch",
     "cmx_ceres2d_match", "cmx_ceres2d_match_grid", "cmx_fast2d_refine_batch", "cmx_ceres3d_match",
     "cmx_ceres2d_match_tsdf", "cmx_ceres2d_match_tsdf_grid", "cmx_ceres2d_refine_batch_tsdf",
     "cmx_ceres2d_tsdf_residuals",
@@ -422,6 +433,9 @@ def lib():
                                     C.c_int32, P(C.c_void_p)]
     L.cmx_fast3d_create_from_grids.argtypes = [P(Fast3DOptions), C.c_void_p, C.c_void_p,
                                                C.c_void_p, C.c_int32, P(C.c_void_p)]
+    if hasattr(L, "cmx_fast3d_create_batch"):   # (absent from an older library an A/B tool loads)
+        L.cmx_fast3d_create_batch.argtypes = [P(Fast3DOptions), P(Fast3DSource), C.c_int32,
+                                              C.c_int32, P(C.c_void_p)]
     L.cmx_fast3d_destroy.argtypes = [C.c_void_p]
     L.cmx_fast3d_destroy.restype = None
     L.cmx_fast3d_match.argtypes = [C.c_void_p, P(Pose3d), P(Pose3d), P(NodeData3D), C.c_float,

@@ -366,16 +366,23 @@ class ConstraintBuilder3D:
     occupied-space weights: the builder's ``ceres_scan_matcher_``), the found ones to
     ``cmx_fast3d_refine_pairs`` (:263-276) -- both
     against grids that stay in HBM.  ``refine`` is a host callback instead, for experiments.
+    With ``batch_create=True`` a submap's matcher is not built when its first pair is added:
+    the flush builds all the matchers the queued pairs still lack by one
+    ``cmx_fast3d_create_batch`` call (``DispatchScanMatcherConstruction``, :170-198, for every new
+    submap at once) before the searches; the constraints are the same.
     """
 
     def __init__(self, options: ConstraintBuilderOptions3D, device: int = 0,
-                 refine: Optional[Callable] = None, ceres=None):
+                 refine: Optional[Callable] = None, ceres=None, batch_create: bool = False):
         self.options = options
         self.device = device
         self.refine = refine
         self.ceres = ceres
+        self.batch_create = batch_create
         self.last_refine_summaries = None
         self._scan_matchers = {}
+        # batch_create: the submaps whose matcher the next flush builds and keeps
+        self._awaited: Dict[SubmapId, Submap3D] = {}
         self._samplers: Dict[SubmapId, FixedRatioSampler] = {}
         self._constraints: List[Optional[Constraint3D]] = []
         self._pending = []
@@ -418,30 +425,63 @@ class ConstraintBuilder3D:
 
     def delete_scan_matcher(self, submap_id) -> None:
         self._scan_matchers.pop(submap_id, None)
+        self._awaited.pop(submap_id, None)
         self._samplers.pop(submap_id, None)
 
     def num_scan_matchers(self) -> int:
         return len(self._scan_matchers)
 
+    def _matcher_options(self):
+        o = self.options
+        return dict(branch_and_bound_depth=o.branch_and_bound_depth,
+                    full_resolution_depth=o.full_resolution_depth,
+                    min_rotational_score=o.min_rotational_score,
+                    min_low_resolution_score=o.min_low_resolution_score,
+                    linear_xy_search_window=o.linear_xy_search_window,
+                    linear_z_search_window=o.linear_z_search_window,
+                    angular_search_window=o.angular_search_window)
+
     def _enqueue(self, submap_id, submap, node_id, constant_data, full, node, sub):
         from .scan_matching_3d import FastCorrelativeScanMatcher3D
         self._constraints.append(None)
-        if submap_id not in self._scan_matchers:          # DispatchScanMatcherConstruction
-            o = self.options
-            self._scan_matchers[submap_id] = FastCorrelativeScanMatcher3D(
-                submap.high_resolution, submap.high_resolution_voxels, submap.grid_size,
-                submap.low_resolution, submap.low_resolution_voxels,
-                submap.rotational_scan_matcher_histogram,
-                branch_and_bound_depth=o.branch_and_bound_depth,
-                full_resolution_depth=o.full_resolution_depth,
-                min_rotational_score=o.min_rotational_score,
-                min_low_resolution_score=o.min_low_resolution_score,
-                linear_xy_search_window=o.linear_xy_search_window,
-                linear_z_search_window=o.linear_z_search_window,
-                angular_search_window=o.angular_search_window, device=self.device)
+        if self.batch_create:
+            # (the submap travels with the pair instead of a matcher: _flush builds it)
+            if submap_id not in self._scan_matchers:
+                self._awaited.setdefault(submap_id, submap)
+            matcher = self._scan_matchers.get(submap_id) or submap
+        else:
+            if submap_id not in self._scan_matchers:      # DispatchScanMatcherConstruction
+                self._scan_matchers[submap_id] = FastCorrelativeScanMatcher3D(
+                    submap.high_resolution, submap.high_resolution_voxels, submap.grid_size,
+                    submap.low_resolution, submap.low_resolution_voxels,
+                    submap.rotational_scan_matcher_histogram, **self._matcher_options(),
+                    device=self.device)
+            matcher = self._scan_matchers[submap_id]
         # (the matcher travels with the pair: a later delete_scan_matcher must not break it)
         self._pending.append((len(self._constraints) - 1, submap_id, node_id, constant_data, full,
-                              node, sub, self._scan_matchers[submap_id]))
+                              node, sub, matcher))
+
+    def _create_missing(self, pending):
+        """batch_create: the matchers the pending pairs still lack, each submap once, in one
+        cmx_fast3d_create_batch call.  A submap deleted since its pair was added
+        (delete_scan_matcher) gets a matcher for its scheduled pairs only, as the reference keeps
+        a scheduled pair's matcher alive."""
+        from .scan_matching_3d import fast3d_create_batch
+        missing: Dict[SubmapId, Submap3D] = {}
+        for item in pending:
+            if isinstance(item[7], Submap3D) and item[1] not in self._scan_matchers:
+                missing.setdefault(item[1], item[7])
+        built = {}
+        if missing:
+            built = dict(zip(missing.keys(), fast3d_create_batch(
+                [(s.high_resolution, s.high_resolution_voxels, s.grid_size, s.low_resolution,
+                  s.low_resolution_voxels, s.rotational_scan_matcher_histogram)
+                 for s in missing.values()], device=self.device, **self._matcher_options())))
+            for submap_id, matcher in built.items():
+                if self._awaited.pop(submap_id, None) is not None:
+                    self._scan_matchers[submap_id] = matcher
+        return [item[:7] + (self._scan_matchers.get(item[1]) or built[item[1]],)
+                if isinstance(item[7], Submap3D) else item for item in pending]
 
     def _flush(self):
         """All queued pairs, of however many nodes, go to the device together: one
@@ -452,6 +492,8 @@ class ConstraintBuilder3D:
         pending, self._pending = self._pending, []
         if not pending:
             return
+        if self.batch_create:
+            pending = self._create_missing(pending)
         groups: Dict[int, list] = {}
         for item in pending:
             groups.setdefault(id(item[3]), []).append(item)

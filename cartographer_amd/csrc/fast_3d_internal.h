@@ -1,5 +1,6 @@
 // What the translation units of the fast 3D matcher share on the host:
 //   fast_3d_stack.hip    precomputation stack and octs (Fast3DMatcher), from voxels or resident grids
+//   fast_3d_stack_batch.hip  the same for the matchers of many submaps, one chain of launches
 //   fast_3d_coarse.hip   staging of a chain of launches, scan discretisation, lowest-resolution
 //                        scoring (the front end)
 //   fast_3d.hip          branch and bound
@@ -29,6 +30,23 @@ struct Fast3DMatcher {
   DeviceBrick low;
   DeviceBrick high;                                 // raw uint16 grid (Ceres refinement)
   std::vector<float> histogram;
+  // A matcher of cmx_fast3d_create_batch keeps everything above in ONE allocation: its bricks
+  // carry `desc` and `bytes`, own no memory (mem == nullptr) and point into the slab.
+  DeviceBrick slab;
+};
+
+// One submap of a batch create, checked (CheckVoxelSource3D / ResidentSource3D): voxel lists in
+// host memory with their boxes, or the bricks of two resident grids.
+struct Fast3DSource {
+  bool resident = false;
+  float resolution = 0.f, low_resolution = 0.f;
+  int width_in_voxels = 0;
+  const cmx_voxel* voxels[2] = {nullptr, nullptr};   // high, low
+  int64_t num_voxels[2] = {0, 0};
+  int lo[2][3] = {}, hi[2][3] = {};                  // VoxelBoxOrOrigin of the lists
+  Brick grid[2] = {};                                // resident (cells == nullptr: still empty)
+  const float* histogram = nullptr;
+  int histogram_size = 0;
 };
 
 // A node's constant data with what GenerateDiscreteScans (:246-295) needs of it on the host, made
@@ -151,6 +169,25 @@ inline void DebugSync3D(Workspace& ws, const char* name) {
   fprintf(stderr, "[cmx sync] %s ...\n", name);
   CMX_HIP(hipStreamSynchronize(ws.stream));
 }
+
+// ---- fast_3d_stack.hip
+// The argument checks of cmx_fast3d_create short of grid_size (which takes a pass over the list).
+void CheckVoxelSource3D(float resolution, const cmx_voxel* voxels, int64_t num_voxels,
+                        float low_resolution, const cmx_voxel* low_resolution_voxels,
+                        int64_t num_low_resolution_voxels, const float* histogram,
+                        int32_t histogram_size);
+// The argument checks of cmx_fast3d_create_from_grids; bricks (zeroed for a grid that is still
+// empty), resolutions and grid_size of the pair, the device both live on.
+void ResidentSource3D(const cmx_grid3d* high_resolution_grid, const cmx_grid3d* low_resolution_grid,
+                      const float* histogram, int32_t histogram_size, Brick grid[2],
+                      float resolution[2], int32_t* grid_size, int* device);
+
+// ---- fast_3d_stack_batch.hip
+// The matchers of `num` checked sources on `device`, built by chains of launches whose length
+// does not depend on `num`; all or nothing (an exception leaves nothing allocated).
+std::vector<std::unique_ptr<cmx_fast3d>> BuildFast3DBatch(const cmx_fast3d_options& options,
+                                                          const Fast3DSource* sources, int num,
+                                                          int device);
 
 // ---- fast_3d_coarse.hip
 // Totals, bases (into `prep`) and the layout of the upload block; host only.  False: no search

@@ -2,14 +2,13 @@
 // resident HybridGrids, and its introspection entries (reference map: fast_3d.hip).
 #include <algorithm>
 
-#include "fast_3d_internal.h"
+#include "fast_3d_stack_device.h"
 
 namespace cmx {
 namespace {
 
-// ---------------------------------------------------------------------------
-// Precomputation stack (gather form of PrecomputeGrid's scatter-max)
-// ---------------------------------------------------------------------------
+// The per-cell arithmetic of these kernels is fast_3d_stack_device.h's, shared with their twins
+// in fast_3d_stack_batch.hip.
 __global__ void PrecomputeLevel3DKernel(Brick prev, Brick out, int shift, int half) {
   const long long total = static_cast<long long>(out.nx) * out.ny * out.nz;
   const long long i = static_cast<long long>(blockIdx.x) * blockDim.x + threadIdx.x;
@@ -17,21 +16,8 @@ __global__ void PrecomputeLevel3DKernel(Brick prev, Brick out, int shift, int ha
   const int ix = static_cast<int>(i % out.nx);
   const int iy = static_cast<int>((i / out.nx) % out.ny);
   const int iz = static_cast<int>(i / (static_cast<long long>(out.nx) * out.ny));
-  const int tx = ix + out.lo_x, ty = iy + out.lo_y, tz = iz + out.lo_z;
-  unsigned best = 0;
-  const int sub = half ? 2 : 1;
-  // out(t) = max over octants o and (for half resolution) sub-cells e of
-  // prev(sub*t + e + shift*o)   <=>   t = (c - shift*o) >> (half ? 1 : 0).
-  for (int oz = 0; oz < 2; ++oz)
-    for (int oy = 0; oy < 2; ++oy)
-      for (int ox = 0; ox < 2; ++ox)
-        for (int ez = 0; ez < sub; ++ez)
-          for (int ey = 0; ey < sub; ++ey)
-            for (int ex = 0; ex < sub; ++ex)
-              best = max(best, BrickValueU8(prev, sub * tx + ex + shift * ox,
-                                            sub * ty + ey + shift * oy,
-                                            sub * tz + ez + shift * oz));
-  static_cast<uint8_t*>(const_cast<void*>(out.cells))[i] = static_cast<uint8_t>(best);
+  static_cast<uint8_t*>(const_cast<void*>(out.cells))[i] = static_cast<uint8_t>(
+      PrecomputedCell3D(prev, ix + out.lo_x, iy + out.lo_y, iz + out.lo_z, shift, half));
 }
 
 __global__ void BuildOct3DKernel(Brick L, int s, uint2* __restrict__ out, int qx, int qy, int qz) {
@@ -39,20 +25,7 @@ __global__ void BuildOct3DKernel(Brick L, int s, uint2* __restrict__ out, int qx
   if (i >= static_cast<size_t>(qx) * qy * qz) return;
   const int X = static_cast<int>(i % qx), Y = static_cast<int>((i / qx) % qy),
             Z = static_cast<int>(i / (static_cast<size_t>(qx) * qy));
-  const uint8_t* __restrict__ cells = static_cast<const uint8_t*>(L.cells);
-  unsigned lo = 0, hi = 0;
-#pragma unroll
-  for (int k = 0; k < 8; ++k) {
-    const int x = X - s + ((k & 1) ? s : 0), y = Y - s + ((k & 2) ? s : 0),
-              z = Z - s + ((k & 4) ? s : 0);
-    unsigned v = 0;
-    if (static_cast<unsigned>(x) < static_cast<unsigned>(L.nx) &&
-        static_cast<unsigned>(y) < static_cast<unsigned>(L.ny) &&
-        static_cast<unsigned>(z) < static_cast<unsigned>(L.nz))
-      v = cells[(static_cast<size_t>(z) * L.ny + y) * L.nx + x];
-    if (k < 4) lo |= v << (8 * k); else hi |= v << (8 * (k - 4));
-  }
-  out[i] = make_uint2(lo, hi);
+  out[i] = OctWord3D(L, s, X, Y, Z);
 }
 
 // ---------------------------------------------------------------------------
@@ -71,40 +44,11 @@ struct GridPair3D {
 __global__ void __launch_bounds__(256)
 Grid3DNonZeroBoundsKernel(GridPair3D pair, int* __restrict__ box) {
   const Brick b = pair.grid[blockIdx.y];
-  const long long groups = static_cast<long long>(b.nx) * b.ny * b.nz / 8;
-  const uint4* __restrict__ cells = static_cast<const uint4*>(b.cells);
-  int lo[3] = {0x7fffffff, 0x7fffffff, 0x7fffffff}, hi[3] = {-0x7fffffff - 1, -0x7fffffff - 1,
-                                                             -0x7fffffff - 1};
-  for (long long g = static_cast<long long>(blockIdx.x) * blockDim.x + threadIdx.x; g < groups;
-       g += static_cast<long long>(gridDim.x) * blockDim.x) {
-    const uint4 v = cells[g];
-    const unsigned w[4] = {v.x, v.y, v.z, v.w};
-    int first = 8, last = -1;                // non-zero cells k of the group (cell 2j = low half)
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-      if ((w[k >> 1] >> (16 * (k & 1))) & 0xffffu) {
-        first = min(first, k);
-        last = k;
-      }
-    }
-    if (last < 0) continue;
-    const long long cell = 8 * g;
-    const long long row = cell / b.nx;
-    const int x = static_cast<int>(cell - row * b.nx) + b.lo_x;
-    const int y = static_cast<int>(row % b.ny) + b.lo_y;
-    const int z = static_cast<int>(row / b.ny) + b.lo_z;
-    lo[0] = min(lo[0], x + first); hi[0] = max(hi[0], x + last);
-    lo[1] = min(lo[1], y); hi[1] = max(hi[1], y);
-    lo[2] = min(lo[2], z); hi[2] = max(hi[2], z);
-  }
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    const int wlo = WaveMin(lo[k]), whi = WaveMax(hi[k]);
-    if ((threadIdx.x & 63) == 0 && wlo <= whi) {
-      atomicMin(&box[6 * blockIdx.y + k], wlo);
-      atomicMax(&box[6 * blockIdx.y + 3 + k], whi);
-    }
-  }
+  int lo[3] = {kEmptyBoxLo, kEmptyBoxLo, kEmptyBoxLo}, hi[3] = {kEmptyBoxHi, kEmptyBoxHi,
+                                                                kEmptyBoxHi};
+  WidenNonZeroBounds3D(b, static_cast<long long>(blockIdx.x) * blockDim.x + threadIdx.x,
+                       static_cast<long long>(gridDim.x) * blockDim.x, lo, hi);
+  MergeBoundsIntoBox3D(lo, hi, box + 6 * blockIdx.y);
 }
 
 // One thread per cell of the tight boxes (x fastest): grid 0 writes the raw uint16 copy `high` and
@@ -121,51 +65,28 @@ Grid3DCropKernel(GridPair3D source, Brick high, Brick level0, Brick low) {
   const int x = static_cast<int>(i - row * out.nx) + out.lo_x;
   const int y = static_cast<int>(row % out.ny) + out.lo_y;
   const int z = static_cast<int>(row / out.ny) + out.lo_z;
-  const Brick src = source.grid[blockIdx.y];
-  const unsigned v = src.cells ? BrickValueU16(src, x, y, z) : 0u;
+  const unsigned v = CropValue3D(source.grid[blockIdx.y], x, y, z);
   static_cast<uint16_t*>(const_cast<void*>(out.cells))[i] = static_cast<uint16_t>(v);
   if (is_high)
     static_cast<uint8_t*>(const_cast<void*>(level0.cells))[i] = PrecomputationValueDev(v);
-}
-
-// CHECKs of PrecomputationGridStack3D (:60-61).
-void CheckFast3DOptions(const cmx_fast3d_options& options) {
-  CMX_REQUIRE(options.branch_and_bound_depth >= 1 && options.branch_and_bound_depth <= kMaxDepth,
-              "branch_and_bound_depth %d outside [1,%d]", options.branch_and_bound_depth,
-              kMaxDepth);
-  CMX_REQUIRE(options.full_resolution_depth >= 1, "full_resolution_depth must be >= 1");
 }
 
 // PrecomputationGridStack3D (:57-77) over level 0 (m->levels[0]) and the octs of every level
 // that can be a child level: the part both constructors share.
 void BuildStackAndOcts(Workspace& ws, Fast3DMatcher* matcher) {
   Fast3DMatcher& m = *matcher;
-  int last_width = 1;
   for (int depth = 1; depth != m.options.branch_and_bound_depth; ++depth) {
-    const bool half = depth >= m.options.full_resolution_depth;
-    const int next_width = 1 << depth;
-    const int per_voxel = 1 << std::max(0, depth - m.options.full_resolution_depth);
-    const int shift = (next_width - last_width + (per_voxel - 1)) / per_voxel;
     const Brick prev = m.levels.back()->desc;
-    Brick b{};
-    int lo[3] = {prev.lo_x - shift, prev.lo_y - shift, prev.lo_z - shift};
-    int hi[3] = {prev.lo_x + prev.nx - 1, prev.lo_y + prev.ny - 1, prev.lo_z + prev.nz - 1};
-    if (half) {
-      for (int k = 0; k < 3; ++k) { lo[k] >>= 1; hi[k] >>= 1; }
-    }
-    b.lo_x = lo[0]; b.lo_y = lo[1]; b.lo_z = lo[2];
-    b.nx = hi[0] - lo[0] + 1; b.ny = hi[1] - lo[1] + 1; b.nz = hi[2] - lo[2] + 1;
     std::unique_ptr<DeviceBrick> level(new DeviceBrick);
-    level->bytes = static_cast<size_t>(b.nx) * b.ny * b.nz;
-    CMX_REQUIRE(level->bytes < (size_t(1) << 31), "precomputation level too large");
+    int shift, half;
+    Brick b = LevelAbove3D(prev, depth, m.options.full_resolution_depth, &shift, &half,
+                           &level->bytes);
     CMX_HIP(hipMalloc(&level->mem, level->bytes + 16));   // (+16: aligned 8-byte reads of the last cells)
     b.cells = level->mem;
     level->desc = b;
-    PrecomputeLevel3DKernel<<<DivUp(level->bytes, 256), 256, 0, ws.stream>>>(prev, b, shift,
-                                                                            half ? 1 : 0);
+    PrecomputeLevel3DKernel<<<DivUp(level->bytes, 256), 256, 0, ws.stream>>>(prev, b, shift, half);
     CMX_HIP(hipGetLastError());
     m.levels.push_back(std::move(level));
-    last_width = next_width;
   }
   // Octs of every level that can be a child level (debug switch fast3d_no_oct: none, tests).
   {
@@ -175,15 +96,11 @@ void BuildStackAndOcts(Workspace& ws, Fast3DMatcher* matcher) {
     for (int i = 0; build_octs && i + 1 < depth; ++i) {
       const Brick L = m.levels[i]->desc;
       OctDesc O;
-      O.s = 1 << std::min(i, m.options.full_resolution_depth - 1);
-      O.qx = L.nx + O.s; O.qy = L.ny + O.s; O.qz = L.nz + O.s;
-      const size_t count = static_cast<size_t>(O.qx) * O.qy * O.qz;
-      if (count * sizeof(uint2) >= (size_t(1) << 32)) continue;     // 32-bit offsets elsewhere
       std::unique_ptr<DeviceBrick> mem(new DeviceBrick);
-      mem->bytes = count * sizeof(uint2);
+      if (!OctOfLevel3D(L, i, m.options.full_resolution_depth, &O, &mem->bytes)) continue;
       CMX_HIP(hipMalloc(&mem->mem, mem->bytes));
       O.cells = static_cast<const uint2*>(mem->mem);
-      BuildOct3DKernel<<<DivUp(count, 256), 256, 0, ws.stream>>>(
+      BuildOct3DKernel<<<DivUp(mem->bytes / sizeof(uint2), 256), 256, 0, ws.stream>>>(
           L, O.s, static_cast<uint2*>(mem->mem), O.qx, O.qy, O.qz);
       CMX_HIP(hipGetLastError());
       m.oct_desc[i] = O;
@@ -193,6 +110,33 @@ void BuildStackAndOcts(Workspace& ws, Fast3DMatcher* matcher) {
 }
 
 }  // namespace
+
+void CheckVoxelSource3D(float resolution, const cmx_voxel* voxels, int64_t num_voxels,
+                        float low_resolution, const cmx_voxel* low_resolution_voxels,
+                        int64_t num_low_resolution_voxels, const float* histogram,
+                        int32_t histogram_size) {
+  CMX_REQUIRE(resolution > 0.f && low_resolution > 0.f, "resolutions must be > 0");
+  CMX_REQUIRE(num_voxels == 0 || voxels, "voxels is null");
+  CMX_REQUIRE(num_low_resolution_voxels == 0 || low_resolution_voxels, "low voxels null");
+  CMX_REQUIRE(histogram_size >= 0 && (histogram_size == 0 || histogram), "bad histogram");
+}
+
+void ResidentSource3D(const cmx_grid3d* high_resolution_grid, const cmx_grid3d* low_resolution_grid,
+                      const float* histogram, int32_t histogram_size, Brick grid[2],
+                      float resolution[2], int32_t* grid_size, int* device) {
+  CMX_REQUIRE(high_resolution_grid && low_resolution_grid, "null argument");
+  CMX_REQUIRE(histogram_size >= 0 && (histogram_size == 0 || histogram), "bad histogram");
+  int on[2];
+  const cmx_grid3d* grids[2] = {high_resolution_grid, low_resolution_grid};
+  for (int g = 0; g < 2; ++g) {
+    if (!Grid3DBrick(grids[g], &grid[g], &resolution[g], &on[g])) grid[g] = Brick{};
+    CMX_REQUIRE(grid[g].nx % 8 == 0, "internal error: resident brick not in 8-cell rows");
+  }
+  CMX_REQUIRE(on[0] == on[1], "the grids live on different devices (%d, %d)", on[0], on[1]);
+  *device = on[0];
+  const cmx_status status = cmx_grid3d_info(high_resolution_grid, nullptr, grid_size, nullptr);
+  CMX_REQUIRE(status == CMX_OK, "cmx_grid3d_info failed");
+}
 
 // For sharded.hip: the device a 3D matcher's grids live on.
 int Fast3DDevice(const cmx_fast3d* matcher) { return matcher->impl.device; }
@@ -220,11 +164,9 @@ cmx_status cmx_fast3d_create(const cmx_fast3d_options* options, float resolution
     CMX_REQUIRE(options && out, "null argument");
     *out = nullptr;
     CheckFast3DOptions(*options);
-    CMX_REQUIRE(resolution > 0.f && low_resolution > 0.f, "resolutions must be > 0");
-    CMX_REQUIRE(num_voxels == 0 || voxels, "voxels is null");
-    CMX_REQUIRE(num_low_resolution_voxels == 0 || low_resolution_voxels, "low voxels null");
-    CMX_REQUIRE(histogram_size >= 0 && (histogram_size == 0 || rotational_scan_matcher_histogram),
-                "bad histogram");
+    CheckVoxelSource3D(resolution, voxels, num_voxels, low_resolution, low_resolution_voxels,
+                       num_low_resolution_voxels, rotational_scan_matcher_histogram,
+                       histogram_size);
     CMX_REQUIRE(grid_size >= GridSizeOf(voxels, num_voxels),
                 "grid_size %d is smaller than the voxels' extent", grid_size);
     std::unique_ptr<cmx_fast3d> h(new cmx_fast3d);
@@ -263,27 +205,16 @@ cmx_status cmx_fast3d_create_from_grids(const cmx_fast3d_options* options,
     CMX_REQUIRE(options && high_resolution_grid && low_resolution_grid && out, "null argument");
     *out = nullptr;
     CheckFast3DOptions(*options);
-    CMX_REQUIRE(histogram_size >= 0 && (histogram_size == 0 || rotational_scan_matcher_histogram),
-                "bad histogram");
     GridPair3D source{};
     float resolution[2];
-    int device[2];
-    const cmx_grid3d* grids[2] = {high_resolution_grid, low_resolution_grid};
-    for (int g = 0; g < 2; ++g) {
-      if (!Grid3DBrick(grids[g], &source.grid[g], &resolution[g], &device[g])) source.grid[g] = Brick{};
-      CMX_REQUIRE(source.grid[g].nx % 8 == 0, "internal error: resident brick not in 8-cell rows");
-    }
-    CMX_REQUIRE(device[0] == device[1], "the grids live on different devices (%d, %d)", device[0],
-                device[1]);
     int32_t grid_size = 0;
-    {
-      const cmx_status status = cmx_grid3d_info(high_resolution_grid, nullptr, &grid_size, nullptr);
-      CMX_REQUIRE(status == CMX_OK, "cmx_grid3d_info failed");
-    }
+    int on_device = 0;
+    ResidentSource3D(high_resolution_grid, low_resolution_grid, rotational_scan_matcher_histogram,
+                     histogram_size, source.grid, resolution, &grid_size, &on_device);
     std::unique_ptr<cmx_fast3d> h(new cmx_fast3d);
     Fast3DMatcher& m = h->impl;
     m.options = *options;
-    m.device = device[0];
+    m.device = on_device;
     m.resolution = resolution[0];
     m.low_resolution = resolution[1];
     m.width_in_voxels = grid_size;
@@ -295,8 +226,8 @@ cmx_status cmx_fast3d_create_from_grids(const cmx_fast3d_options* options,
     int* h_box = ws->pinned[1].ReserveAs<int>(12);
     for (int g = 0; g < 2; ++g)
       for (int k = 0; k < 3; ++k) {
-        h_box[6 * g + k] = 0x7fffffff;
-        h_box[6 * g + 3 + k] = -0x7fffffff - 1;
+        h_box[6 * g + k] = kEmptyBoxLo;
+        h_box[6 * g + 3 + k] = kEmptyBoxHi;
       }
     const long long groups = std::max(
         static_cast<long long>(source.grid[0].nx) * source.grid[0].ny * source.grid[0].nz,
@@ -361,8 +292,9 @@ cmx_status cmx_fast3d_level_cells(const cmx_fast3d* matcher, int32_t depth, uint
     CMX_REQUIRE(matcher && out, "null argument");
     CMX_REQUIRE(depth >= 0 && depth < static_cast<int>(matcher->impl.levels.size()), "bad depth");
     UseDevice(matcher->impl.device);
+    // (desc.cells: a batch-built matcher's bricks lie in its slab and own no memory)
     const DeviceBrick& b = *matcher->impl.levels[depth];
-    CMX_HIP(hipMemcpy(out, b.mem, b.bytes, hipMemcpyDeviceToHost));
+    CMX_HIP(hipMemcpy(out, b.desc.cells, b.bytes, hipMemcpyDeviceToHost));
   });
 }
 

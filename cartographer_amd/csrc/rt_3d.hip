@@ -30,14 +30,7 @@ __global__ void ScatterVoxelsKernel(const cmx_voxel* __restrict__ voxels, long l
                                     int bytes_per_cell) {
   const long long i = static_cast<long long>(blockIdx.x) * blockDim.x + threadIdx.x;
   if (i >= n) return;
-  const cmx_voxel v = voxels[i];
-  const size_t off = (static_cast<size_t>(v.z - b.lo_z) * b.ny + (v.y - b.lo_y)) * b.nx +
-                     (v.x - b.lo_x);
-  if (bytes_per_cell == 2) {
-    static_cast<uint16_t*>(const_cast<void*>(b.cells))[off] = v.value;
-  } else {
-    static_cast<uint8_t*>(const_cast<void*>(b.cells))[off] = PrecomputationValueDev(v.value);
-  }
+  ScatterVoxel(voxels[i], b, bytes_per_cell);
 }
 
 // Dense f32 probability brick with a one-cell border of kMinProbability: a voxel
@@ -1729,13 +1722,6 @@ Brick BoxBrick(const int lo[3], const int hi[3]) {
   return b;
 }
 
-// Bounding box of a voxel list; the cell at the origin when the list is empty.
-void VoxelBoxOrOrigin(const cmx_voxel* voxels, int64_t n, int lo[3], int hi[3]) {
-  if (VoxelBounds(voxels, n, lo, hi)) return;
-  lo[0] = lo[1] = lo[2] = 0;
-  hi[0] = hi[1] = hi[2] = 0;
-}
-
 // The voxel list on the device (kSlotVoxels), copy enqueued on ws.stream.
 cmx_voxel* UploadVoxels(Workspace& ws, const cmx_voxel* voxels, int64_t n) {
   cmx_voxel* d_vox = ws.dev[kSlotVoxels].ReserveAs<cmx_voxel>(n);
@@ -1744,6 +1730,12 @@ cmx_voxel* UploadVoxels(Workspace& ws, const cmx_voxel* voxels, int64_t n) {
 }
 
 }  // namespace
+
+void VoxelBoxOrOrigin(const cmx_voxel* voxels, int64_t n, int lo[3], int hi[3]) {
+  if (VoxelBounds(voxels, n, lo, hi)) return;
+  lo[0] = lo[1] = lo[2] = 0;
+  hi[0] = hi[1] = hi[2] = 0;
+}
 
 bool VoxelBounds(const cmx_voxel* voxels, int64_t n, int lo[3], int hi[3]) {
   if (n <= 0) return false;
@@ -1770,12 +1762,17 @@ int GridSizeOf(const cmx_voxel* voxels, int64_t n) {
   return gs;
 }
 
-void AllocateDenseBrick(const int lo[3], const int hi[3], int bytes_per_cell, DeviceBrick* out) {
-  Brick b = BoxBrick(lo, hi);
+Brick DenseBrickGeometry(const int lo[3], const int hi[3], int bytes_per_cell, size_t* bytes) {
+  const Brick b = BoxBrick(lo, hi);
   const size_t cells = static_cast<size_t>(b.nx) * b.ny * b.nz;
   CMX_REQUIRE(cells * bytes_per_cell < (size_t(8) << 30),
               "dense grid of %d x %d x %d cells is too large", b.nx, b.ny, b.nz);
-  out->bytes = cells * bytes_per_cell;
+  *bytes = cells * bytes_per_cell;
+  return b;
+}
+
+void AllocateDenseBrick(const int lo[3], const int hi[3], int bytes_per_cell, DeviceBrick* out) {
+  Brick b = DenseBrickGeometry(lo, hi, bytes_per_cell, &out->bytes);
   CMX_HIP(hipMalloc(&out->mem, out->bytes + 16));   // (+16: aligned 8-byte reads of the last cells)
   b.cells = out->mem;
   out->desc = b;

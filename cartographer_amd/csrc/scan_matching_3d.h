@@ -69,6 +69,20 @@ __device__ __forceinline__ uint8_t PrecomputationValueDev(unsigned raw) {
   return static_cast<uint8_t>(min(max(value, 0), 255));
 }
 
+// One voxel of a list into the dense brick over the list's box: the raw uint16 value
+// (bytes_per_cell 2) or ConvertToPrecomputationGrid's uint8 (1).  Shared by the single scatter
+// (rt_3d.hip) and the scatter of a batch of matchers (fast_3d_stack_batch.hip).
+__device__ __forceinline__ void ScatterVoxel(const cmx_voxel& v, const Brick& b,
+                                             int bytes_per_cell) {
+  const size_t off = (static_cast<size_t>(v.z - b.lo_z) * b.ny + (v.y - b.lo_y)) * b.nx +
+                     (v.x - b.lo_x);
+  if (bytes_per_cell == 2) {
+    static_cast<uint16_t*>(const_cast<void*>(b.cells))[off] = v.value;
+  } else {
+    static_cast<uint8_t*>(const_cast<void*>(b.cells))[off] = PrecomputationValueDev(v.value);
+  }
+}
+
 // HybridGrid::GetCellIndex (hybrid_grid.h:428-433): lround(p / resolution), f32.
 __device__ __forceinline__ int3 CellIndex3(const F3& p, float resolution) {
   return make_int3(LRoundF32(p.x / resolution), LRoundF32(p.y / resolution),
@@ -171,6 +185,11 @@ struct DeviceBrick {
 
 // Bounding box of a voxel list; false when the list is empty.
 bool VoxelBounds(const cmx_voxel* voxels, int64_t n, int lo[3], int hi[3]);
+// Bounding box of a voxel list; the cell at the origin when the list is empty.
+void VoxelBoxOrOrigin(const cmx_voxel* voxels, int64_t n, int lo[3], int hi[3]);
+// The dense brick over [lo, hi] (inclusive) without cells and its size in `bytes`: the limits every
+// dense brick of this library keeps (index range, 8 GiB), checked without touching the device.
+Brick DenseBrickGeometry(const int lo[3], const int hi[3], int bytes_per_cell, size_t* bytes);
 // Allocates `out` as the dense brick over [lo, hi] (inclusive) of `bytes_per_cell`, uninitialised.
 void AllocateDenseBrick(const int lo[3], const int hi[3], int bytes_per_cell, DeviceBrick* out);
 // Uploads `voxels` and scatters them into a zeroed dense brick of `bytes_per_cell`

@@ -363,6 +363,63 @@ class FastCorrelativeScanMatcher3D:
         return out
 
 
+def fast3d_create_batch(sources, *, device=0, **options):
+    """``cmx_fast3d_create_batch``: the matchers of many submaps in one call (a loaded map, the
+    first global constraint of a node against every finished submap).  A source is either the
+    tuple of the constructor's arguments ``(resolution, voxels, grid_size, low_resolution,
+    low_resolution_voxels, rotational_scan_matcher_histogram)`` or a triple ``(high_grid,
+    low_grid, rotational_scan_matcher_histogram)`` of ``grid_3d.HybridGridOnDevice`` resident on
+    ``device``; ``options`` are the constructor's keywords and hold for all.  Returns ordinary
+    ``FastCorrelativeScanMatcher3D`` objects, each what the constructor / ``from_device_grids``
+    builds."""
+    sources = list(sources)
+    num = len(sources)
+    defaults = dict(branch_and_bound_depth=8, full_resolution_depth=3, min_rotational_score=0.77,
+                    min_low_resolution_score=0.55, linear_xy_search_window=5.0,
+                    linear_z_search_window=1.0, angular_search_window=float(np.deg2rad(15.0)))
+    unknown = set(options) - set(defaults)
+    if unknown:
+        raise TypeError(f"unknown option(s) {sorted(unknown)}")
+    defaults.update(options)
+    make_options = lambda: Fast3DOptions(*[defaults[k] for k, _ in Fast3DOptions._fields_])  # noqa: E731
+    records = (_lib.Fast3DSource * max(num, 1))()
+    keep = []                                       # the arrays the records point at
+    for k, source in enumerate(sources):
+        if len(source) == 3:
+            high_grid, low_grid, histogram = source
+            records[k].high_resolution_grid = high_grid._h
+            records[k].low_resolution_grid = low_grid._h
+        else:
+            resolution, voxels, grid_size, low_resolution, low_voxels, histogram = source
+            vox, nv = _voxels(voxels)
+            low, nl = _voxels(low_voxels)
+            keep += [vox, low]
+            records[k].resolution = resolution
+            records[k].grid_size = grid_size
+            records[k].voxels = vox.ctypes.data if nv else None
+            records[k].num_voxels = nv
+            records[k].low_resolution = low_resolution
+            records[k].low_resolution_voxels = low.ctypes.data if nl else None
+            records[k].num_low_resolution_voxels = nl
+        hist = np.ascontiguousarray(histogram, np.float32)
+        keep.append(hist)
+        records[k].rotational_scan_matcher_histogram = hist.ctypes.data if hist.size else None
+        records[k].histogram_size = hist.shape[0]
+    handles = (C.c_void_p * max(num, 1))()
+    opts = make_options()
+    check(_lib.lib().cmx_fast3d_create_batch(C.byref(opts), records, num, device, handles))
+    del keep
+    matchers = []
+    for k in range(num):
+        m = FastCorrelativeScanMatcher3D.__new__(FastCorrelativeScanMatcher3D)
+        m.options = make_options()
+        m.depth = defaults["branch_and_bound_depth"]
+        m.last_stats = None
+        m._h = C.c_void_p(handles[k])
+        matchers.append(m)
+    return matchers
+
+
 def fast3d_match_batch(matchers, node_poses, submap_poses, match_full_submap, min_scores,
                        constant_data):
     """One node's data against many submaps' matchers (ConstraintBuilder3D's fan-out,

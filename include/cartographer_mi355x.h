@@ -31,6 +31,9 @@
  *                                  SM3/real_time_correlative_scan_matcher_3d.h:47-50, .cc:34-53
  *   cmx_fast3d_*                   FastCorrelativeScanMatcher3D ctor / Match / MatchFullSubmap
  *                                  SM3/fast_correlative_scan_matcher_3d.h:75-101, .cc:112-170
+ *   cmx_fast3d_create_batch        the same ctor for many submaps in one call (the
+ *                                  DispatchScanMatcherConstruction of a loaded map or of a first
+ *                                  global constraint, constraints/constraint_builder_3d.cc:170-198)
  *
  * Conventions
  *   - Plain C, POD only.  Host pointers are borrowed for the duration of the
@@ -765,6 +768,42 @@ cmx_status cmx_fast3d_create_from_grids(const cmx_fast3d_options* options,
                                         const cmx_grid3d* low_resolution_grid,
                                         const float* rotational_scan_matcher_histogram,
                                         int32_t histogram_size, cmx_fast3d** out);
+/* One submap of a cmx_fast3d_create_batch call.  Exactly one kind is set: the voxel lists of
+ * cmx_fast3d_create (host memory; resolution, grid_size, low_resolution with them), or the two
+ * resident grids of cmx_fast3d_create_from_grids.  The histogram belongs to either kind. */
+typedef struct cmx_fast3d_source {
+  float resolution;  int32_t grid_size;
+  const cmx_voxel* voxels;                 int64_t num_voxels;
+  float low_resolution;
+  const cmx_voxel* low_resolution_voxels;  int64_t num_low_resolution_voxels;
+  const cmx_grid3d* high_resolution_grid;
+  const cmx_grid3d* low_resolution_grid;
+  const float* rotational_scan_matcher_histogram;  int32_t histogram_size;
+} cmx_fast3d_source;
+/* The matchers of `num_sources` submaps on `device` -- a loaded map, or the first global
+ * constraint of a node against every finished submap (constraints/constraint_builder_3d.cc:118-142,
+ * :170-198) -- in ONE call: out[k] is, bit for bit, the matcher the single create of sources[k]
+ * returns (every precomputation level with its bounds, every oct array, both raw uint16 grids
+ * cmx_fast3d_refine_* reads, the histogram, grid_size and both resolutions).  Sources may differ
+ * in kind, extent and resolution; `options` holds for all, as a ConstraintBuilder3D has one set.
+ * The number of launches and synchronisations does not grow with num_sources: one launch finds
+ * the boxes of all resident sources (one synchronisation, none without a resident source), one
+ * chain of launches builds the whole list (a list too large for the staging memory, a launch
+ * grid or a 32-bit count: consecutive chains), one synchronisation per chain.
+ * Every matcher owns its memory (one allocation each), is used like any other and is destroyed
+ * with cmx_fast3d_destroy, in any order; the sources are free once the call returns.
+ * All or nothing: every argument check of the two single creates is made for every source
+ * before the device is touched -- a failing one is CMX_INVALID_ARGUMENT and cmx_last_error names
+ * the index of the source; so are num_sources < 1, a source with both kinds set (a voxel pointer
+ * together with a grid pointer) or none (a source without any pointer is the voxel kind: valid
+ * with both counts 0 and its resolutions set, the single create's empty case), and a resident
+ * source on another device than `device`.  The limits of a dense grid (index range, size of a
+ * level) are argument errors that name the index too, found before anything is allocated.  On
+ * any error (a device allocation that fails half-way included) nothing is left allocated and
+ * every out[k] is NULL. */
+cmx_status cmx_fast3d_create_batch(const cmx_fast3d_options* options,
+                                   const cmx_fast3d_source* sources, int32_t num_sources,
+                                   int32_t device, cmx_fast3d** out /* num_sources */);
 void cmx_fast3d_destroy(cmx_fast3d* matcher);
 
 /* TrajectoryNode::Data (mapping/trajectory_node.h:45-63), the fields the
