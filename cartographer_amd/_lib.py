@@ -52,6 +52,19 @@ class Fast2DSource(C.Structure):
                 ("tsdf", C.c_void_p)]
 
 
+class Grid2DInsertion(C.Structure):
+    """cmx_grid2d_insertion: one (grid, scan) pair of cmx_grid2d_insert_batch."""
+    _fields_ = [("grid", C.c_void_p), ("origin_xy", C.c_void_p), ("returns_xyz", C.c_void_p),
+                ("num_returns", C.c_int32), ("misses_xyz", C.c_void_p), ("num_misses", C.c_int32)]
+
+
+class DebugGrid2DInsertion(C.Structure):
+    """cmx_debug_grid2d_insertion: an insertion of cmx_debug_grid2d_insert_plan (grid by index)."""
+    _fields_ = [("grid", C.c_int32), ("num_returns", C.c_int32), ("origin_xy", C.c_void_p),
+                ("returns_xyz", C.c_void_p), ("misses_xyz", C.c_void_p),
+                ("num_misses", C.c_int32), ("reserved", C.c_int32)]
+
+
 class TSDFInserterOptions2D(C.Structure):
     """cmx_tsdf_inserter_options_2d = proto::TSDFRangeDataInserterOptions2D (+ the
     NormalEstimationOptions2D it holds)."""
@@ -186,7 +199,7 @@ EXPORTED_SYMBOLS = [
     "cmx_version", "cmx_status_string", "cmx_last_error", "cmx_device_count", "cmx_set_stream",
     "cmx_rt2d_match", "cmx_rt2d_match_tsdf", "cmx_grid2d_create", "cmx_grid2d_destroy",
     "cmx_grid2d_get_limits", "cmx_grid2d_download", "cmx_grid2d_crop", "cmx_grid2d_insert",
-    "cmx_rt2d_match_grid",
+    "cmx_rt2d_match_grid", "cmx_grid2d_insert_batch",
     "cmx_tsdf2d_create", "cmx_tsdf2d_destroy", "cmx_tsdf2d_get_limits", "cmx_tsdf2d_download",
     "cmx_tsdf2d_insert", "cmx_tsdf2d_crop", "cmx_rt2d_match_tsdf_grid",
     "cmx_fast2d_create_from_tsdf",
@@ -225,7 +238,8 @@ EXPORTED_SYMBOLS = [
 ]
 
 # include/cartographer_mi355x_debug.h (test and tool switches, not part of the boundary).
-DEBUG_SYMBOLS = ["cmx_debug_set", "cmx_debug_reset", "cmx_debug_fast2d_plan"]
+DEBUG_SYMBOLS = ["cmx_debug_set", "cmx_debug_reset", "cmx_debug_fast2d_plan",
+                 "cmx_debug_grid2d_insert_plan"]
 
 _lib = None
 
@@ -291,6 +305,12 @@ def lib():
     L.cmx_grid3d_download.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, P(C.c_int64)]
     L.cmx_grid2d_insert.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p,
                                     C.c_int32, C.c_float, C.c_float, C.c_int32]
+    if hasattr(L, "cmx_grid2d_insert_batch"):   # (absent from an older library an A/B tool loads)
+        L.cmx_grid2d_insert_batch.argtypes = [P(Grid2DInsertion), C.c_int32, C.c_float, C.c_float,
+                                              C.c_int32]
+        L.cmx_debug_grid2d_insert_plan.argtypes = [P(Grid2DLimits), C.c_int32,
+                                                   P(DebugGrid2DInsertion), C.c_int32,
+                                                   C.c_void_p, P(Grid2DLimits)]
     L.cmx_rt2d_match_grid.argtypes = [P(RtOptions), C.c_void_p, P(Pose2d), C.c_void_p, C.c_int32,
                                       P(C.c_double), P(Pose2d), P(MatchStats)]
     L.cmx_rt2d_match_grid_batch.argtypes = [P(RtOptions), P(C.c_void_p), C.c_int32, C.c_void_p,

@@ -23,18 +23,7 @@
 #include <memory>
 #include <vector>
 
-#include "ray_mask_2d.h"
-#include "scan_matching_2d.h"
-
-struct cmx_grid2d {
-  int device = 0;
-  double resolution = 0., max_x = 0., max_y = 0.;
-  int nx = 0, ny = 0;
-  uint16_t* cells = nullptr;                             // device, nx * ny
-  std::map<uint32_t, uint16_t*> tables;                  // odds tables by float bits, device
-  unsigned long long version = 1;                        // bumped whenever the cells change
-  mutable cmx::Rt2DImageCache rt_image;                  // the real-time matcher's staged image
-};
+#include "grid_2d_internal.h"
 
 namespace cmx {
 namespace {
@@ -74,18 +63,6 @@ void OddsTable(float probability, uint16_t* out /*[32768]*/) {
 }
 
 // ---- device ----------------------------------------------------------------------
-struct GridView {
-  uint16_t* cells;
-  int nx, ny;
-  double fine_resolution, max_x, max_y;                  // superscaled limits (:58-62)
-};
-
-// MapLimits::GetCellIndex on the superscaled limits (mapping/2d/map_limits.h:69-76).
-__device__ __forceinline__ int2 FineIndex(const GridView& g, float px, float py) {
-  return make_int2(LRoundF64((g.max_y - static_cast<double>(py)) / g.fine_resolution - 0.5),
-                   LRoundF64((g.max_x - static_cast<double>(px)) / g.fine_resolution - 0.5));
-}
-
 // ProbabilityGrid::ApplyLookupTable (probability_grid.cc:58-72) for one cell.
 __device__ __forceinline__ void Apply(const GridView& g, int cx, int cy,
                                       const uint16_t* __restrict__ table, int* error) {
@@ -218,6 +195,8 @@ const uint16_t* DeviceTable(cmx_grid2d* g, float probability) {
 }
 
 }  // namespace
+
+void Grid2DOddsTable(float probability, uint16_t* out) { OddsTable(probability, out); }
 }  // namespace cmx
 
 using cmx::Guard;

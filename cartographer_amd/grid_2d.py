@@ -5,7 +5,8 @@ Mirrors what LocalTrajectoryBuilder2D does with the active submap
 (``mapping/internal/2d/local_trajectory_builder_2d.cc:78-80, 288-289``):
 ``ProbabilityGridRangeDataInserter2D::Insert`` (``insert``) and
 ``RealTimeCorrelativeScanMatcher2D::Match`` (``RealTimeCorrelativeScanMatcher2D.match`` accepts
-this class in place of a host ``Grid2D``).  ``TSDF2DOnDevice`` does the same for submaps of
+this class in place of a host ``Grid2D``); ``insert_batch`` makes the insertions of many grids --
+both active submaps, or those of many robots -- in one call.  ``TSDF2DOnDevice`` does the same for submaps of
 ``grid_type = "TSDF"`` with ``TSDFRangeDataInserter2D::Insert``.
 """
 import ctypes as C
@@ -71,6 +72,61 @@ class ProbabilityGridOnDevice:
         from .scan_matching import FastCorrelativeScanMatcher2D
         return FastCorrelativeScanMatcher2D.from_device_grid(
             self, branch_and_bound_depth, linear_search_window, angular_search_window)
+
+
+def _points(xyz, kept):
+    """(pointer or None, count) of an xyz array; the same array object is converted once, so that
+    it reaches the library by the same pointer every time it appears in a call."""
+    if xyz is None:
+        return None, 0
+    if id(xyz) not in kept:
+        kept[id(xyz)] = (xyz, np.ascontiguousarray(xyz, np.float32).reshape(-1, 3))
+    array = kept[id(xyz)][1]
+    return (array.ctypes.data if array.shape[0] else None), array.shape[0]
+
+
+def insert_batch(insertions, hit_probability=0.7, miss_probability=0.4, insert_free_space=True):
+    """cmx_grid2d_insert_batch: ``grid.insert(origin_xy, returns_xyz, misses_xyz)`` for every
+    ``(ProbabilityGridOnDevice, origin_xy, returns_xyz, misses_xyz_or_None)`` of the list, in list
+    order and bit for bit, in shared launches with one synchronisation.  A grid may appear several
+    times; an array object passed several times is one scan and is uploaded once."""
+    insertions = list(insertions)
+    kept = {}                       # id(array) -> (array, float32 copy): alive until the call returns
+    items = (_lib.Grid2DInsertion * max(len(insertions), 1))()
+    for item, (grid, origin_xy, returns_xyz, misses_xyz) in zip(items, insertions):
+        origin = np.ascontiguousarray(origin_xy, np.float32)[:2].copy()
+        kept[id(origin)] = (origin, origin)
+        item.grid, item.origin_xy = grid._h, origin.ctypes.data
+        item.returns_xyz, item.num_returns = _points(returns_xyz, kept)
+        item.misses_xyz, item.num_misses = _points(misses_xyz, kept)
+    check(_lib.lib().cmx_grid2d_insert_batch(items, len(insertions), hit_probability,
+                                             miss_probability, int(insert_free_space)))
+
+
+def insert_batch_plan(limits, insertions):
+    """cmx_debug_grid2d_insert_plan: what one ``insert_batch`` call would do to grids of the given
+    limits (dicts with resolution, max_x, max_y, num_x_cells, num_y_cells), without a device.
+    ``insertions``: ``(grid index, origin_xy, returns_xyz, misses_xyz_or_None)``.  Returns the round
+    of every insertion and the limits of every grid after the call."""
+    insertions = list(insertions)
+    lims = (Grid2DLimits * len(limits))(*[
+        Grid2DLimits(l["resolution"], l["max_x"], l["max_y"], l["num_x_cells"], l["num_y_cells"],
+                     0.0, 0.0) for l in limits])
+    kept = {}
+    items = (_lib.DebugGrid2DInsertion * max(len(insertions), 1))()
+    for item, (grid, origin_xy, returns_xyz, misses_xyz) in zip(items, insertions):
+        origin = np.ascontiguousarray(origin_xy, np.float32)[:2].copy()
+        kept[id(origin)] = (origin, origin)
+        item.grid, item.origin_xy = int(grid), origin.ctypes.data
+        item.returns_xyz, item.num_returns = _points(returns_xyz, kept)
+        item.misses_xyz, item.num_misses = _points(misses_xyz, kept)
+    rounds = np.empty(max(len(insertions), 1), np.int32)
+    final = (Grid2DLimits * len(limits))()
+    check(_lib.lib().cmx_debug_grid2d_insert_plan(lims, len(limits), items, len(insertions),
+                                                  rounds.ctypes.data, final))
+    return [int(r) for r in rounds[:len(insertions)]], [
+        dict(resolution=f.resolution, max_x=f.max_x, max_y=f.max_y, num_x_cells=f.num_x_cells,
+             num_y_cells=f.num_y_cells) for f in final]
 
 
 class TSDF2DOnDevice:

@@ -1,10 +1,11 @@
 // Submap2D / ActiveSubmaps2D with the probability grid RESIDENT IN HBM: the third build of the
 // local-trajectory-builder test.  Same bookkeeping as shims_local/.../submap_2d.h (which restates
 // mapping/2d/submap_2d.cc:70-76,140-155,159-183,221-236), but the grid is a cmx_grid2d:
-// InsertRangeData is cmx_grid2d_insert (the reference's ProbabilityGridRangeDataInserter2D +
-// FinishUpdate on the device, bit for bit), Finish is cmx_grid2d_crop, and grid() hands the
-// matchers a Grid2D that is also a dropin::DeviceGrid2DView, so that the adapters take the
-// *_match_grid entry points: per scan only the point clouds cross PCIe.  With grid_type = "TSDF"
+// InsertRangeData is cmx_grid2d_insert_batch (the reference's ProbabilityGridRangeDataInserter2D +
+// FinishUpdate on the device, bit for bit, for both active submaps in one call), Finish is
+// cmx_grid2d_crop, and grid() hands the matchers a Grid2D that is also a
+// dropin::DeviceGrid2DView, so that the adapters take the *_match_grid entry points: per scan
+// only the point clouds cross PCIe.  With grid_type = "TSDF"
 // the submap is a cmx_tsdf2d instead: cmx_tsdf2d_insert (TSDFRangeDataInserter2D::Insert),
 // cmx_tsdf2d_crop, and a TSDF2D view that is a dropin::DeviceTsdf2DView, so that the matchers take
 // cmx_rt2d_match_tsdf_grid and cmx_ceres2d_match_tsdf_grid.
@@ -130,19 +131,14 @@ class Submap2D {
   int num_range_data() const { return num_range_data_; }
   bool insertion_finished() const { return insertion_finished_; }
 
-  void InsertRangeData(const sensor::RangeData& range_data,
-                       const proto::ProbabilityGridRangeDataInserterOptions2D& options) {
+  // The probability-grid insertion itself is made by ActiveSubmaps2D::InsertRangeData, for both
+  // active submaps in one cmx_grid2d_insert_batch call; these two are Submap2D::InsertRangeData's
+  // bookkeeping before and after it.
+  cmx_grid2d* BeginInsertRangeData() {
     CHECK(!insertion_finished_);
-    const float origin[2] = {range_data.origin.x(), range_data.origin.y()};
-    const std::vector<float> returns = Flatten(range_data.returns);
-    const std::vector<float> misses = Flatten(range_data.misses);
-    DropinCheckOk(cmx_grid2d_insert(device_grid_, origin, returns.data(),
-                                    static_cast<int32_t>(range_data.returns.size()), misses.data(),
-                                    static_cast<int32_t>(range_data.misses.size()),
-                                    static_cast<float>(options.hit_probability()),
-                                    static_cast<float>(options.miss_probability()),
-                                    options.insert_free_space() ? 1 : 0),
-                  "cmx_grid2d_insert");
+    return device_grid_;
+  }
+  void EndInsertRangeData() {
     RefreshView();
     ++num_range_data_;
   }
@@ -166,6 +162,16 @@ class Submap2D {
     RefreshView();
     ++num_range_data_;
   }
+  static std::vector<float> Flatten(const sensor::PointCloud& cloud) {
+    std::vector<float> xyz;
+    xyz.reserve(3 * cloud.size());
+    for (const sensor::RangefinderPoint& p : cloud) {
+      xyz.push_back(p.position.x());
+      xyz.push_back(p.position.y());
+      xyz.push_back(p.position.z());
+    }
+    return xyz;
+  }
   void Finish() {
     CHECK(!insertion_finished_);
     if (device_tsdf_) {
@@ -178,16 +184,6 @@ class Submap2D {
   }
 
  private:
-  static std::vector<float> Flatten(const sensor::PointCloud& cloud) {
-    std::vector<float> xyz;
-    xyz.reserve(3 * cloud.size());
-    for (const sensor::RangefinderPoint& p : cloud) {
-      xyz.push_back(p.position.x());
-      xyz.push_back(p.position.y());
-      xyz.push_back(p.position.z());
-    }
-    return xyz;
-  }
   // A new view only when the limits moved (the grid grew or was cropped): scans of a known area
   // leave the matchers' object alone.
   void RefreshView() {
@@ -242,12 +238,11 @@ class ActiveSubmaps2D {
     if (submaps_.empty() || submaps_.back()->num_range_data() == options_.num_range_data()) {
       AddSubmap(range_data.origin.head<2>());
     }
-    for (auto& submap : submaps_) {
-      if (tsdf())
+    if (tsdf()) {
+      for (auto& submap : submaps_)
         submap->InsertRangeData(range_data, options_.tsdf_range_data_inserter_options_2d());
-      else
-        submap->InsertRangeData(range_data,
-                                options_.probability_grid_range_data_inserter_options_2d());
+    } else {
+      InsertIntoProbabilityGrids(range_data);
     }
     if (submaps_.front()->num_range_data() == 2 * options_.num_range_data()) {
       submaps_.front()->Finish();
@@ -255,6 +250,29 @@ class ActiveSubmaps2D {
     return submaps();
   }
  private:
+  // The same range data into every active submap: one call, the points passed by the same
+  // pointers, so that they cross PCIe once.
+  void InsertIntoProbabilityGrids(const sensor::RangeData& range_data) {
+    const proto::ProbabilityGridRangeDataInserterOptions2D& options =
+        options_.probability_grid_range_data_inserter_options_2d();
+    const float origin[2] = {range_data.origin.x(), range_data.origin.y()};
+    const std::vector<float> returns = Submap2D::Flatten(range_data.returns);
+    const std::vector<float> misses = Submap2D::Flatten(range_data.misses);
+    std::vector<cmx_grid2d_insertion> insertions;
+    for (auto& submap : submaps_) {
+      insertions.push_back(cmx_grid2d_insertion{
+          submap->BeginInsertRangeData(), origin, returns.data(),
+          static_cast<int32_t>(range_data.returns.size()), misses.data(),
+          static_cast<int32_t>(range_data.misses.size())});
+    }
+    DropinCheckOk(cmx_grid2d_insert_batch(insertions.data(),
+                                          static_cast<int32_t>(insertions.size()),
+                                          static_cast<float>(options.hit_probability()),
+                                          static_cast<float>(options.miss_probability()),
+                                          options.insert_free_space() ? 1 : 0),
+                  "cmx_grid2d_insert_batch");
+    for (auto& submap : submaps_) submap->EndInsertRangeData();
+  }
   void AddSubmap(const Eigen::Vector2f& origin) {
     if (submaps_.size() >= 2) {
       CHECK(submaps_.front()->insertion_finished());

@@ -34,6 +34,10 @@
  *   cmx_fast3d_create_batch        the same ctor for many submaps in one call (the
  *                                  DispatchScanMatcherConstruction of a loaded map or of a first
  *                                  global constraint, constraints/constraint_builder_3d.cc:170-198)
+ *   cmx_grid2d_insert_batch        ProbabilityGridRangeDataInserter2D::Insert for many (grid, scan)
+ *                                  pairs in one call: the two insertions of
+ *                                  ActiveSubmaps2D::InsertRangeData (mapping/2d/submap_2d.cc:161-174),
+ *                                  or those of many trajectories
  *
  * Conventions
  *   - Plain C, POD only.  Host pointers are borrowed for the duration of the
@@ -212,6 +216,7 @@ cmx_status cmx_rt2d_score_candidates(const cmx_rt_options* options,
  *                          mapping/internal/2d/ray_to_pixel_mask.cc:34-156); grows the
  *                         limits like GrowAsNeeded / Grid2D::GrowLimits. Points are in the
  *                         map frame (range data already transformed), xyz triples.
+ *   cmx_grid2d_insert_batch  the same for many (grid, range data) pairs in one call (below)
  *   cmx_grid2d_crop       grid = grid->ComputeCroppedGrid(): what Submap2D::Finish does before the
  *                         loop-closure matcher is built (mapping/2d/submap_2d.cc:146-149,
  *                         mapping/2d/probability_grid.cc:90-106, grid_2d.cc:104-114)
@@ -228,6 +233,41 @@ cmx_status cmx_grid2d_insert(cmx_grid2d* grid, const float* origin_xy, const flo
                              int32_t num_returns, const float* misses_xyz, int32_t num_misses,
                              float hit_probability, float miss_probability,
                              int32_t insert_free_space);
+
+/* One insertion of a cmx_grid2d_insert_batch call: the arguments of cmx_grid2d_insert that differ
+ * from insertion to insertion. */
+typedef struct cmx_grid2d_insertion {
+  cmx_grid2d* grid;
+  const float* origin_xy;      /* 2 floats */
+  const float* returns_xyz;    /* num_returns xyz triples, map frame */
+  int32_t num_returns;
+  const float* misses_xyz;
+  int32_t num_misses;
+} cmx_grid2d_insertion;
+
+/* cmx_grid2d_insert(insertions[i] ...) for i = 0 .. num_insertions - 1 in list order, bit for bit
+ * (cells, limits and the staleness of the real-time matcher's cached image), in shared launches:
+ * what ActiveSubmaps2D::InsertRangeData does to its two submaps, or a fleet to the active submaps of
+ * every robot after one cmx_rt2d_match_grid_batch.
+ *   - A grid may appear several times: its insertions apply in list order.  The r-th insertion of
+ *     every grid forms round r; a round is three launches (hits, rays, marker clearing) over all
+ *     its insertions, so the number of launches grows with the most insertions any one grid has,
+ *     not with the number of grids.  One synchronisation per call.
+ *   - Equal returns_xyz (or misses_xyz) pointers are the same scan and cross PCIe once per call;
+ *     their counts must be equal too.
+ *   - An insertion may have no returns, no misses, or neither (the grid still grows around the
+ *     origin), as in the single call.  One set of probabilities holds for the whole call.
+ *   - Every argument check of the single call is made for every insertion before the device is
+ *     touched: CMX_INVALID_ARGUMENT names `insertion <index>` in cmx_last_error and no grid has
+ *     changed.  num_insertions < 1, null `insertions`, a null grid or origin and grids on different
+ *     devices are invalid.
+ *   - Every grid is grown once, to the size its last insertion needs, before anything is inserted.
+ *     When a device allocation fails there (CMX_OUT_OF_MEMORY), no grid has changed: neither its
+ *     size nor its cells, and no insertion has been applied. */
+cmx_status cmx_grid2d_insert_batch(const cmx_grid2d_insertion* insertions,
+                                   int32_t num_insertions, float hit_probability,
+                                   float miss_probability, int32_t insert_free_space);
+
 cmx_status cmx_rt2d_match_grid(const cmx_rt_options* options, const cmx_grid2d* grid,
                                const cmx_pose2d* initial_pose_estimate,
                                const float* point_cloud_xyz, int32_t num_points, double* score,

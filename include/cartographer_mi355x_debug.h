@@ -56,6 +56,27 @@ cmx_status cmx_debug_fast2d_plan(const cmx_fast2d* const* matchers,
                                  float max_range_xy, cmx_debug_fast2d_problem_plan* problems,
                                  cmx_debug_fast2d_launch_plan* launch);
 
+/* The plan of one cmx_grid2d_insert_batch call from the limits of its grids and the points alone:
+ * the round of every insertion (how many earlier insertions of the list go to the same grid) and
+ * the limits every grid has after the call (GrowAsNeeded of every insertion replayed in list
+ * order).  The launch path asks the same function; this entry launches nothing and needs no
+ * device.  `limits` [num_grids] are the grids' limits before the call; an insertion names its grid
+ * by index. */
+typedef struct cmx_debug_grid2d_insertion {
+  int32_t grid;                /* index into `limits` */
+  int32_t num_returns;
+  const float* origin_xy;      /* 2 floats */
+  const float* returns_xyz;
+  const float* misses_xyz;
+  int32_t num_misses;
+  int32_t reserved;
+} cmx_debug_grid2d_insertion;
+
+cmx_status cmx_debug_grid2d_insert_plan(const cmx_grid2d_limits* limits, int32_t num_grids,
+                                        const cmx_debug_grid2d_insertion* insertions,
+                                        int32_t num_insertions, int32_t* rounds,
+                                        cmx_grid2d_limits* final_limits);
+
 #ifdef __cplusplus
 }
 #endif
