@@ -65,6 +65,23 @@ class DebugGrid2DInsertion(C.Structure):
                 ("num_misses", C.c_int32), ("reserved", C.c_int32)]
 
 
+class Grid3DInsertion(C.Structure):
+    """cmx_grid3d_insertion: one (grid, cloud) pair of cmx_grid3d_insert_batch."""
+    _fields_ = [("grid", C.c_void_p), ("origin_xyz", C.c_void_p), ("returns_xyz", C.c_void_p),
+                ("num_returns", C.c_int32), ("reserved", C.c_int32)]
+
+
+class DebugGrid3DState(C.Structure):
+    """cmx_debug_grid3d_state: brick bounds and grid_size of a grid of cmx_debug_grid3d_insert_plan."""
+    _fields_ = [("lo", C.c_int32 * 3), ("dims", C.c_int32 * 3), ("grid_size", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
+class DebugGrid3DInsertion(C.Structure):
+    """cmx_debug_grid3d_insertion: an insertion of cmx_debug_grid3d_insert_plan (grid by index)."""
+    _fields_ = [("grid", C.c_int32), ("reserved", C.c_int32), ("box", C.c_int32 * 6)]
+
+
 class TSDFInserterOptions2D(C.Structure):
     """cmx_tsdf_inserter_options_2d = proto::TSDFRangeDataInserterOptions2D (+ the
     NormalEstimationOptions2D it holds)."""
@@ -206,8 +223,8 @@ EXPORTED_SYMBOLS = [
     "cmx_rt2d_match_tsdf_grid_batch", "cmx_rt2d_match_tsdf_grid_batch_resident",
     "cmx_rt2d_match_grid_batch", "cmx_rt2d_match_grid_batch_resident",
     "cmx_grid3d_create", "cmx_grid3d_destroy", "cmx_grid3d_insert", "cmx_grid3d_info",
-    "cmx_grid3d_download",
-    "cmx_fast2d_create", "cmx_fast2d_create_from_grid", "cmx_fast2d_create_batch",
+    "cmx_grid3d_download", "cmx_grid3d_insert_batch",
+    "cmx_fast2d_create","cmx_fast2d_create_from_grid", "cmx_fast2d_create_batch",
     "cmx_fast2d_destroy", "cmx_fast2d_match",
     "cmx_fast2d_match_full_submap", "cmx_fast2d_match_batch",
     "cmx_fast2d_match_pairs", "cmx_fast2d_match_pairs_resident",
@@ -239,7 +256,7 @@ EXPORTED_SYMBOLS = [
 
 # include/cartographer_mi355x_debug.h (test and tool switches, not part of the boundary).
 DEBUG_SYMBOLS = ["cmx_debug_set", "cmx_debug_reset", "cmx_debug_fast2d_plan",
-                 "cmx_debug_grid2d_insert_plan"]
+                 "cmx_debug_grid2d_insert_plan", "cmx_debug_grid3d_insert_plan"]
 
 _lib = None
 
@@ -289,6 +306,12 @@ def lib():
     L.cmx_grid3d_destroy.restype = None
     L.cmx_grid3d_insert.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_float,
                                     C.c_float, C.c_int32]
+    if hasattr(L, "cmx_grid3d_insert_batch"):   # (absent from an older library an A/B tool loads)
+        L.cmx_grid3d_insert_batch.argtypes = [P(Grid3DInsertion), C.c_int32, C.c_float, C.c_float,
+                                              C.c_int32]
+        L.cmx_debug_grid3d_insert_plan.argtypes = [P(DebugGrid3DState), C.c_int32,
+                                                   P(DebugGrid3DInsertion), C.c_int32,
+                                                   C.c_void_p, P(DebugGrid3DState)]
     L.cmx_grid3d_info.argtypes = [C.c_void_p, P(C.c_float), P(C.c_int32), P(C.c_int64)]
     if hasattr(L, "cmx_intensity_grid3d_create"):      # (absent from the round-3 library)
         L.cmx_intensity_grid3d_create.argtypes = [C.c_float, C.c_int32, P(C.c_void_p)]

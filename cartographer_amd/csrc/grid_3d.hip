@@ -18,6 +18,7 @@
 // every hit, then every miss sample.  All hits apply one table to the pre-insert value and so do
 // all misses, so "first writer wins" is order-independent inside a phase: one kernel per phase
 // (a thread per return / per (return, sample)), one that clears the markers.
+// grid_3d_internal.h holds what cmx_grid3d_insert_batch (grid_3d_batch.hip) shares with this file.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -25,19 +26,8 @@
 #include <memory>
 #include <vector>
 
-#include "cmx_common.h"
-#include "cmx_device.h"
-#include "cmx_odds_table.h"
+#include "grid_3d_internal.h"
 #include "scan_matching_3d.h"
-
-struct cmx_grid3d {
-  int device = 0;
-  float resolution = 0.f;
-  int grid_size = 128;                       // DynamicGrid starts at 2 x 64 voxels per axis
-  int lo[3] = {0, 0, 0}, dims[3] = {0, 0, 0};   // brick bounds; empty while dims[0] == 0
-  uint16_t* cells = nullptr;                 // device, dims[0] * dims[1] * dims[2]
-  std::map<uint32_t, uint16_t*> tables;      // odds tables by float bits, device
-};
 
 // IntensityHybridGrid (mapping/3d/hybrid_grid.h:543-571): AverageIntensityData {sum, count} per
 // voxel, here two dense bricks over the bounding box of the voxels written so far (x fastest),
@@ -54,7 +44,6 @@ struct cmx_intensity_grid3d {
 };
 
 namespace cmx {
-namespace {
 
 const uint16_t* DeviceTable(cmx_grid3d* g, float probability) {
   CMX_REQUIRE(probability > 0.f && probability < 1.f, "probability must be in (0, 1)");
@@ -71,41 +60,7 @@ const uint16_t* DeviceTable(cmx_grid3d* g, float probability) {
   return table;
 }
 
-// ---- device ------------------------------------------------------------------------------------
-struct BrickView {
-  uint16_t* cells;
-  int lo_x, lo_y, lo_z, nx, ny, nz;
-};
-
-// HybridGridBase::GetCellIndex (hybrid_grid.h:428-433): f32 divide, lround.
-__device__ __forceinline__ int3 CellOf(const float* __restrict__ p, float resolution) {
-  return make_int3(LRoundF32(p[0] / resolution), LRoundF32(p[1] / resolution),
-                   LRoundF32(p[2] / resolution));
-}
-
-// The sample `position` of ray origin -> hit (range_data_inserter_3d.cc:37-52):
-// origin_cell + delta * position / num_samples, integer arithmetic truncating towards zero.
-__device__ __forceinline__ int3 MissCell(int3 origin, int3 delta, int position, int num_samples) {
-  return make_int3(origin.x + delta.x * position / num_samples,
-                   origin.y + delta.y * position / num_samples,
-                   origin.z + delta.z * position / num_samples);
-}
-
-// HybridGrid::ApplyLookupTable (hybrid_grid.h:471-481) for one voxel.
-__device__ __forceinline__ void Apply(const BrickView& b, int3 c,
-                                      const uint16_t* __restrict__ table, int* error) {
-  const int x = c.x - b.lo_x, y = c.y - b.lo_y, z = c.z - b.lo_z;
-  if (static_cast<unsigned>(x) >= static_cast<unsigned>(b.nx) ||
-      static_cast<unsigned>(y) >= static_cast<unsigned>(b.ny) ||
-      static_cast<unsigned>(z) >= static_cast<unsigned>(b.nz)) {
-    *error = 1;                                          // the extent pass sized the brick
-    return;
-  }
-  uint16_t* cell = b.cells + (static_cast<size_t>(z) * b.ny + y) * b.nx + x;
-  const uint16_t old = *cell;
-  if (old >= kUpdateMarker) return;
-  *cell = table[old];
-}
+namespace {
 
 // Pass 0: the bounding box of every voxel this insertion touches (hits and miss samples), so
 // that the host can grow the brick and grid_size() before anything is written.
@@ -201,41 +156,49 @@ __global__ void Grid3DCountKernel(const uint16_t* __restrict__ cells, size_t cou
   if ((threadIdx.x & 63) == 0 && in_wave) atomicAdd(total, static_cast<unsigned long long>(in_wave));
 }
 
-int FloorTo(int v, int m) { return v >= 0 ? v / m * m : -((-v + m - 1) / m * m); }
+}  // namespace
 
-// Makes the brick cover [lo, hi] (inclusive), keeping its contents.
-void EnsureBrick(cmx_grid3d* g, Workspace& ws, const int lo[3], const int hi[3]) {
-  int nlo[3], nhi[3];
-  bool change = g->dims[0] == 0;
-  for (int k = 0; k < 3; ++k) {
-    const int cur_lo = g->lo[k], cur_hi = g->lo[k] + g->dims[k] - 1;
-    // Grow in steps of 16 voxels so that a slowly widening scene does not re-allocate per scan.
-    nlo[k] = g->dims[0] == 0 ? FloorTo(lo[k], 16) : std::min(cur_lo, FloorTo(lo[k], 16));
-    nhi[k] = g->dims[0] == 0 ? FloorTo(hi[k], 16) + 15 : std::max(cur_hi, FloorTo(hi[k], 16) + 15);
-    change |= nlo[k] != cur_lo || nhi[k] != cur_hi;
-  }
-  if (!change) return;
-  const int ndims[3] = {nhi[0] - nlo[0] + 1, nhi[1] - nlo[1] + 1, nhi[2] - nlo[2] + 1};
-  const long long count = static_cast<long long>(ndims[0]) * ndims[1] * ndims[2];   // each < 2^21
-  CMX_REQUIRE(count < (1ll << 30), "dense voxel brick of %d x %d x %d is too large", ndims[0],
-              ndims[1], ndims[2]);
+uint16_t* StageGrownBrick(const cmx_grid3d* g, const BrickBounds& to, hipStream_t stream) {
+  const size_t bytes = static_cast<size_t>(BrickCells(to)) * sizeof(uint16_t);
   uint16_t* grown = nullptr;
-  CMX_HIP(hipMalloc(reinterpret_cast<void**>(&grown), static_cast<size_t>(count) * sizeof(uint16_t)));
-  hipError_t err = hipMemsetAsync(grown, 0, static_cast<size_t>(count) * sizeof(uint16_t), ws.stream);
+  CMX_HIP(hipMalloc(reinterpret_cast<void**>(&grown), bytes));
+  hipError_t err = hipMemsetAsync(grown, 0, bytes, stream);
   if (err == hipSuccess && g->dims[0] != 0) {
-    Grid3DCopyKernel<<<dim3(DivUp(g->dims[0], 256), g->dims[1], g->dims[2]), 256, 0, ws.stream>>>(
-        g->cells, g->dims[0], g->dims[1], grown, ndims[0], ndims[1], g->lo[0] - nlo[0],
-        g->lo[1] - nlo[1], g->lo[2] - nlo[2]);
+    Grid3DCopyKernel<<<dim3(DivUp(g->dims[0], 256), g->dims[1], g->dims[2]), 256, 0, stream>>>(
+        g->cells, g->dims[0], g->dims[1], grown, to.dims[0], to.dims[1], g->lo[0] - to.lo[0],
+        g->lo[1] - to.lo[1], g->lo[2] - to.lo[2]);
     err = hipGetLastError();
   }
-  if (err == hipSuccess) err = hipStreamSynchronize(ws.stream);
   if (err != hipSuccess) {
     (void)hipFree(grown);
     CMX_HIP(err);
   }
-  if (g->cells) CMX_HIP(hipFree(g->cells));
+  return grown;
+}
+
+void CommitBrick(cmx_grid3d* g, uint16_t* grown, const BrickBounds& to) {
+  uint16_t* old = g->cells;
   g->cells = grown;
-  for (int k = 0; k < 3; ++k) { g->lo[k] = nlo[k]; g->dims[k] = ndims[k]; }
+  for (int k = 0; k < 3; ++k) { g->lo[k] = to.lo[k]; g->dims[k] = to.dims[k]; }
+  if (old) CMX_HIP(hipFree(old));
+}
+
+namespace {
+
+// Makes the brick cover [lo, hi] (inclusive), keeping its contents.
+void EnsureBrick(cmx_grid3d* g, Workspace& ws, const int lo[3], const int hi[3]) {
+  BrickBounds cur, to;
+  for (int k = 0; k < 3; ++k) { cur.lo[k] = g->lo[k]; cur.dims[k] = g->dims[k]; }
+  if (!PlanBrick(cur, lo, hi, &to)) return;
+  CMX_REQUIRE(BrickCells(to) < kMaxBrickCells, "dense voxel brick of %d x %d x %d is too large",
+              to.dims[0], to.dims[1], to.dims[2]);
+  uint16_t* grown = StageGrownBrick(g, to, ws.stream);
+  const hipError_t err = hipStreamSynchronize(ws.stream);
+  if (err != hipSuccess) {
+    (void)hipFree(grown);
+    CMX_HIP(err);
+  }
+  CommitBrick(g, grown, to);
 }
 
 // ---- IntensityHybridGrid -----------------------------------------------------------------------
@@ -545,9 +508,7 @@ void InsertRangeData(cmx_grid3d* grid, cmx_intensity_grid3d* intensity_grid, con
     for (int k = 0; k < 3; ++k)
       CMX_REQUIRE(lo[k] > -(1 << 20) && hi[k] < (1 << 20), "voxel index out of range");
     // DynamicGrid::mutable_value grows until every written index fits (hybrid_grid.h:282-287).
-    const auto fits = [&](int v) { return v >= -(grid->grid_size / 2) && v < grid->grid_size / 2; };
-    for (int k = 0; k < 3; ++k)
-      while (!(fits(lo[k]) && fits(hi[k]))) grid->grid_size *= 2;
+    grid->grid_size = PlanGridSize(grid->grid_size, lo, hi);
     EnsureBrick(grid, *ws, lo, hi);
 
     const BrickView view{grid->cells, grid->lo[0], grid->lo[1], grid->lo[2], grid->dims[0],

@@ -4,7 +4,8 @@ grid across PCIe.
 Mirrors what LocalTrajectoryBuilder3D does with an active submap's grids:
 ``RangeDataInserter3D::Insert`` (``mapping/3d/range_data_inserter_3d.cc:93-114``, ``insert``);
 ``voxels()`` is the flattened list ``HybridGrid::Iterator`` yields, which is what
-``scan_matching_3d`` takes for matching.
+``scan_matching_3d`` takes for matching; ``insert_batch`` makes the insertions of many grids -- the
+high- and low-resolution grids of both active submaps, or those of many robots -- in one call.
 """
 import ctypes as C
 
@@ -74,6 +75,55 @@ class HybridGridOnDevice:
                                              C.byref(got)))
         assert got.value == count
         return out
+
+
+def insert_batch(insertions, hit_probability=0.7, miss_probability=0.4, num_free_space_voxels=5):
+    """cmx_grid3d_insert_batch: ``grid.insert(origin_xyz, returns_xyz)`` for every
+    ``(HybridGridOnDevice, origin_xyz, returns_xyz)`` of the list, in list order and bit for bit,
+    in shared launches.  A grid may appear several times and grids of different resolutions may
+    share a call; an array object passed several times is one cloud and is uploaded once."""
+    insertions = list(insertions)
+    kept = {}                       # id(array) -> (array, float32 copy): alive until the call returns
+    items = (_lib.Grid3DInsertion * max(len(insertions), 1))()
+    for item, (grid, origin_xyz, returns_xyz) in zip(items, insertions):
+        origin = np.ascontiguousarray(origin_xyz, np.float32).reshape(3).copy()
+        kept[id(origin)] = (origin, origin)
+        if id(returns_xyz) not in kept:
+            kept[id(returns_xyz)] = (returns_xyz,
+                                     np.ascontiguousarray(returns_xyz, np.float32).reshape(-1, 3))
+        ret = kept[id(returns_xyz)][1]
+        item.grid, item.origin_xyz = grid._h, origin.ctypes.data
+        item.returns_xyz = ret.ctypes.data if ret.shape[0] else None
+        item.num_returns = ret.shape[0]
+    check(_lib.lib().cmx_grid3d_insert_batch(items, len(insertions), hit_probability,
+                                             miss_probability, num_free_space_voxels))
+
+
+def insert_batch_plan(grids, insertions):
+    """cmx_debug_grid3d_insert_plan: what one ``insert_batch`` call would do to grids in the given
+    states -- dicts with ``lo`` and ``dims`` (the brick's lowest voxel and extent, or None for a
+    grid nothing was inserted into) and ``grid_size`` -- without a device.  ``insertions``:
+    ``(grid index, box)``, ``box`` the touched voxels as (min x, y, z, max x, y, z) or None for an
+    insertion without returns.  Returns the round of every insertion and the state of every grid
+    after the call."""
+    insertions = list(insertions)
+    states = (_lib.DebugGrid3DState * len(grids))()
+    for state, grid in zip(states, grids):
+        if grid.get("dims") is not None:
+            state.lo[:] = [int(v) for v in grid["lo"]]
+            state.dims[:] = [int(v) for v in grid["dims"]]
+        state.grid_size = int(grid["grid_size"])
+    items = (_lib.DebugGrid3DInsertion * max(len(insertions), 1))()
+    for item, (grid, box) in zip(items, insertions):
+        item.grid = int(grid)
+        item.box[:] = ([2**31 - 1] * 3 + [-2**31] * 3) if box is None else [int(v) for v in box]
+    rounds = np.empty(max(len(insertions), 1), np.int32)
+    final = (_lib.DebugGrid3DState * len(grids))()
+    check(_lib.lib().cmx_debug_grid3d_insert_plan(states, len(grids), items, len(insertions),
+                                                  rounds.ctypes.data, final))
+    return [int(r) for r in rounds[:len(insertions)]], [
+        dict(lo=tuple(f.lo) if f.dims[0] else None, dims=tuple(f.dims) if f.dims[0] else None,
+             grid_size=f.grid_size) for f in final]
 
 
 class IntensityHybridGridOnDevice:

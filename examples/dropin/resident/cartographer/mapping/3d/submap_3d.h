@@ -1,8 +1,8 @@
 // Submap3D / ActiveSubmaps3D with both hybrid grids RESIDENT IN HBM: the third build of the 3D
 // local-trajectory-builder test.  Same bookkeeping as shims_local/.../submap_3d.h (which restates
-// mapping/3d/submap_3d.cc:162-177,276-327), but each grid is a cmx_grid3d: InsertData is two
-// cmx_grid3d_insert calls (the reference's RangeDataInserter3D::Insert on the device, bit for
-// bit).  The HybridGrid objects the accessors hand out stay empty; their addresses are registered
+// mapping/3d/submap_3d.cc:162-177,276-327), but each grid is a cmx_grid3d: InsertData is one
+// cmx_grid3d_insert_batch call for the high- and low-resolution grids of both active submaps (the
+// reference's RangeDataInserter3D::Insert on the device, bit for bit).  The HybridGrid objects the accessors hand out stay empty; their addresses are registered
 // with the device grids (device_grids.h), so that the adapters take cmx_rt3d_match_grid and
 // cmx_ceres3d_match_grids: per scan only the point clouds cross PCIe.
 #ifndef DROPIN_RESIDENT_SUBMAP_3D_H_
@@ -65,31 +65,34 @@ class Submap3D {
   const Eigen::VectorXf& rotational_scan_matcher_histogram() const {
     return rotational_scan_matcher_histogram_;
   }
-  void InsertData(const sensor::RangeData& range_data_in_local,
-                  const proto::RangeDataInserterOptions3D& inserter, float high_resolution_max_range,
-                  const Eigen::Quaterniond& local_from_gravity_aligned,
-                  const Eigen::VectorXf& scan_histogram_in_gravity) {
+  // The insertion itself is made by ActiveSubmaps3D::InsertData, for the grids of both active
+  // submaps in one cmx_grid3d_insert_batch call; these two are Submap3D::InsertData's halves
+  // before and after it.  `staged` holds the clouds in this submap's frame until the call is made.
+  struct StagedClouds {
+    float origin[3];
+    std::vector<float> all, near;
+  };
+  void BeginInsertData(const sensor::RangeData& range_data_in_local, float high_resolution_max_range,
+                       StagedClouds* staged, std::vector<cmx_grid3d_insertion>* insertions) {
     CHECK(!insertion_finished_);
     const sensor::RangeData in_submap =
         sensor::TransformRangeData(range_data_in_local, local_pose_.inverse().cast<float>());
-    const float origin[3] = {in_submap.origin.x(), in_submap.origin.y(), in_submap.origin.z()};
-    std::vector<float> all, near;
+    staged->origin[0] = in_submap.origin.x();
+    staged->origin[1] = in_submap.origin.y();
+    staged->origin[2] = in_submap.origin.z();
     for (const sensor::RangefinderPoint& hit : in_submap.returns) {
       const float xyz[3] = {hit.position.x(), hit.position.y(), hit.position.z()};
-      all.insert(all.end(), xyz, xyz + 3);
+      staged->all.insert(staged->all.end(), xyz, xyz + 3);
       if ((hit.position - in_submap.origin).norm() <= high_resolution_max_range)
-        near.insert(near.end(), xyz, xyz + 3);
+        staged->near.insert(staged->near.end(), xyz, xyz + 3);
     }
-    DropinCheckOk(cmx_grid3d_insert(high_, origin, near.data(), static_cast<int32_t>(near.size() / 3),
-                                    static_cast<float>(inserter.hit_probability()),
-                                    static_cast<float>(inserter.miss_probability()),
-                                    inserter.num_free_space_voxels()),
-                  "cmx_grid3d_insert");
-    DropinCheckOk(cmx_grid3d_insert(low_, origin, all.data(), static_cast<int32_t>(all.size() / 3),
-                                    static_cast<float>(inserter.hit_probability()),
-                                    static_cast<float>(inserter.miss_probability()),
-                                    inserter.num_free_space_voxels()),
-                  "cmx_grid3d_insert");
+    insertions->push_back(cmx_grid3d_insertion{high_, staged->origin, staged->near.data(),
+                                               static_cast<int32_t>(staged->near.size() / 3), 0});
+    insertions->push_back(cmx_grid3d_insertion{low_, staged->origin, staged->all.data(),
+                                               static_cast<int32_t>(staged->all.size() / 3), 0});
+  }
+  void EndInsertData(const Eigen::Quaterniond& local_from_gravity_aligned,
+                     const Eigen::VectorXf& scan_histogram_in_gravity) {
     ++num_range_data_;
     const float yaw_in_submap_from_gravity =
         transform::GetYaw(local_pose_.inverse().rotation() * local_from_gravity_aligned);
@@ -150,10 +153,23 @@ class ActiveSubmaps3D {
           transform::Rigid3d(range_data.origin.cast<double>(), local_from_gravity_aligned),
           Eigen::VectorXf::Zero(rotational_scan_matcher_histogram_in_gravity.size()), device_));
     }
+    // Both grids of every active submap in one call: four insertions, or two while only one
+    // submap exists.
+    const proto::RangeDataInserterOptions3D& inserter = options_.range_data_inserter_options();
+    std::vector<Submap3D::StagedClouds> staged(submaps_.size());
+    std::vector<cmx_grid3d_insertion> insertions;
+    for (size_t i = 0; i != submaps_.size(); ++i)
+      submaps_[i]->BeginInsertData(range_data, options_.high_resolution_max_range(), &staged[i],
+                                   &insertions);
+    DropinCheckOk(cmx_grid3d_insert_batch(insertions.data(),
+                                          static_cast<int32_t>(insertions.size()),
+                                          static_cast<float>(inserter.hit_probability()),
+                                          static_cast<float>(inserter.miss_probability()),
+                                          inserter.num_free_space_voxels()),
+                  "cmx_grid3d_insert_batch");
     for (auto& submap : submaps_)
-      submap->InsertData(range_data, options_.range_data_inserter_options(),
-                         options_.high_resolution_max_range(), local_from_gravity_aligned,
-                         rotational_scan_matcher_histogram_in_gravity);
+      submap->EndInsertData(local_from_gravity_aligned,
+                            rotational_scan_matcher_histogram_in_gravity);
     if (submaps_.front()->num_range_data() == 2 * options_.num_range_data())
       submaps_.front()->Finish();
     return submaps();

@@ -38,6 +38,10 @@
  *                                  pairs in one call: the two insertions of
  *                                  ActiveSubmaps2D::InsertRangeData (mapping/2d/submap_2d.cc:161-174),
  *                                  or those of many trajectories
+ *   cmx_grid3d_insert_batch        RangeDataInserter3D::Insert for many (grid, cloud) pairs in one
+ *                                  call: the four insertions of ActiveSubmaps3D::InsertData
+ *                                  (mapping/3d/submap_3d.cc:271-287,310-329), or those of many
+ *                                  trajectories
  *
  * Conventions
  *   - Plain C, POD only.  Host pointers are borrowed for the duration of the
@@ -701,7 +705,8 @@ cmx_status cmx_rt3d_match(const cmx_rt_options* options, float grid_resolution,
  *                        (mapping/3d/range_data_inserter_3d.cc:27-52, :93-114): hits, then the last
  *                        `num_free_space_voxels` voxels of every ray as misses, FinishUpdate;
  *                        points in the map frame, xyz triples
- *   cmx_grid3d_info      resolution(), DynamicGrid::grid_size() (hybrid_grid.h:259,381-398) and
+ *   cmx_grid3d_insert_batch  the same for many (grid, cloud) pairs in one call (below)
+ *   cmx_grid3d_info     resolution(), DynamicGrid::grid_size() (hybrid_grid.h:259,381-398) and
  *                        the number of known voxels
  *   cmx_grid3d_download  the voxels HybridGrid::Iterator yields (hybrid_grid.h:304-372), sorted
  *                        (z, y, x): the list cmx_rt3d_match / cmx_fast3d_create take */
@@ -711,6 +716,50 @@ void cmx_grid3d_destroy(cmx_grid3d* grid);
 cmx_status cmx_grid3d_insert(cmx_grid3d* grid, const float* origin_xyz, const float* returns_xyz,
                              int32_t num_returns, float hit_probability, float miss_probability,
                              int32_t num_free_space_voxels);
+
+/* One insertion of a cmx_grid3d_insert_batch call: the arguments of cmx_grid3d_insert that differ
+ * from insertion to insertion. */
+typedef struct cmx_grid3d_insertion {
+  cmx_grid3d* grid;
+  const float* origin_xyz;     /* 3 floats */
+  const float* returns_xyz;    /* num_returns xyz triples, map frame */
+  int32_t num_returns;
+  int32_t reserved;            /* 0 */
+} cmx_grid3d_insertion;
+
+/* cmx_grid3d_insert(insertions[i] ...) for i = 0 .. num_insertions - 1 in list order, bit for bit
+ * (every voxel value, grid_size and the brick bounds), in shared launches: what
+ * ActiveSubmaps3D::InsertData does to the high- and low-resolution grids of its two submaps, or a
+ * fleet to the active submaps of every robot after one cmx_fast3d_match_pairs.
+ *   - Grids of different resolutions may share a call.  One set of probabilities and one
+ *     num_free_space_voxels hold for the whole call.
+ *   - A grid may appear several times: its insertions apply in list order.  The r-th insertion of
+ *     every grid forms round r; a round is three launches (hits, miss samples, marker clearing)
+ *     over all its insertions, so the number of launches grows with the most insertions any one
+ *     grid has, not with the number of grids.
+ *   - One extent launch for the whole call finds the touched voxels and the rays of 2^15 voxels or
+ *     more of every insertion; the host reads it back once and plans the growth of all grids.  Two
+ *     stream synchronisations per call: after that pass and at the end.
+ *   - The clouds go up in one staged copy.  Equal returns_xyz pointers are the same cloud and cross
+ *     PCIe once per call; their counts must be equal too.
+ *   - An insertion with num_returns == 0 does nothing to its grid, as in the single call; it still
+ *     takes its place in the count of rounds.
+ *   - Every argument check of the single call is made for every insertion before the device is
+ *     touched: CMX_INVALID_ARGUMENT names `insertion <index>` in cmx_last_error.  num_insertions
+ *     < 1, null `insertions`, a null grid or origin, num_returns < 0, num_returns > 0 with null
+ *     returns, reserved != 0, num_free_space_voxels < 0, probabilities outside (0, 1) and grids on
+ *     different devices are invalid.
+ *   - A ray of 2^15 voxels or more and a voxel index outside +-2^20 are found by the extent pass:
+ *     CMX_INVALID_ARGUMENT names the first such insertion, and no grid has changed: not its brick,
+ *     its grid_size or any cell.
+ *   - Every grid is grown once, to what its last insertion needs, before anything is inserted, and
+ *     all new bricks are allocated before any old one is released.  When an allocation fails there
+ *     (CMX_OUT_OF_MEMORY), no grid has changed.
+ * cmx_grid3d_insert_with_intensities has no batch form. */
+cmx_status cmx_grid3d_insert_batch(const cmx_grid3d_insertion* insertions, int32_t num_insertions,
+                                   float hit_probability, float miss_probability,
+                                   int32_t num_free_space_voxels);
+
 cmx_status cmx_grid3d_info(const cmx_grid3d* grid, float* resolution, int32_t* grid_size,
                            int64_t* num_voxels);
 cmx_status cmx_grid3d_download(const cmx_grid3d* grid, cmx_voxel* voxels, int64_t capacity,

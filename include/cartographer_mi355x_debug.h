@@ -77,6 +77,32 @@ cmx_status cmx_debug_grid2d_insert_plan(const cmx_grid2d_limits* limits, int32_t
                                         int32_t num_insertions, int32_t* rounds,
                                         cmx_grid2d_limits* final_limits);
 
+/* The plan of one cmx_grid3d_insert_batch call from the state of its grids before the call and the
+ * box of voxels every insertion touches (what the call's extent pass reads back): the round of
+ * every insertion (how many earlier insertions of the list go to the same grid) and the brick
+ * bounds and grid_size every grid has after the call (the growth steps of cmx_grid3d_insert
+ * replayed in list order: the brick becomes the union of the 16-aligned boxes, grid_size doubles
+ * until every index lies in [-grid_size / 2, grid_size / 2)).  The launch path asks the same
+ * function; this entry launches nothing and needs no device.  An insertion names its grid by
+ * index; a voxel index outside +-2^20 is CMX_INVALID_ARGUMENT naming the insertion. */
+typedef struct cmx_debug_grid3d_state {
+  int32_t lo[3];               /* lowest voxel of the brick */
+  int32_t dims[3];             /* its extent in voxels; all 0: nothing inserted yet */
+  int32_t grid_size;           /* DynamicGrid::grid_size(), 128 for a new grid */
+  int32_t reserved;
+} cmx_debug_grid3d_state;
+
+typedef struct cmx_debug_grid3d_insertion {
+  int32_t grid;                /* index into `grids` */
+  int32_t reserved;
+  int32_t box[6];              /* min x, y, z, max x, y, z; min x > max x: touches no voxel */
+} cmx_debug_grid3d_insertion;
+
+cmx_status cmx_debug_grid3d_insert_plan(const cmx_debug_grid3d_state* grids, int32_t num_grids,
+                                        const cmx_debug_grid3d_insertion* insertions,
+                                        int32_t num_insertions, int32_t* rounds,
+                                        cmx_debug_grid3d_state* final_states);
+
 #ifdef __cplusplus
 }
 #endif
