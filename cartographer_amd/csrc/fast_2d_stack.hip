@@ -10,6 +10,7 @@
 #include <string>
 #include <vector>
 
+#include "cmx_batch.h"
 #include "fast_2d_internal.h"
 
 struct cmx_grid2d;   // grid_2d.hip
@@ -212,17 +213,7 @@ struct StackProblem {
   float min_cc, max_cc;
 };
 
-// first[e] = first block of entry e of the launch, first[num] = blocks of the launch: the entry
-// that owns `block` (entries without blocks own none).
-__device__ __forceinline__ int EntryOfBlock(const int* __restrict__ first, int num, int block) {
-  int lo = 0, hi = num;     // first[lo] <= block < first[hi]
-  while (hi - lo > 1) {
-    const int mid = (lo + hi) >> 1;
-    if (first[mid] <= block) lo = mid; else hi = mid;
-  }
-  return lo;
-}
-
+// first[e] = first block of entry e of a launch, first[num] = its blocks: EntryOfBlock (cmx_batch.h).
 __global__ void BatchLevel0Kernel(const StackProblem* __restrict__ problems,
                                   const int* __restrict__ first, int num) {
   const int p = EntryOfBlock(first, num, blockIdx.x);
@@ -300,8 +291,6 @@ __global__ void BatchPlanesKernel(const StackProblem* __restrict__ problems,
 constexpr size_t kChainStagingBytes = size_t(32) << 20;
 constexpr long long kChainBlocks = 1ll << 30;
 constexpr int kChainMatchers = 8192;
-
-size_t Align256(size_t v) { return (v + 255) & ~size_t(255); }
 
 }  // namespace
 
@@ -382,7 +371,7 @@ Fast2DMatcher::Fast2DMatcher(const cmx_fast2d_options& options, const cmx_grid2d
     level_offsets_[i] = total;
     levels_[i].wx = nx + w - 1;
     levels_[i].wy = ny + w - 1;
-    total += (static_cast<size_t>(levels_[i].wx) * levels_[i].wy + 255) & ~size_t(255);
+    total += Align256(static_cast<size_t>(levels_[i].wx) * levels_[i].wy);
   }
   CMX_HIP(hipMalloc(&stack_mem_, total));
   for (int i = 0; i < depth; ++i)
@@ -536,26 +525,18 @@ Fast2DMatcher::Fast2DMatcher(BatchTag, const cmx_fast2d_options& options,
 
 namespace {
 
-// The launches of one chain: matchers [begin, end) of the batch.
-struct StackChain {
-  int begin = 0, end = 0;
-  size_t staged_cells = 0;       // bytes of host cells, every grid from a 256-byte boundary
-};
-
-long long BlocksOf(long long cells) { return (cells + kStackTile - 1) / kStackTile; }
-
 // Blocks over all launches of a chain that one matcher adds (the bound of kChainBlocks).
 long long ChainBlocksOf(const Fast2DMatcher& m) {
   long long blocks = BlocksOf(static_cast<long long>(m.limits().num_x_cells) *
-                              m.limits().num_y_cells);
+                              m.limits().num_y_cells, kStackTile);
   for (int i = 0; i < m.depth(); ++i) {
     const LevelDesc& L = m.level(i);
-    if (i > 0) blocks += BlocksOf(static_cast<long long>(L.wx) * L.wy);
-    blocks += BlocksOf(QuadSlots(L.qy, L.qtx));
+    if (i > 0) blocks += BlocksOf(static_cast<long long>(L.wx) * L.wy, kStackTile);
+    blocks += BlocksOf(QuadSlots(L.qy, L.qtx), kStackTile);
   }
   if (m.planes())
     blocks += BlocksOf((static_cast<long long>(1) << (2 * (m.depth() - 1))) * m.plane_stride() +
-                       m.plane_stride());
+                       m.plane_stride(), kStackTile);
   return blocks;
 }
 
@@ -580,52 +561,41 @@ std::vector<std::unique_ptr<Fast2DMatcher>> Fast2DMatcher::BuildBatch(
   const double alloc_us = since(lap);
 
   const int most = Debug().fast2d_create_chain > 0 ? Debug().fast2d_create_chain : kChainMatchers;
-  std::vector<StackChain> chains;
-  for (int k = 0; k < num;) {
-    StackChain chain;
-    chain.begin = k;
-    long long blocks = 0;
-    for (; k < num && k - chain.begin < most; ++k) {
-      const size_t staged = sources[k].cells_on_device ? 0 : Align256(
-          static_cast<size_t>(sources[k].limits.num_x_cells) * sources[k].limits.num_y_cells *
-          sizeof(uint16_t));
-      const long long add = ChainBlocksOf(*matchers[k]);
-      // (a submap that exceeds a bound alone still goes out: as a chain of its own)
-      if (k > chain.begin &&
-          (chain.staged_cells + staged > kChainStagingBytes || blocks + add > kChainBlocks))
-        break;
-      chain.staged_cells += staged;
-      blocks += add;
-    }
-    chain.end = k;
-    chains.push_back(chain);
-  }
+  // The chains; total[0]: bytes of host cells staged, every grid from a 256-byte boundary.
+  const std::vector<LaunchSet> chains = CutSets(
+      std::vector<int>(num, 0), most, {kChainStagingBytes, kChainBlocks, 0},
+      [&](int k, long long* add) {
+        add[0] = sources[k].cells_on_device ? 0 : Align256(
+            static_cast<size_t>(sources[k].limits.num_x_cells) * sources[k].limits.num_y_cells *
+            sizeof(uint16_t));
+        add[1] = ChainBlocksOf(*matchers[k]);
+      },
+      [](int, int, const long long*) {});
 
   double stage_us = 0., issue_us = 0., wait_us = 0.;
   int launches = 0;
-  for (const StackChain& chain : chains) {
+  for (const LaunchSet& chain : chains) {
     lap = Clock::now();
     const int n = chain.end - chain.begin;
     // The upload block: problems, the prefix tables of the launches, the host grids.
     //   tables: level 0 | levels 1 .. depth-1 | quads (n * child_levels entries) | planes
     const size_t table_ints = static_cast<size_t>(depth) * (n + 1) +
                               (static_cast<size_t>(n) * child_levels + 1) + (n + 1);
-    const size_t tables_at = Align256(sizeof(StackProblem) * n);
-    const size_t cells_at = Align256(tables_at + table_ints * sizeof(int));
-    const size_t bytes = cells_at + chain.staged_cells;
-    char* h_block = static_cast<char*>(ws->pinned[0].Reserve(bytes));
-    char* d_block = static_cast<char*>(ws->dev[0].Reserve(bytes));
-    StackProblem* h_problems = reinterpret_cast<StackProblem*>(h_block);
-    int* h_tables = reinterpret_cast<int*>(h_block + tables_at);
-    const StackProblem* d_problems = reinterpret_cast<const StackProblem*>(d_block);
-    const int* d_tables = reinterpret_cast<const int*>(d_block + tables_at);
-    int* first_level = h_tables;                                   // [depth][n + 1]
+    BlockLayout block;
+    const auto problems_in = block.Add<StackProblem>(n);
+    const auto tables_in = block.Add<int>(table_ints);
+    const auto cells_in = block.Add<char>(chain.total[0]);
+    char* h_block = static_cast<char*>(ws->pinned[0].Reserve(block.bytes));
+    char* d_block = static_cast<char*>(ws->dev[0].Reserve(block.bytes));
+    StackProblem* h_problems = problems_in(h_block);
+    const StackProblem* d_problems = problems_in(d_block);
+    int* first_level = tables_in(h_block);                         // [depth][n + 1]
     int* first_quads = first_level + static_cast<size_t>(depth) * (n + 1);
     int* first_planes = first_quads + static_cast<size_t>(n) * child_levels + 1;
     std::vector<size_t> staged_at(n, 0);
     long long planes_blocks = 0, quads_blocks = 0;
     std::vector<long long> level_blocks(depth, 0);
-    size_t cursor = cells_at;
+    size_t cursor = cells_in.at;
     for (int j = 0; j < n; ++j) {
       const Fast2DMatcher& m = *matchers[chain.begin + j];
       const Fast2DSource& src = sources[chain.begin + j];
@@ -644,10 +614,10 @@ std::vector<std::unique_ptr<Fast2DMatcher>> Fast2DMatcher::BuildBatch(
         P.level[i] = StackLevel{const_cast<uint8_t*>(L.cells), const_cast<uint32_t*>(L.quads),
                                 L.wx, L.wy, L.qx, L.qy, L.qtx};
         first_level[static_cast<size_t>(i) * (n + 1) + j] = static_cast<int>(level_blocks[i]);
-        level_blocks[i] += BlocksOf(static_cast<long long>(L.wx) * L.wy);
+        level_blocks[i] += BlocksOf(static_cast<long long>(L.wx) * L.wy, kStackTile);
         if (i < child_levels) {
           first_quads[static_cast<size_t>(j) * child_levels + i] = static_cast<int>(quads_blocks);
-          quads_blocks += BlocksOf(QuadSlots(L.qy, L.qtx));
+          quads_blocks += BlocksOf(QuadSlots(L.qy, L.qtx), kStackTile);
         }
       }
       P.planes = m.planes_;
@@ -660,7 +630,8 @@ std::vector<std::unique_ptr<Fast2DMatcher>> Fast2DMatcher::BuildBatch(
       P.max_cc = m.limits_.max_correspondence_cost;
       first_planes[j] = static_cast<int>(planes_blocks);
       if (m.planes_)
-        planes_blocks += BlocksOf(static_cast<long long>(P.w * P.w + 1) * P.plane_stride);
+        planes_blocks +=
+            BlocksOf(static_cast<long long>(P.w * P.w + 1) * P.plane_stride, kStackTile);
       h_problems[j] = P;
     }
     for (int i = 0; i < depth; ++i)
@@ -679,9 +650,9 @@ std::vector<std::unique_ptr<Fast2DMatcher>> Fast2DMatcher::BuildBatch(
     lap = Clock::now();
 
     hipStream_t stream = ws->stream;
-    SmallCopyAsync(d_block, h_block, bytes, /*to_device=*/true, stream);
+    SmallCopyAsync(d_block, h_block, block.bytes, /*to_device=*/true, stream);
     ++launches;
-    const int* d_first_level = d_tables;
+    const int* d_first_level = tables_in(d_block);
     const int* d_first_quads = d_first_level + static_cast<size_t>(depth) * (n + 1);
     const int* d_first_planes = d_first_quads + static_cast<size_t>(n) * child_levels + 1;
     BatchLevel0Kernel<<<static_cast<unsigned>(level_blocks[0]), kStackThreads, 0, stream>>>(

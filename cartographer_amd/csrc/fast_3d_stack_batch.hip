@@ -8,6 +8,7 @@
 #include <algorithm>
 #include <chrono>
 
+#include "cmx_batch.h"
 #include "fast_3d_stack_device.h"
 
 namespace cmx {
@@ -43,15 +44,7 @@ struct StackProblem3D {
 // that owns this workgroup (entries without blocks own none), searched by one thread.
 __device__ __forceinline__ int EntryOfWorkgroup(const int* __restrict__ first, int num) {
   __shared__ int entry;
-  if (threadIdx.x == 0) {
-    const int block = blockIdx.x;
-    int lo = 0, hi = num;           // first[lo] <= block < first[hi]
-    while (hi - lo > 1) {
-      const int mid = (lo + hi) >> 1;
-      if (first[mid] <= block) lo = mid; else hi = mid;
-    }
-    entry = lo;
-  }
+  if (threadIdx.x == 0) entry = EntryOfBlock(first, num, blockIdx.x);
   __syncthreads();
   return entry;
 }
@@ -222,8 +215,6 @@ constexpr size_t kChainStagingBytes = size_t(32) << 20;
 constexpr long long kChainBlocks = 1ll << 30;
 constexpr int kChainMatchers = 8192;
 
-size_t Align256(size_t v) { return (v + 255) & ~size_t(255); }
-long long BlocksOf(long long items, int tile) { return (items + tile - 1) / tile; }
 long long CellsOf(const Brick& b) { return static_cast<long long>(b.nx) * b.ny * b.nz; }
 
 // The geometry of one matcher -- pure integer work from the two boxes, the rule of
@@ -261,20 +252,16 @@ Plan3D PlanOf(const cmx_fast3d_options& options, const int lo[2][3], const int h
   for (int i = 0; build_octs && i + 1 < depth; ++i)
     plan.has_oct[i] = OctOfLevel3D(plan.level[i], i, options.full_resolution_depth, &plan.oct[i],
                                    &plan.oct_bytes[i]);
-  size_t at = 0;
-  auto region = [&at](size_t bytes) {
-    const size_t begin = at;
-    at += Align256(bytes);
-    return begin;
-  };
+  BlockLayout slab;
+  auto region = [&slab](size_t bytes) { return slab.Add<char>(bytes).at; };
   plan.level_at[0] = region(plan.level_bytes[0] + 16);
   plan.high_at = region(plan.high_bytes + 16);
   plan.low_at = region(plan.low_bytes + 16);
-  plan.zero_bytes = at;
+  plan.zero_bytes = slab.bytes;
   for (int d = 1; d < depth; ++d) plan.level_at[d] = region(plan.level_bytes[d] + 16);
   for (int i = 0; i + 1 < depth; ++i)
     if (plan.has_oct[i]) plan.oct_at[i] = region(plan.oct_bytes[i]);
-  plan.total = at;
+  plan.total = slab.bytes;
   plan.blocks = BlocksOf(CellsOf(plan.high), kCellTile) + BlocksOf(CellsOf(plan.low), kCellTile) +
                 BlocksOf(static_cast<long long>(plan.zero_bytes), kZeroTile);
   for (int d = 1; d < depth; ++d) plan.blocks += BlocksOf(CellsOf(plan.level[d]), kCellTile);
@@ -341,14 +328,15 @@ void ResidentBoxes(Workspace& ws, const Fast3DSource* sources, const std::vector
   const int R = static_cast<int>(resident.size());
   const int entries = 2 * R;
   // The block: bricks | first[entries + 1] | boxes, one pinned mirror.
-  const size_t first_at = Align256(sizeof(Brick) * entries);
-  const size_t box_at = Align256(first_at + sizeof(int) * (entries + 1));
-  const size_t bytes = box_at + Align256(sizeof(int) * 6 * entries);
-  char* h_block = static_cast<char*>(ws.pinned[1].Reserve(bytes));
-  char* d_block = static_cast<char*>(ws.dev[1].Reserve(bytes));
-  Brick* h_bricks = reinterpret_cast<Brick*>(h_block);
-  int* h_first = reinterpret_cast<int*>(h_block + first_at);
-  int* h_box = reinterpret_cast<int*>(h_block + box_at);
+  BlockLayout block;
+  const auto bricks_in = block.Add<Brick>(entries);
+  const auto first_in = block.Add<int>(entries + 1);
+  const auto box_in = block.Add<int>(6 * entries);
+  char* h_block = static_cast<char*>(ws.pinned[1].Reserve(block.bytes));
+  char* d_block = static_cast<char*>(ws.dev[1].Reserve(block.bytes));
+  Brick* h_bricks = bricks_in(h_block);
+  int* h_first = first_in(h_block);
+  int* h_box = box_in(h_block);
   long long blocks = 0;
   for (int e = 0; e < entries; ++e) {
     const Brick& b = sources[resident[e >> 1]].grid[e & 1];
@@ -363,12 +351,11 @@ void ResidentBoxes(Workspace& ws, const Fast3DSource* sources, const std::vector
   }
   h_first[entries] = static_cast<int>(blocks);
   if (blocks > 0) {
-    SmallCopyAsync(d_block, h_block, bytes, /*to_device=*/true, ws.stream);
+    SmallCopyAsync(d_block, h_block, block.bytes, /*to_device=*/true, ws.stream);
     BatchBounds3DKernel<<<static_cast<unsigned>(blocks), kBatchThreads, 0, ws.stream>>>(
-        reinterpret_cast<const Brick*>(d_block), reinterpret_cast<const int*>(d_block + first_at),
-        entries, reinterpret_cast<int*>(d_block + box_at));
+        bricks_in(d_block), first_in(d_block), entries, box_in(d_block));
     CMX_HIP(hipGetLastError());
-    SmallCopyAsync(h_box, d_block + box_at, sizeof(int) * 6 * entries, /*to_device=*/false,
+    SmallCopyAsync(h_box, box_in(d_block), sizeof(int) * 6 * entries, /*to_device=*/false,
                    ws.stream);
     CMX_HIP(hipStreamSynchronize(ws.stream));
     *launches += 3;
@@ -376,11 +363,6 @@ void ResidentBoxes(Workspace& ws, const Fast3DSource* sources, const std::vector
   for (int r = 0; r < R; ++r)
     std::copy(h_box + 12 * r, h_box + 12 * r + 12, box->begin() + 12 * resident[r]);
 }
-
-struct StackChain3D {
-  int begin = 0, end = 0;
-  size_t staged = 0;               // bytes of voxel lists, every list from a 256-byte boundary
-};
 
 size_t StagedBytesOf(const Fast3DSource& s) {
   if (s.resident) return 0;
@@ -445,26 +427,17 @@ std::vector<std::unique_ptr<cmx_fast3d>> BuildFast3DBatch(const cmx_fast3d_optio
   const double alloc_us = since(lap);
 
   const int most = Debug().fast3d_create_chain > 0 ? Debug().fast3d_create_chain : kChainMatchers;
-  std::vector<StackChain3D> chains;
-  for (int k = 0; k < num;) {
-    StackChain3D chain;
-    chain.begin = k;
-    long long blocks = 0;
-    for (; k < num && k - chain.begin < most; ++k) {
-      const size_t staged = StagedBytesOf(sources[k]);
-      // (a submap that exceeds a bound alone still goes out: as a chain of its own)
-      if (k > chain.begin && (chain.staged + staged > kChainStagingBytes ||
-                              blocks + plans[k].blocks > kChainBlocks))
-        break;
-      chain.staged += staged;
-      blocks += plans[k].blocks;
-    }
-    chain.end = k;
-    chains.push_back(chain);
-  }
+  // The chains; total[0]: bytes of voxel lists staged, every list from a 256-byte boundary.
+  const std::vector<LaunchSet> chains = CutSets(
+      std::vector<int>(num, 0), most, {kChainStagingBytes, kChainBlocks, 0},
+      [&](int k, long long* add) {
+        add[0] = StagedBytesOf(sources[k]);
+        add[1] = plans[k].blocks;
+      },
+      [](int, int, const long long*) {});
 
   double stage_us = 0., issue_us = 0., wait_us = 0.;
-  for (const StackChain3D& chain : chains) {
+  for (const LaunchSet& chain : chains) {
     lap = Clock::now();
     const int n = chain.end - chain.begin;
     std::vector<int> crop_members, voxel_members;
@@ -478,14 +451,14 @@ std::vector<std::unique_ptr<cmx_fast3d>> BuildFast3DBatch(const cmx_fast3d_optio
     const size_t oct_entries = static_cast<size_t>(n) * child_levels;
     const size_t table_ints = static_cast<size_t>(R + V) + (2 * R + 1) + (V + 1) + (2 * V + 1) +
                               static_cast<size_t>(child_levels) * (n + 1) + (oct_entries + 1);
-    const size_t tables_at = Align256(sizeof(StackProblem3D) * n);
-    const size_t lists_at = Align256(tables_at + table_ints * sizeof(int));
-    const size_t bytes = lists_at + chain.staged;
-    char* h_block = static_cast<char*>(ws->pinned[0].Reserve(bytes));
-    char* d_block = static_cast<char*>(ws->dev[0].Reserve(bytes));
-    StackProblem3D* h_problems = reinterpret_cast<StackProblem3D*>(h_block);
-    int* h_tables = reinterpret_cast<int*>(h_block + tables_at);
-    int* crop_of = h_tables;
+    BlockLayout block;
+    const auto problems_in = block.Add<StackProblem3D>(n);
+    const auto tables_in = block.Add<int>(table_ints);
+    const auto lists_in = block.Add<char>(chain.total[0]);
+      char* h_block = static_cast<char*>(ws->pinned[0].Reserve(block.bytes));
+    char* d_block = static_cast<char*>(ws->dev[0].Reserve(block.bytes));
+    StackProblem3D* h_problems = problems_in(h_block);
+    int* crop_of = tables_in(h_block);
     int* voxel_of = crop_of + R;
     int* first_crop = voxel_of + V;
     int* first_zero = first_crop + 2 * R + 1;
@@ -499,7 +472,7 @@ std::vector<std::unique_ptr<cmx_fast3d>> BuildFast3DBatch(const cmx_fast3d_optio
     std::copy(voxel_members.begin(), voxel_members.end(), voxel_of);
 
     std::vector<size_t> staged_at(static_cast<size_t>(n) * 2, 0);
-    size_t cursor = lists_at;
+    size_t cursor = lists_in.at;
     long long crop_blocks = 0, zero_blocks = 0, scatter_blocks = 0, oct_blocks = 0;
     std::vector<long long> level_blocks(depth, 0);
     int r = 0, v = 0;
@@ -567,8 +540,8 @@ std::vector<std::unique_ptr<cmx_fast3d>> BuildFast3DBatch(const cmx_fast3d_optio
     stage_us += since(lap);
     lap = Clock::now();
 
-    const StackProblem3D* d_problems = reinterpret_cast<const StackProblem3D*>(d_block);
-    SmallCopyAsync(d_block, h_block, bytes, /*to_device=*/true, stream);
+    const StackProblem3D* d_problems = problems_in(d_block);
+    SmallCopyAsync(d_block, h_block, block.bytes, /*to_device=*/true, stream);
     ++launches;
     if (crop_blocks > 0) {
       BatchCrop3DKernel<<<static_cast<unsigned>(crop_blocks), kBatchThreads, 0, stream>>>(

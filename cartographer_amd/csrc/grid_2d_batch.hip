@@ -30,11 +30,11 @@
 #include <cstring>
 #include <map>
 #include <mutex>
-#include <unordered_map>
 #include <utility>
 #include <vector>
 
 #include "../../include/cartographer_mi355x_debug.h"
+#include "cmx_batch.h"
 #include "grid_2d_internal.h"
 
 namespace cmx {
@@ -63,7 +63,6 @@ struct PlanInput {
 };
 
 struct PlannedInsertion {
-  int round = 0;
   PlanLimits at{};            // the grid's limits at this insertion, after its own growth
   int start_x = 0, start_y = 0;  // where cell (0, 0) of the grid before the call lies in `at`
   int box_x = 0, box_y = 0, box_w = 0, box_h = 0;  // cells the insertion can mark, in `at`
@@ -104,7 +103,7 @@ long PlanCell(double max, float p, double resolution) {
          kSubpixelScale;
 }
 
-// Rounds, limits and boxes of a call.  `grids` in: the limits before the call.
+// Limits and boxes of a call.  `grids` in: the limits before the call.
 void PlanInsertions(std::vector<PlannedGrid>* grids, const PlanInput* in, int num,
                     std::vector<PlannedInsertion>* out) {
   out->assign(num, PlannedInsertion{});
@@ -129,7 +128,7 @@ void PlanInsertions(std::vector<PlannedGrid>* grids, const PlanInput* in, int nu
     PlanGrow(&G, b.lo_x - kPadding * 1.f, b.lo_y - kPadding * 1.f, k);
     PlanGrow(&G, b.hi_x + kPadding * 1.f, b.hi_y + kPadding * 1.f, k);
     PlannedInsertion& P = (*out)[k];
-    P.round = G.insertions++;
+    ++G.insertions;
     P.at = G.limits;
     P.start_x = G.start_x;
     P.start_y = G.start_y;
@@ -147,7 +146,7 @@ void PlanInsertions(std::vector<PlannedGrid>* grids, const PlanInput* in, int nu
 }
 
 // ---- device ----------------------------------------------------------------------------
-struct InsertionDesc {
+struct Grid2DInsertionDesc {
   GridView view;              // limits at this insertion; cells: its cell (0, 0) in the final storage
   int stride;                 // row stride of the final storage
   float origin_x, origin_y;
@@ -159,21 +158,8 @@ struct InsertionDesc {
   int box_x, box_y, box_w, box_h;
 };
 
-// The insertion block `block` of a launch works for: the last one whose first block is not
-// beyond it (an insertion without blocks shares its first block with its successor).
-template <int InsertionDesc::*First>
-__device__ __forceinline__ int DescOfBlock(const InsertionDesc* __restrict__ descs, int num,
-                                           int block) {
-  int lo = 0, hi = num;       // descs[lo].*First <= block < descs[hi].*First
-  while (hi - lo > 1) {
-    const int mid = (lo + hi) >> 1;
-    if (descs[mid].*First <= block) lo = mid; else hi = mid;
-  }
-  return lo;
-}
-
 // Apply of grid_2d.hip on a view that is a window of a larger storage.
-__device__ __forceinline__ void ApplyAt(const InsertionDesc& D, int cx, int cy,
+__device__ __forceinline__ void ApplyAt(const Grid2DInsertionDesc& D, int cx, int cy,
                                         const uint16_t* __restrict__ table, int* error) {
   if (static_cast<unsigned>(cx) >= static_cast<unsigned>(D.view.nx) ||
       static_cast<unsigned>(cy) >= static_cast<unsigned>(D.view.ny)) {
@@ -187,9 +173,9 @@ __device__ __forceinline__ void ApplyAt(const InsertionDesc& D, int cx, int cy,
 }
 
 __global__ void __launch_bounds__(kHitPoints)
-BatchHitKernel(const InsertionDesc* __restrict__ descs, int num,
+BatchHitKernel(const Grid2DInsertionDesc* __restrict__ descs, int num,
                const uint16_t* __restrict__ hit_table, int* __restrict__ error) {
-  const InsertionDesc& D = descs[DescOfBlock<&InsertionDesc::first_hit>(descs, num, blockIdx.x)];
+  const auto& D = descs[DescOfBlock<&Grid2DInsertionDesc::first_hit>(descs, num, blockIdx.x)];
   const int i = (blockIdx.x - D.first_hit) * kHitPoints + threadIdx.x;
   if (i >= D.num_points) return;
   const float* p = i < D.num_returns ? D.returns + 3 * static_cast<size_t>(i)
@@ -200,9 +186,9 @@ BatchHitKernel(const InsertionDesc* __restrict__ descs, int num,
 }
 
 __global__ void __launch_bounds__(64 * kRaysPerBlock)
-BatchMissKernel(const InsertionDesc* __restrict__ descs, int num,
+BatchMissKernel(const Grid2DInsertionDesc* __restrict__ descs, int num,
                 const uint16_t* __restrict__ miss_table, int* __restrict__ error) {
-  const InsertionDesc& D = descs[DescOfBlock<&InsertionDesc::first_ray>(descs, num, blockIdx.x)];
+  const auto& D = descs[DescOfBlock<&Grid2DInsertionDesc::first_ray>(descs, num, blockIdx.x)];
   const int lane = threadIdx.x & 63;
   const int ray = (blockIdx.x - D.first_ray) * kRaysPerBlock + (threadIdx.x >> 6);
   if (ray >= D.num_points) return;
@@ -212,8 +198,8 @@ BatchMissKernel(const InsertionDesc* __restrict__ descs, int num,
 
 // Grid2D::FinishUpdate over the insertion's box.
 __global__ void __launch_bounds__(256)
-BatchFinishKernel(const InsertionDesc* __restrict__ descs, int num) {
-  const InsertionDesc& D = descs[DescOfBlock<&InsertionDesc::first_clear>(descs, num, blockIdx.x)];
+BatchFinishKernel(const Grid2DInsertionDesc* __restrict__ descs, int num) {
+  const auto& D = descs[DescOfBlock<&Grid2DInsertionDesc::first_clear>(descs, num, blockIdx.x)];
   const int count = D.box_w * D.box_h;
   const int base = (blockIdx.x - D.first_clear) * kClearCells;
   const int end = min(base + kClearCells, count);
@@ -281,13 +267,6 @@ struct GrownCells {
   }
 };
 
-size_t Align256(size_t bytes) { return (bytes + 255) & ~static_cast<size_t>(255); }
-
-struct LaunchSet {
-  int begin = 0, end = 0;         // descriptors [begin, end)
-  long long hit_blocks = 0, ray_blocks = 0, clear_blocks = 0;
-};
-
 void InsertBatch(const cmx_grid2d_insertion* insertions, int num, float hit_probability,
                  float miss_probability, bool insert_free_space) {
   // Every argument check before the device is touched.
@@ -296,12 +275,11 @@ void InsertBatch(const cmx_grid2d_insertion* insertions, int num, float hit_prob
   CMX_REQUIRE(hit_probability > 0.f && hit_probability < 1.f && miss_probability > 0.f &&
                   miss_probability < 1.f,
               "probability must be in (0, 1)");
-  std::vector<cmx_grid2d*> grids;
-  std::unordered_map<const cmx_grid2d*, int> grid_index;
-  std::unordered_map<const float*, std::pair<int, size_t>> scans;   // pointer -> count, float offset
-  std::vector<const float*> scan_order;
+  TargetRounds<cmx_grid2d*> order;
+  const std::vector<cmx_grid2d*>& grids = order.targets;
+  StagedArrays scans(3);
   std::vector<PlanInput> inputs(num);
-  size_t staged_floats = 0, total_points = 0;
+  size_t total_points = 0;
   for (int k = 0; k < num; ++k) {           // (no grid is looked into before all are known to be there)
     const cmx_grid2d_insertion& I = insertions[k];
     CMX_REQUIRE(I.grid && I.origin_xy, "insertion %d: null argument", k);
@@ -315,30 +293,18 @@ void InsertBatch(const cmx_grid2d_insertion* insertions, int num, float hit_prob
     const cmx_grid2d_insertion& I = insertions[k];
     CMX_REQUIRE(I.grid->device == insertions[0].grid->device,
                 "insertion %d: all grids of a batch must live on one device", k);
-    const auto stage = [&](const float* p, int count) {
-      if (count == 0) return;
-      auto it = scans.find(p);
-      if (it == scans.end()) {
-        scans.emplace(p, std::make_pair(count, staged_floats));
-        scan_order.push_back(p);
-        staged_floats += 3 * static_cast<size_t>(count);
-      } else {
-        CMX_REQUIRE(it->second.first == count,
-                    "insertion %d: points given by the pointer of an earlier scan of the call, "
-                    "%d of them there and %d here",
-                    k, it->second.first, count);
-      }
+    const auto mismatch = [](int item, int there, int here) {
+      CMX_REQUIRE(false,
+                  "insertion %d: points given by the pointer of an earlier scan of the call, "
+                  "%d of them there and %d here",
+                  item, there, here);
     };
-    stage(I.returns_xyz, I.num_returns);
-    stage(I.misses_xyz, I.num_misses);
+    scans.Add(k, I.returns_xyz, I.num_returns, mismatch);
+    scans.Add(k, I.misses_xyz, I.num_misses, mismatch);
     total_points += static_cast<size_t>(I.num_returns) + I.num_misses;
-    auto found = grid_index.find(I.grid);
-    if (found == grid_index.end()) {
-      found = grid_index.emplace(I.grid, static_cast<int>(grids.size())).first;
-      grids.push_back(I.grid);
-    }
-    inputs[k] = PlanInput{found->second, I.origin_xy, I.returns_xyz, I.num_returns, I.misses_xyz,
-                          I.num_misses};
+    order.Add(I.grid);
+    inputs[k] = PlanInput{order.target_of[k], I.origin_xy, I.returns_xyz, I.num_returns,
+                          I.misses_xyz, I.num_misses};
   }
   const int num_grids = static_cast<int>(grids.size());
   std::vector<PlannedGrid> planned_grids(num_grids);
@@ -366,39 +332,28 @@ void InsertBatch(const cmx_grid2d_insertion* insertions, int num, float hit_prob
     growing.push_back(g);
   }
 
-  // The sets of launches: round by round, a round in list order, cut where a set is full.
-  int rounds = 0;
-  for (const PlannedInsertion& P : plan) rounds = std::max(rounds, P.round + 1);
-  std::vector<std::vector<int>> by_round(rounds);
-  for (int k = 0; k < num; ++k) by_round[plan[k].round].push_back(k);
-  const int most = Debug().grid2d_insert_chain > 0 ? Debug().grid2d_insert_chain : kChainInsertions;
-
   // One upload block: descriptors (set after set) | grow descriptors | points.
-  const size_t grow_at = Align256(sizeof(InsertionDesc) * num);
-  const size_t points_at = Align256(grow_at + sizeof(GrowDesc) * growing.size());
-  const size_t bytes = Align256(points_at + staged_floats * sizeof(float));
-  char* h_block = static_cast<char*>(ws->pinned[0].Reserve(bytes));
-  char* d_block = static_cast<char*>(ws->dev[0].Reserve(bytes));
+  BlockLayout block;
+  const auto descs_in = block.Add<Grid2DInsertionDesc>(num);
+  const auto grow_in = block.Add<GrowDesc>(growing.size());
+  const auto points_in = block.Add<float>(scans.floats());
+  char* h_block = static_cast<char*>(ws->pinned[0].Reserve(block.bytes));
+  char* d_block = static_cast<char*>(ws->dev[0].Reserve(block.bytes));
   int2* d_ends = ws->dev[1].ReserveAs<int2>(std::max<size_t>(total_points, 1));
   // (the kernels raise the flag in pinned memory themselves: nothing to copy back)
   int* h_error = ws->pinned[1].ReserveAs<int>(4);
   *h_error = 0;
-  InsertionDesc* h_descs = reinterpret_cast<InsertionDesc*>(h_block);
-  const InsertionDesc* d_descs = reinterpret_cast<const InsertionDesc*>(d_block);
-  GrowDesc* h_grow = reinterpret_cast<GrowDesc*>(h_block + grow_at);
-  float* h_points = reinterpret_cast<float*>(h_block + points_at);
-  const float* d_points = reinterpret_cast<const float*>(d_block + points_at);
+  const float* d_points = points_in(d_block);
 
   size_t largest_growing = 0;
   for (size_t j = 0; j < growing.size(); ++j) {
     const int g = growing[j];
     const PlannedGrid& G = planned_grids[g];
-    h_grow[j] = GrowDesc{grids[g]->cells, grown.cells[g], grids[g]->nx, grids[g]->ny,
+    grow_in(h_block)[j] = GrowDesc{grids[g]->cells, grown.cells[g], grids[g]->nx, grids[g]->ny,
                          G.limits.nx, G.limits.ny, G.start_x, G.start_y};
     largest_growing = std::max(largest_growing, static_cast<size_t>(G.limits.nx) * G.limits.ny);
   }
 
-  std::vector<LaunchSet> sets;
   std::vector<size_t> ends_at(num);
   {
     size_t cursor = 0;
@@ -407,65 +362,52 @@ void InsertBatch(const cmx_grid2d_insertion* insertions, int num, float hit_prob
       cursor += static_cast<size_t>(inputs[k].num_returns) + inputs[k].num_misses;
     }
   }
-  int next_desc = 0;
-  for (const std::vector<int>& round : by_round) {
-    for (size_t j = 0; j < round.size();) {
-      LaunchSet set;
-      set.begin = next_desc;
-      for (; j < round.size() && next_desc - set.begin < most; ++j) {
-        const int k = round[j];
+  // The sets of launches (hits, rays, marker clearing), a descriptor where its set wants it.
+  const int most = Debug().grid2d_insert_chain > 0 ? Debug().grid2d_insert_chain : kChainInsertions;
+  const std::vector<LaunchSet> sets = CutSets(
+      order.round_of, most, {kSetBlocks, kSetBlocks, kSetBlocks},
+      [&](int k, long long* blocks) {
+        const long long points = static_cast<long long>(inputs[k].num_returns) + inputs[k].num_misses;
+        blocks[0] = BlocksOf(points, kHitPoints);
+        blocks[1] = insert_free_space ? BlocksOf(points, kRaysPerBlock) : 0;
+        blocks[2] = points ? BlocksOf(static_cast<long long>(plan[k].box_w) * plan[k].box_h,
+                                      kClearCells) : 0;
+      },
+      [&](int k, int slot, const long long* first) {
         const PlanInput& I = inputs[k];
         const PlannedInsertion& P = plan[k];
         const PlannedGrid& G = planned_grids[I.grid];
-        const long long points = static_cast<long long>(I.num_returns) + I.num_misses;
-        const long long hit = (points + kHitPoints - 1) / kHitPoints;
-        const long long ray = insert_free_space ? (points + kRaysPerBlock - 1) / kRaysPerBlock : 0;
-        const long long clear =
-            points ? (static_cast<long long>(P.box_w) * P.box_h + kClearCells - 1) / kClearCells : 0;
-        // (an insertion that exceeds the bound alone still goes out: as a set of its own)
-        if (next_desc > set.begin &&
-            (set.hit_blocks + hit > kSetBlocks || set.ray_blocks + ray > kSetBlocks ||
-             set.clear_blocks + clear > kSetBlocks))
-          break;
         uint16_t* storage = grown.cells[I.grid] ? grown.cells[I.grid] : grids[I.grid]->cells;
         // Whole cells between this view and the final storage.
         const int off_x = G.start_x - P.start_x, off_y = G.start_y - P.start_y;
-        InsertionDesc D{};
+        Grid2DInsertionDesc D{};
         D.view = GridView{storage + static_cast<size_t>(G.limits.nx) * off_y + off_x, P.at.nx,
                           P.at.ny, P.at.resolution / kSubpixelScale, P.at.max_x, P.at.max_y};
         D.stride = G.limits.nx;
         D.origin_x = I.origin[0];
         D.origin_y = I.origin[1];
-        D.returns = I.num_returns ? d_points + scans[I.returns].second : nullptr;
-        D.misses = I.num_misses ? d_points + scans[I.misses].second : nullptr;
+        D.returns = I.num_returns ? d_points + scans.OffsetOf(I.returns) : nullptr;
+        D.misses = I.num_misses ? d_points + scans.OffsetOf(I.misses) : nullptr;
         D.ends = d_ends + ends_at[k];
         D.num_returns = I.num_returns;
-        D.num_points = static_cast<int>(points);
-        D.first_hit = static_cast<int>(set.hit_blocks);
-        D.first_ray = static_cast<int>(set.ray_blocks);
-        D.first_clear = static_cast<int>(set.clear_blocks);
+        D.num_points = I.num_returns + I.num_misses;
+        D.first_hit = static_cast<int>(first[0]);
+        D.first_ray = static_cast<int>(first[1]);
+        D.first_clear = static_cast<int>(first[2]);
         D.box_x = P.box_x;
         D.box_y = P.box_y;
         D.box_w = P.box_w;
         D.box_h = P.box_h;
-        h_descs[next_desc++] = D;
-        set.hit_blocks += hit;
-        set.ray_blocks += ray;
-        set.clear_blocks += clear;
-      }
-      set.end = next_desc;
-      sets.push_back(set);
-    }
-  }
+        descs_in(h_block)[slot] = D;
+      });
   // Every distinct scan once (the pool's threads: a copy is memory bound).
-  ParallelFor(static_cast<int>(scan_order.size()), 8, [&](int s) {
-    const std::pair<int, size_t>& at = scans.find(scan_order[s])->second;
-    std::memcpy(h_points + at.second, scan_order[s], 3 * sizeof(float) * at.first);
+  scans.CopyTo(points_in(h_block), [](int n, const std::function<void(int)>& copy) {
+    ParallelFor(n, 8, copy);
   });
 
   // From here on cells may change: whatever happens, the cached images of the grids are stale.
   struct Touched {
-    std::vector<cmx_grid2d*>& grids;
+    const std::vector<cmx_grid2d*>& grids;
     hipStream_t stream;
     bool committed = false;
     ~Touched() {
@@ -475,11 +417,11 @@ void InsertBatch(const cmx_grid2d_insertion* insertions, int num, float hit_prob
     }
   } touched{grids, stream};
 
-  SmallCopyAsync(d_block, h_block, bytes, /*to_device=*/true, stream);
+  SmallCopyAsync(d_block, h_block, block.bytes, /*to_device=*/true, stream);
   if (!growing.empty()) {
-    const GrowDesc* d_grow = reinterpret_cast<const GrowDesc*>(d_block + grow_at);
+    const GrowDesc* d_grow = grow_in(d_block);
     const unsigned columns =
-        static_cast<unsigned>(std::min<size_t>((largest_growing + 255) / 256, 4096));
+        static_cast<unsigned>(std::min<long long>(BlocksOf(largest_growing, 256), 4096));
     for (size_t first = 0; first < growing.size(); first += 65535) {
       const unsigned rows = static_cast<unsigned>(std::min<size_t>(growing.size() - first, 65535));
       BatchGrowKernel<<<dim3(columns, rows), 256, 0, stream>>>(d_grow + first);
@@ -487,15 +429,15 @@ void InsertBatch(const cmx_grid2d_insertion* insertions, int num, float hit_prob
   }
   for (const LaunchSet& set : sets) {
     const int n = set.end - set.begin;
-    const InsertionDesc* descs = d_descs + set.begin;
-    if (set.hit_blocks > 0)
-      BatchHitKernel<<<static_cast<unsigned>(set.hit_blocks), kHitPoints, 0, stream>>>(
+    const Grid2DInsertionDesc* descs = descs_in(d_block) + set.begin;
+    if (set.total[0] > 0)
+      BatchHitKernel<<<static_cast<unsigned>(set.total[0]), kHitPoints, 0, stream>>>(
           descs, n, hit_table, h_error);
-    if (set.ray_blocks > 0)
-      BatchMissKernel<<<static_cast<unsigned>(set.ray_blocks), 64 * kRaysPerBlock, 0, stream>>>(
+    if (set.total[1] > 0)
+      BatchMissKernel<<<static_cast<unsigned>(set.total[1]), 64 * kRaysPerBlock, 0, stream>>>(
           descs, n, miss_table, h_error);
-    if (set.clear_blocks > 0)
-      BatchFinishKernel<<<static_cast<unsigned>(set.clear_blocks), 256, 0, stream>>>(descs, n);
+    if (set.total[2] > 0)
+      BatchFinishKernel<<<static_cast<unsigned>(set.total[2]), 256, 0, stream>>>(descs, n);
   }
   CMX_HIP(hipGetLastError());
   CMX_HIP(hipStreamSynchronize(stream));
@@ -561,7 +503,9 @@ extern "C" cmx_status cmx_debug_grid2d_insert_plan(const cmx_grid2d_limits* limi
     }
     std::vector<PlannedInsertion> plan;
     PlanInsertions(&grids, inputs.data(), num_insertions, &plan);
-    for (int k = 0; k < num_insertions; ++k) rounds[k] = plan[k].round;
+    TargetRounds<int> order;
+    for (int k = 0; k < num_insertions; ++k) order.Add(inputs[k].grid);
+    std::copy(order.round_of.begin(), order.round_of.end(), rounds);
     for (int g = 0; g < num_grids; ++g) {
       final_limits[g] = limits[g];
       final_limits[g].max_x = grids[g].limits.max_x;

@@ -27,11 +27,10 @@
 // and stores `cell & 0x7fff` where bit 15 is set.  Threads that meet on a voxel store one value.
 #include <algorithm>
 #include <cstring>
-#include <unordered_map>
-#include <utility>
 #include <vector>
 
 #include "../../include/cartographer_mi355x_debug.h"
+#include "cmx_batch.h"
 #include "grid_3d_internal.h"
 
 namespace cmx {
@@ -51,16 +50,14 @@ struct PlanInput {
 struct PlannedGrid {
   BrickBounds brick;          // in: before the call; out: after it
   int grid_size = 128;
-  int insertions = 0;
   bool grows = false;
 };
 
-// Rounds, and what InsertRangeData's growth steps (grid_3d.hip) make of every grid when the
-// insertions run in list order.  `grids` in: the state before the call.
-void PlanInsertions(std::vector<PlannedGrid>* grids, const PlanInput* in, int num, int* rounds) {
+// What InsertRangeData's growth steps (grid_3d.hip) make of every grid when the insertions run in
+// list order.  `grids` in: the state before the call.
+void PlanInsertions(std::vector<PlannedGrid>* grids, const PlanInput* in, int num) {
   for (int k = 0; k < num; ++k) {
     PlannedGrid& G = (*grids)[in[k].grid];
-    rounds[k] = G.insertions++;
     const int* lo = in[k].box;
     const int* hi = in[k].box + 3;
     if (lo[0] > hi[0]) continue;                         // no returns: nothing is written
@@ -79,7 +76,7 @@ void PlanInsertions(std::vector<PlannedGrid>* grids, const PlanInput* in, int nu
 }
 
 // ---- device ----------------------------------------------------------------------------
-struct InsertionDesc {
+struct Grid3DInsertionDesc {
   BrickView view;             // the grid's brick after the call's growth (set once it is planned)
   const float* returns;       // staged points
   float origin[3];
@@ -89,26 +86,13 @@ struct InsertionDesc {
   int first_hit, first_miss, first_clear;   // first block in each launch of its set
 };
 
-// The insertion block `block` of a launch works for: the last one whose first block is not
-// beyond it (an insertion without blocks shares its first block with its successor).
-template <int InsertionDesc::*First>
-__device__ __forceinline__ int DescOfBlock(const InsertionDesc* __restrict__ descs, int num,
-                                           int block) {
-  int lo = 0, hi = num;       // descs[lo].*First <= block < descs[hi].*First
-  while (hi - lo > 1) {
-    const int mid = (lo + hi) >> 1;
-    if (descs[mid].*First <= block) lo = mid; else hi = mid;
-  }
-  return lo;
-}
-
 // Grid3DExtentKernel of grid_3d.hip, segmented: out[8 * d] = {min x, y, z, max x, y, z, error,
 // pad} of descriptor d; error 2: a ray of 2^15 voxels or more.
 __global__ void __launch_bounds__(kBlock)
-BatchExtentKernel(const InsertionDesc* __restrict__ descs, int num, int num_free_space_voxels,
+BatchExtentKernel(const Grid3DInsertionDesc* __restrict__ descs, int num, int num_free_space_voxels,
                   int* __restrict__ out) {
-  const int d = DescOfBlock<&InsertionDesc::first_extent>(descs, num, blockIdx.x);
-  const InsertionDesc& D = descs[d];
+  const int d = DescOfBlock<&Grid3DInsertionDesc::first_extent>(descs, num, blockIdx.x);
+  const Grid3DInsertionDesc& D = descs[d];
   int* box = out + 8 * static_cast<size_t>(d);
   const long long i = static_cast<long long>(blockIdx.x - D.first_extent) * kBlock + threadIdx.x;
   int lo[3] = {kIntMax, kIntMax, kIntMax}, hi[3] = {kIntMin, kIntMin, kIntMin};
@@ -146,10 +130,10 @@ BatchExtentKernel(const InsertionDesc* __restrict__ descs, int num, int num_free
 
 // `errors`: one flag per descriptor of the set ("a voxel fell outside the brick").
 __global__ void __launch_bounds__(kBlock)
-BatchHitKernel(const InsertionDesc* __restrict__ descs, int num,
+BatchHitKernel(const Grid3DInsertionDesc* __restrict__ descs, int num,
                const uint16_t* __restrict__ hit_table, int* __restrict__ errors) {
-  const int d = DescOfBlock<&InsertionDesc::first_hit>(descs, num, blockIdx.x);
-  const InsertionDesc& D = descs[d];
+  const int d = DescOfBlock<&Grid3DInsertionDesc::first_hit>(descs, num, blockIdx.x);
+  const Grid3DInsertionDesc& D = descs[d];
   const long long i = static_cast<long long>(blockIdx.x - D.first_hit) * kBlock + threadIdx.x;
   if (i >= D.num_returns) return;
   Apply(D.view, CellOf(D.returns + 3 * static_cast<size_t>(i), D.resolution), hit_table,
@@ -158,10 +142,10 @@ BatchHitKernel(const InsertionDesc* __restrict__ descs, int num,
 
 // One thread per (return, k): sample position num_samples - num_free_space_voxels + k.
 __global__ void __launch_bounds__(kBlock)
-BatchMissKernel(const InsertionDesc* __restrict__ descs, int num, int num_free_space_voxels,
+BatchMissKernel(const Grid3DInsertionDesc* __restrict__ descs, int num, int num_free_space_voxels,
                 const uint16_t* __restrict__ miss_table, int* __restrict__ errors) {
-  const int d = DescOfBlock<&InsertionDesc::first_miss>(descs, num, blockIdx.x);
-  const InsertionDesc& D = descs[d];
+  const int d = DescOfBlock<&Grid3DInsertionDesc::first_miss>(descs, num, blockIdx.x);
+  const Grid3DInsertionDesc& D = descs[d];
   const long long t = static_cast<long long>(blockIdx.x - D.first_miss) * kBlock + threadIdx.x;
   if (t >= static_cast<long long>(D.num_returns) * num_free_space_voxels) return;
   const int i = static_cast<int>(t / num_free_space_voxels);
@@ -178,8 +162,8 @@ BatchMissKernel(const InsertionDesc* __restrict__ descs, int num, int num_free_s
 // HybridGrid::FinishUpdate (hybrid_grid.h:463-469) for the voxels the insertion visited: one
 // thread per (return, k), k = num_free_space_voxels being the hit itself.
 __global__ void __launch_bounds__(kBlock)
-BatchClearKernel(const InsertionDesc* __restrict__ descs, int num, int num_free_space_voxels) {
-  const InsertionDesc& D = descs[DescOfBlock<&InsertionDesc::first_clear>(descs, num, blockIdx.x)];
+BatchClearKernel(const Grid3DInsertionDesc* __restrict__ descs, int num, int num_free_space_voxels) {
+  const auto& D = descs[DescOfBlock<&Grid3DInsertionDesc::first_clear>(descs, num, blockIdx.x)];
   const long long per_return = static_cast<long long>(num_free_space_voxels) + 1;
   const long long t = static_cast<long long>(blockIdx.x - D.first_clear) * kBlock + threadIdx.x;
   if (t >= D.num_returns * per_return) return;
@@ -220,13 +204,6 @@ struct StagedBricks {
   }
 };
 
-size_t Align256(size_t bytes) { return (bytes + 255) & ~static_cast<size_t>(255); }
-
-struct LaunchSet {
-  int begin = 0, end = 0;         // descriptors [begin, end)
-  long long hit_blocks = 0, miss_blocks = 0, clear_blocks = 0;
-};
-
 void InsertBatch(const cmx_grid3d_insertion* insertions, int num, float hit_probability,
                  float miss_probability, int num_free_space_voxels) {
   // Every argument check before the device is touched.
@@ -246,88 +223,52 @@ void InsertBatch(const cmx_grid3d_insertion* insertions, int num, float hit_prob
     CMX_REQUIRE(static_cast<long long>(I.num_returns) * num_free_space_voxels < (1ll << 38),
                 "insertion %d: too many free-space samples", k);
   }
-  std::vector<cmx_grid3d*> grids;
-  std::unordered_map<const cmx_grid3d*, int> grid_index;
-  std::unordered_map<const float*, std::pair<int, size_t>> clouds;   // pointer -> count, float offset
-  std::vector<const float*> cloud_order;
-  std::vector<int> grid_of(num), round_of(num);
-  std::vector<int> per_grid;
-  size_t staged_floats = 0;
-  int rounds = 0;
+  TargetRounds<cmx_grid3d*> order;
+  const std::vector<cmx_grid3d*>& grids = order.targets;
+  const std::vector<int>& grid_of = order.target_of;
+  StagedArrays clouds(3);
   for (int k = 0; k < num; ++k) {
     const cmx_grid3d_insertion& I = insertions[k];
     CMX_REQUIRE(I.grid->device == insertions[0].grid->device,
                 "insertion %d: all grids of a batch must live on one device", k);
-    if (I.num_returns > 0) {
-      auto it = clouds.find(I.returns_xyz);
-      if (it == clouds.end()) {
-        clouds.emplace(I.returns_xyz, std::make_pair(I.num_returns, staged_floats));
-        cloud_order.push_back(I.returns_xyz);
-        staged_floats += 3 * static_cast<size_t>(I.num_returns);
-      } else {
-        CMX_REQUIRE(it->second.first == I.num_returns,
-                    "insertion %d: returns given by the pointer of an earlier cloud of the call, "
-                    "%d of them there and %d here",
-                    k, it->second.first, I.num_returns);
-      }
-    }
-    auto found = grid_index.find(I.grid);
-    if (found == grid_index.end()) {
-      found = grid_index.emplace(I.grid, static_cast<int>(grids.size())).first;
-      grids.push_back(I.grid);
-      per_grid.push_back(0);
-    }
-    grid_of[k] = found->second;
-    round_of[k] = per_grid[found->second]++;
-    rounds = std::max(rounds, round_of[k] + 1);
+    clouds.Add(k, I.returns_xyz, I.num_returns, [](int item, int there, int here) {
+      CMX_REQUIRE(false,
+                  "insertion %d: returns given by the pointer of an earlier cloud of the call, "
+                  "%d of them there and %d here",
+                  item, there, here);
+    });
+    order.Add(I.grid);
   }
   const int num_grids = static_cast<int>(grids.size());
 
-  // The sets of launches: round by round, a round in list order, cut where a set is full.  An
-  // insertion's descriptor stands where its set wants it; `slot_of` finds it from the list.
-  std::vector<std::vector<int>> by_round(rounds);
-  for (int k = 0; k < num; ++k) by_round[round_of[k]].push_back(k);
+  // The sets of launches (hits, miss samples, marker clearing).  An insertion's descriptor stands
+  // where its set wants it; `slot_of` finds it from the list.
   const int most = Debug().grid3d_insert_chain > 0 ? Debug().grid3d_insert_chain : kChainInsertions;
-  std::vector<InsertionDesc> descs(num);
+  std::vector<Grid3DInsertionDesc> descs(num);
   std::vector<int> slot_of(num);
-  std::vector<LaunchSet> sets;
   long long extent_blocks = 0;
-  int next = 0;
-  for (const std::vector<int>& round : by_round) {
-    for (size_t j = 0; j < round.size();) {
-      LaunchSet set;
-      set.begin = next;
-      for (; j < round.size() && next - set.begin < most; ++j) {
-        const int k = round[j];
+  const std::vector<LaunchSet> sets = CutSets(
+      order.round_of, most, {kSetBlocks, kSetBlocks, kSetBlocks},
+      [&](int k, long long* blocks) {
         const long long n = insertions[k].num_returns;
-        const long long hit = (n + kBlock - 1) / kBlock;
-        const long long miss = (n * num_free_space_voxels + kBlock - 1) / kBlock;
-        const long long clear = (n * per_return + kBlock - 1) / kBlock;
-        // (an insertion that exceeds the bound alone still goes out: as a set of its own)
-        if (next > set.begin && (set.hit_blocks + hit > kSetBlocks ||
-                                 set.miss_blocks + miss > kSetBlocks ||
-                                 set.clear_blocks + clear > kSetBlocks))
-          break;
-        InsertionDesc D{};
+        blocks[0] = BlocksOf(n, kBlock);
+        blocks[1] = BlocksOf(n * num_free_space_voxels, kBlock);
+        blocks[2] = BlocksOf(n * per_return, kBlock);
+      },
+      [&](int k, int slot, const long long* first) {
+        Grid3DInsertionDesc D{};
         for (int a = 0; a < 3; ++a) D.origin[a] = insertions[k].origin_xyz[a];
         D.resolution = grids[grid_of[k]]->resolution;
-        D.num_returns = static_cast<int>(n);
+        D.num_returns = insertions[k].num_returns;
         D.first_extent = static_cast<int>(extent_blocks);
-        D.first_hit = static_cast<int>(set.hit_blocks);
-        D.first_miss = static_cast<int>(set.miss_blocks);
-        D.first_clear = static_cast<int>(set.clear_blocks);
-        slot_of[k] = next;
-        descs[next++] = D;
-        extent_blocks += hit;
-        set.hit_blocks += hit;
-        set.miss_blocks += miss;
-        set.clear_blocks += clear;
+        D.first_hit = static_cast<int>(first[0]);
+        D.first_miss = static_cast<int>(first[1]);
+        D.first_clear = static_cast<int>(first[2]);
+        slot_of[k] = slot;
+        descs[slot] = D;
+        extent_blocks += BlocksOf(D.num_returns, kBlock);
         CMX_REQUIRE(extent_blocks <= kIntMax, "insertion %d: too many returns in one call", k);
-      }
-      set.end = next;
-      sets.push_back(set);
-    }
-  }
+      });
 
   const int device = grids[0]->device;
   WorkspaceLease ws(device);
@@ -337,37 +278,35 @@ void InsertBatch(const cmx_grid3d_insertion* insertions, int num, float hit_prob
   if (extent_blocks == 0) return;                        // nothing is written, FinishUpdate no-op
 
   // One upload block: descriptors | extent boxes (preset) | points.
-  const size_t boxes_at = Align256(sizeof(InsertionDesc) * num);
-  const size_t points_at = Align256(boxes_at + 8 * sizeof(int) * num);
-  const size_t bytes = Align256(points_at + staged_floats * sizeof(float));
-  char* h_block = static_cast<char*>(ws->pinned[0].Reserve(bytes));
-  char* d_block = static_cast<char*>(ws->dev[0].Reserve(bytes));
-  InsertionDesc* h_descs = reinterpret_cast<InsertionDesc*>(h_block);
-  const InsertionDesc* d_descs = reinterpret_cast<const InsertionDesc*>(d_block);
-  int* h_preset = reinterpret_cast<int*>(h_block + boxes_at);
-  int* d_boxes = reinterpret_cast<int*>(d_block + boxes_at);
-  float* h_points = reinterpret_cast<float*>(h_block + points_at);
-  const float* d_points = reinterpret_cast<const float*>(d_block + points_at);
+  BlockLayout block;
+  const auto descs_in = block.Add<Grid3DInsertionDesc>(num);
+  const auto boxes_in = block.Add<int>(8 * static_cast<size_t>(num));
+  const auto points_in = block.Add<float>(clouds.floats());
+  char* h_block = static_cast<char*>(ws->pinned[0].Reserve(block.bytes));
+  char* d_block = static_cast<char*>(ws->dev[0].Reserve(block.bytes));
+  Grid3DInsertionDesc* h_descs = descs_in(h_block);
+  const Grid3DInsertionDesc* d_descs = descs_in(d_block);
+  int* d_boxes = boxes_in(d_block);
+  const float* d_points = points_in(d_block);
   // Read back: the boxes; raised by the kernels in pinned memory themselves: the error flags.
   int* h_boxes = ws->pinned[1].ReserveAs<int>(9 * static_cast<size_t>(num));
   int* h_errors = h_boxes + 8 * static_cast<size_t>(num);
   std::memset(h_errors, 0, sizeof(int) * num);
   for (int k = 0; k < num; ++k)
     if (insertions[k].num_returns > 0)
-      descs[slot_of[k]].returns = d_points + clouds[insertions[k].returns_xyz].second;
-  std::memcpy(h_descs, descs.data(), sizeof(InsertionDesc) * num);
+      descs[slot_of[k]].returns = d_points + clouds.OffsetOf(insertions[k].returns_xyz);
+  std::memcpy(h_descs, descs.data(), sizeof(Grid3DInsertionDesc) * num);
   for (int s = 0; s < num; ++s) {
     const int preset[8] = {kIntMax, kIntMax, kIntMax, kIntMin, kIntMin, kIntMin, 0, 0};
-    std::memcpy(h_preset + 8 * static_cast<size_t>(s), preset, sizeof(preset));
+    std::memcpy(boxes_in(h_block) + 8 * static_cast<size_t>(s), preset, sizeof(preset));
   }
   // Every distinct cloud once (the pool's threads: a copy is memory bound).
-  ParallelFor(static_cast<int>(cloud_order.size()), 8, [&](int s) {
-    const std::pair<int, size_t>& at = clouds.find(cloud_order[s])->second;
-    std::memcpy(h_points + at.second, cloud_order[s], 3 * sizeof(float) * at.first);
+  clouds.CopyTo(points_in(h_block), [](int n, const std::function<void(int)>& copy) {
+    ParallelFor(n, 8, copy);
   });
 
   // Pass 0: the box of every insertion, one launch and one read-back.
-  SmallCopyAsync(d_block, h_block, bytes, /*to_device=*/true, stream);
+  SmallCopyAsync(d_block, h_block, block.bytes, /*to_device=*/true, stream);
   BatchExtentKernel<<<static_cast<unsigned>(extent_blocks), kBlock, 0, stream>>>(
       d_descs, num, num_free_space_voxels, d_boxes);
   CMX_HIP(hipGetLastError());
@@ -392,7 +331,7 @@ void InsertBatch(const cmx_grid3d_insertion* insertions, int num, float hit_prob
     }
     planned_grids[g].grid_size = grids[g]->grid_size;
   }
-  PlanInsertions(&planned_grids, inputs.data(), planned, round_of.data());
+  PlanInsertions(&planned_grids, inputs.data(), planned);
   CMX_REQUIRE(planned == num, "insertion %d: a ray spans 2^15 voxels or more", planned);
 
   // Every new brick before any old one is released: an allocation that fails leaves every grid
@@ -409,18 +348,18 @@ void InsertBatch(const cmx_grid3d_insertion* insertions, int num, float hit_prob
         BrickView{staged.cells[g] ? staged.cells[g] : grids[g]->cells, B.lo[0], B.lo[1], B.lo[2],
                   B.dims[0], B.dims[1], B.dims[2]};
   }
-  SmallCopyAsync(d_block, h_block, sizeof(InsertionDesc) * num, /*to_device=*/true, stream);
+  SmallCopyAsync(d_block, h_block, sizeof(Grid3DInsertionDesc) * num, /*to_device=*/true, stream);
   for (const LaunchSet& set : sets) {
     const int n = set.end - set.begin;
-    const InsertionDesc* set_descs = d_descs + set.begin;
-    if (set.hit_blocks > 0)
-      BatchHitKernel<<<static_cast<unsigned>(set.hit_blocks), kBlock, 0, stream>>>(
+    const Grid3DInsertionDesc* set_descs = d_descs + set.begin;
+    if (set.total[0] > 0)
+      BatchHitKernel<<<static_cast<unsigned>(set.total[0]), kBlock, 0, stream>>>(
           set_descs, n, hit_table, h_errors + set.begin);
-    if (set.miss_blocks > 0)
-      BatchMissKernel<<<static_cast<unsigned>(set.miss_blocks), kBlock, 0, stream>>>(
+    if (set.total[1] > 0)
+      BatchMissKernel<<<static_cast<unsigned>(set.total[1]), kBlock, 0, stream>>>(
           set_descs, n, num_free_space_voxels, miss_table, h_errors + set.begin);
-    if (set.clear_blocks > 0)
-      BatchClearKernel<<<static_cast<unsigned>(set.clear_blocks), kBlock, 0, stream>>>(
+    if (set.total[2] > 0)
+      BatchClearKernel<<<static_cast<unsigned>(set.total[2]), kBlock, 0, stream>>>(
           set_descs, n, num_free_space_voxels);
   }
   CMX_HIP(hipGetLastError());
@@ -481,7 +420,10 @@ extern "C" cmx_status cmx_debug_grid3d_insert_plan(const cmx_debug_grid3d_state*
       inputs[k].grid = insertions[k].grid;
       std::memcpy(inputs[k].box, insertions[k].box, sizeof(inputs[k].box));
     }
-    PlanInsertions(&planned, inputs.data(), num_insertions, rounds);
+    TargetRounds<int> order;
+    for (int k = 0; k < num_insertions; ++k) order.Add(inputs[k].grid);
+    std::copy(order.round_of.begin(), order.round_of.end(), rounds);
+    PlanInsertions(&planned, inputs.data(), num_insertions);
     for (int g = 0; g < num_grids; ++g) {
       final_states[g] = cmx_debug_grid3d_state{};
       for (int a = 0; a < 3; ++a) {

@@ -8,7 +8,9 @@ the tree's own build.HIP_FLAGS (no GPU needed), the output is split per kernel s
 every kernel the report says whether the instruction stream is the same on both sides (local
 labels renumbered, comments dropped) and prints the register, LDS and scratch figures of both.
 Kernels are matched by symbol across the whole tree, so one that moved to another file is still
-compared with itself.  Kernels of source files that are byte-equal in both trees must come out
+compared with itself.  A symbol that more than one file of a tree defines (kernels of the same
+name and signature in two anonymous namespaces mangle alike) names several kernels: those are
+matched by file and symbol instead, and a line of the report names them.  Kernels of source files that are byte-equal in both trees must come out
 identical (the tool's own sanity check): they are summed up in one line per file unless one
 differs or --all is given.  Exit status 1 when a kernel differs or exists on one side only: a refactor
 of a kernel file is done when this prints "identical" on every line.
@@ -119,14 +121,25 @@ def main():
         for k, tree in enumerate((args.tree_a, args.tree_b)):
             out_dir = os.path.join(tmp, "ab"[k])
             os.makedirs(out_dir)
-            found = {}
+            found = []
             for name, text in compile_tree(os.path.abspath(tree), out_dir, args.j).items():
                 for symbol, (stream, figs) in split_kernels(text).items():
-                    found[symbol] = (name, stream, figs)
+                    found.append((symbol, name, stream, figs))
             sides.append(found)
-    a, b = sides
+    # A kernel's key: its symbol, and its file too where the symbol alone does not tell.
+    duplicates = {}
+    for found in sides:
+        files = {}
+        for symbol, name, _, _ in found:
+            files.setdefault(symbol, set()).add(name)
+        for symbol, where in files.items():
+            if len(where) > 1:
+                duplicates.setdefault(symbol, set()).update(where)
+    a, b = ({(symbol, name if symbol in duplicates else ""): (name, stream, figs)
+             for symbol, name, stream, figs in found} for found in sides)
     symbols = sorted(set(a) | set(b), key=lambda s: ((a.get(s) or b.get(s))[0], s))
-    names = demangle(symbols)
+    names = demangle(sorted({s[0] for s in symbols}))
+    names = {s: names[s[0]] for s in symbols}
     fmt = lambda f: " ".join(f"{k.split('_')[0]}={f[k]}" for k in FIGURES)
     def source(tree, name):
         with open(os.path.join(tree, "cartographer_amd", "csrc", name), "rb") as f:
@@ -138,6 +151,9 @@ def main():
     name_a, name_b = args.names or (args.tree_a, args.tree_b)
     print(f"# A = {name_a}\n# B = {name_b}")
     print("# figures: vgpr_count sgpr_count group_segment_fixed_size private_segment_fixed_size")
+    for symbol in sorted(duplicates):
+        print(f"# DUPLICATE SYMBOL {symbol} in {', '.join(sorted(duplicates[symbol]))}: "
+              "matched by file and symbol")
     for s in symbols:
         if s not in a or s not in b:
             side, (name, _, figs) = ("A", a[s]) if s in a else ("B", b[s])
