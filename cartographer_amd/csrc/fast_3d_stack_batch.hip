@@ -2,7 +2,7 @@
 // ConstraintBuilder3D::DispatchScanMatcherConstruction (constraint_builder_3d.cc:170-198) does once
 // per submap of a loaded map, as ONE chain of launches whose length does not depend on the number
 // of submaps.  Every kernel here is the twin of a single-matcher kernel (fast_3d_stack.hip,
-// rt_3d.hip) and calls the same per-cell function (fast_3d_stack_device.h, ScatterVoxel), so a
+// dense_brick_3d.hip) and calls the same per-cell function (fast_3d_stack_device.h, ScatterVoxel), so a
 // matcher of a batch is the single create's bit for bit.  Workgroups are dealt to (submap, tile of
 // cells) through prefix tables of block counts; every matcher lives in one allocation of its own.
 #include <algorithm>

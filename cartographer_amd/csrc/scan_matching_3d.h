@@ -61,7 +61,7 @@ __device__ __forceinline__ float ValueToProbabilityDev(unsigned raw) {
 
 // ConvertToPrecomputationGrid (SM3/precomputation_grid_3d.cc:49-62): the uint8 value level 0 of
 // the precomputation stack holds for a raw HybridGrid value (0 -> 0).  Shared by the voxel-list
-// scatter (rt_3d.hip) and the crop of a resident grid (fast_3d_stack.hip).
+// scatter (dense_brick_3d.hip) and the crop of a resident grid (fast_3d_stack.hip).
 __device__ __forceinline__ uint8_t PrecomputationValueDev(unsigned raw) {
   const float kMinP = 0.1f;
   const float kMaxP = 1.f - kMinP;
@@ -71,7 +71,7 @@ __device__ __forceinline__ uint8_t PrecomputationValueDev(unsigned raw) {
 
 // One voxel of a list into the dense brick over the list's box: the raw uint16 value
 // (bytes_per_cell 2) or ConvertToPrecomputationGrid's uint8 (1).  Shared by the single scatter
-// (rt_3d.hip) and the scatter of a batch of matchers (fast_3d_stack_batch.hip).
+// (dense_brick_3d.hip) and the scatter of a batch of matchers (fast_3d_stack_batch.hip).
 __device__ __forceinline__ void ScatterVoxel(const cmx_voxel& v, const Brick& b,
                                              int bytes_per_cell) {
   const size_t off = (static_cast<size_t>(v.z - b.lo_z) * b.ny + (v.y - b.lo_y)) * b.nx +
@@ -183,6 +183,12 @@ struct DeviceBrick {
   DeviceBrick& operator=(const DeviceBrick&) = delete;
 };
 
+// ---- dense_brick_3d.hip
+// Box [lo, hi] (inclusive) as a brick without cells, within the index range every dense brick
+// of this library supports.
+Brick BoxBrick(const int lo[3], const int hi[3]);
+// The voxel list on the device (a workspace buffer), copy enqueued on ws.stream.
+cmx_voxel* UploadVoxels(Workspace& ws, const cmx_voxel* voxels, int64_t n);
 // Bounding box of a voxel list; false when the list is empty.
 bool VoxelBounds(const cmx_voxel* voxels, int64_t n, int lo[3], int hi[3]);
 // Bounding box of a voxel list; the cell at the origin when the list is empty.

@@ -98,7 +98,7 @@ def rt3d_c4(synth, rings=64, az=1024):
 
 def rt3d_c4_shaped(synth):
     """C4's SHAPE at a size the oracle finishes in seconds: L = 5 (11^3 translations, 6^3 = 216
-    groups of 2x2x2 per rotation -- the flat 192-lane group mapping of rt_3d.hip), A = 3
+    groups of 2x2x2 per rotation -- the flat 192-lane group mapping of rt_3d_bounds.hip), A = 3
     (343 rotations), a tilted initial orientation, ~4 k points."""
     grid, world = synth.make_submap_3d(5, 0.1, (9.0, 8.0, 4.0), 5, 10, 128)
     pos = world.free_position(6, 0.6)

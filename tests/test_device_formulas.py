@@ -4,7 +4,7 @@ shortcuts whose exactness the GPU parity tests rely on but cannot enumerate:
 * `SumUpperBound` (fast_2d_device.h): the integer recovered from a node's f32 score must never be
   below the integer sum the score was computed from, or the early exit of `ExpandWaveKernel`
   could drop a child the reference keeps.
-* `FastCellIndex` (rt_3d.hip) / `CellIndexF64` (cmx_device.h): when the shortcut path is taken
+* `FastCellIndex` (rt_3d_device.h) / `CellIndexF64` (cmx_device.h): when the shortcut path is taken
   its result must equal lround of the IEEE quotient the reference computes.
 """
 import numpy as np

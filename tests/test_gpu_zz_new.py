@@ -571,7 +571,7 @@ def _rt3d_against_golden(synth, d, g, debug, bulk):
                                   "dense-shipped", "1", "0"])
 def test_rt3d_c4_shaped_equals_the_reference(synth, golden_c4, debug, bulk):
     """C4's shape at 4096 points: L = 5 -> 6^3 = 216 groups of 2x2x2 translations per rotation
-    (the flat 192-lane group mapping of rt_3d.hip spans rotations), A = 3 -> 343 rotations, a
+    (the flat 192-lane group mapping of rt_3d_bounds.hip spans rotations), A = 3 -> 343 rotations, a
     tilted initial orientation.  Bounds path and exhaustive path, f32 score bit-equal and pose
     equal to what RealTimeCorrelativeScanMatcher3D::Match itself returned
     (tests/golden/rt3d_c4_reference.json)."""
