@@ -65,6 +65,18 @@ class DebugGrid2DInsertion(C.Structure):
                 ("num_misses", C.c_int32), ("reserved", C.c_int32)]
 
 
+class TSDF2DInsertion(C.Structure):
+    """cmx_tsdf2d_insertion: one (grid, scan) pair of cmx_tsdf2d_insert_batch."""
+    _fields_ = [("grid", C.c_void_p), ("origin_xyz", C.c_void_p), ("returns_xyz", C.c_void_p),
+                ("num_returns", C.c_int32)]
+
+
+class DebugTSDF2DInsertion(C.Structure):
+    """cmx_debug_tsdf2d_insertion: an insertion of cmx_debug_tsdf2d_insert_plan (grid by index)."""
+    _fields_ = [("grid", C.c_int32), ("num_returns", C.c_int32), ("origin_xyz", C.c_void_p),
+                ("returns_xyz", C.c_void_p)]
+
+
 class Grid3DInsertion(C.Structure):
     """cmx_grid3d_insertion: one (grid, cloud) pair of cmx_grid3d_insert_batch."""
     _fields_ = [("grid", C.c_void_p), ("origin_xyz", C.c_void_p), ("returns_xyz", C.c_void_p),
@@ -218,7 +230,7 @@ EXPORTED_SYMBOLS = [
     "cmx_grid2d_get_limits", "cmx_grid2d_download", "cmx_grid2d_crop", "cmx_grid2d_insert",
     "cmx_rt2d_match_grid", "cmx_grid2d_insert_batch",
     "cmx_tsdf2d_create", "cmx_tsdf2d_destroy", "cmx_tsdf2d_get_limits", "cmx_tsdf2d_download",
-    "cmx_tsdf2d_insert", "cmx_tsdf2d_crop", "cmx_rt2d_match_tsdf_grid",
+    "cmx_tsdf2d_insert", "cmx_tsdf2d_insert_batch", "cmx_tsdf2d_crop", "cmx_rt2d_match_tsdf_grid",
     "cmx_fast2d_create_from_tsdf",
     "cmx_rt2d_match_tsdf_grid_batch", "cmx_rt2d_match_tsdf_grid_batch_resident",
     "cmx_rt2d_match_grid_batch", "cmx_rt2d_match_grid_batch_resident",
@@ -256,7 +268,8 @@ EXPORTED_SYMBOLS = [
 
 # include/cartographer_mi355x_debug.h (test and tool switches, not part of the boundary).
 DEBUG_SYMBOLS = ["cmx_debug_set", "cmx_debug_reset", "cmx_debug_fast2d_plan",
-                 "cmx_debug_grid2d_insert_plan", "cmx_debug_grid3d_insert_plan"]
+                 "cmx_debug_grid2d_insert_plan", "cmx_debug_grid3d_insert_plan",
+                 "cmx_debug_tsdf2d_insert_plan"]
 
 _lib = None
 
@@ -351,6 +364,13 @@ def lib():
     L.cmx_tsdf2d_download.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
     L.cmx_tsdf2d_insert.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
                                     P(TSDFInserterOptions2D)]
+    if hasattr(L, "cmx_tsdf2d_insert_batch"):   # (absent from an older library an A/B tool loads)
+        L.cmx_tsdf2d_insert_batch.argtypes = [P(TSDF2DInsertion), C.c_int32,
+                                              P(TSDFInserterOptions2D)]
+        L.cmx_debug_tsdf2d_insert_plan.argtypes = [P(Grid2DLimits), C.c_int32,
+                                                   P(DebugTSDF2DInsertion), C.c_int32,
+                                                   P(TSDFInserterOptions2D), C.c_void_p,
+                                                   P(Grid2DLimits), C.c_void_p, P(C.c_int32)]
     L.cmx_tsdf2d_crop.argtypes = [C.c_void_p]
     L.cmx_rt2d_match_tsdf_grid.argtypes = [P(RtOptions), C.c_void_p, P(Pose2d), C.c_void_p,
                                            C.c_int32, P(C.c_double), P(Pose2d), P(MatchStats)]

@@ -119,6 +119,7 @@ cmx_status Guard(F&& body) {
   X(fast3d_create_chain)  /* most matchers per chain of launches of cmx_fast3d_create_batch (0: default; tests: splits a batch) */ \
   X(grid2d_insert_chain)  /* most insertions per set of launches of a round of cmx_grid2d_insert_batch (0: default; tests: splits a round) */ \
   X(grid3d_insert_chain)  /* most insertions per set of launches of a round of cmx_grid3d_insert_batch (0: default; tests: splits a round) */ \
+  X(tsdf2d_insert_chain)  /* most insertions per set of launches of a round of cmx_tsdf2d_insert_batch (0: default; tests: splits a round) */ \
   X(filters_generic)     /* 1: voxel filters of small clouds through the multi-launch path too */ \
   X(fast3d_byte_loads)    /* 1: every child cell with its own byte load */                         \
   X(fast3d_affinity)      /* 1: nodes of a problem on any XCD, 2: on one */                        \

@@ -36,6 +36,7 @@
 #include "../../include/cartographer_mi355x_debug.h"
 #include "cmx_batch.h"
 #include "grid_2d_internal.h"
+#include "grid_grow_batch.h"
 
 namespace cmx {
 namespace {
@@ -211,27 +212,6 @@ BatchFinishKernel(const Grid2DInsertionDesc* __restrict__ descs, int num) {
   }
 }
 
-// Grid2D::GrowLimits composed over every doubling of a call: the old grid lands at its final
-// offset in the new storage, everything around it is unknown.  blockIdx.y = grid.
-struct GrowDesc {
-  const uint16_t* old_cells;
-  uint16_t* grown;
-  int old_nx, old_ny, nx, ny, start_x, start_y;
-};
-
-__global__ void __launch_bounds__(256) BatchGrowKernel(const GrowDesc* __restrict__ descs) {
-  const GrowDesc& G = descs[blockIdx.y];
-  const size_t count = static_cast<size_t>(G.nx) * G.ny;
-  for (size_t i = static_cast<size_t>(blockIdx.x) * 256 + threadIdx.x; i < count;
-       i += static_cast<size_t>(gridDim.x) * 256) {
-    const int x = static_cast<int>(i % G.nx) - G.start_x;
-    const int y = static_cast<int>(i / G.nx) - G.start_y;
-    const bool old = static_cast<unsigned>(x) < static_cast<unsigned>(G.old_nx) &&
-                     static_cast<unsigned>(y) < static_cast<unsigned>(G.old_ny);
-    G.grown[i] = old ? G.old_cells[static_cast<size_t>(y) * G.old_nx + x] : uint16_t{0};
-  }
-}
-
 // ---- host ------------------------------------------------------------------------------
 // The odds table of a probability on a device, uploaded when it is first asked for and kept for
 // the life of the process (64 KB each; a call has two).
@@ -335,7 +315,7 @@ void InsertBatch(const cmx_grid2d_insertion* insertions, int num, float hit_prob
   // One upload block: descriptors (set after set) | grow descriptors | points.
   BlockLayout block;
   const auto descs_in = block.Add<Grid2DInsertionDesc>(num);
-  const auto grow_in = block.Add<GrowDesc>(growing.size());
+  const auto grow_in = block.Add<GrowDesc<1>>(growing.size());
   const auto points_in = block.Add<float>(scans.floats());
   char* h_block = static_cast<char*>(ws->pinned[0].Reserve(block.bytes));
   char* d_block = static_cast<char*>(ws->dev[0].Reserve(block.bytes));
@@ -349,8 +329,9 @@ void InsertBatch(const cmx_grid2d_insertion* insertions, int num, float hit_prob
   for (size_t j = 0; j < growing.size(); ++j) {
     const int g = growing[j];
     const PlannedGrid& G = planned_grids[g];
-    grow_in(h_block)[j] = GrowDesc{grids[g]->cells, grown.cells[g], grids[g]->nx, grids[g]->ny,
-                         G.limits.nx, G.limits.ny, G.start_x, G.start_y};
+    grow_in(h_block)[j] = GrowDesc<1>{{grids[g]->cells}, {grown.cells[g]}, nullptr, 0,
+                                      grids[g]->nx, grids[g]->ny, G.limits.nx, G.limits.ny,
+                                      G.start_x, G.start_y};
     largest_growing = std::max(largest_growing, static_cast<size_t>(G.limits.nx) * G.limits.ny);
   }
 
@@ -418,15 +399,8 @@ void InsertBatch(const cmx_grid2d_insertion* insertions, int num, float hit_prob
   } touched{grids, stream};
 
   SmallCopyAsync(d_block, h_block, block.bytes, /*to_device=*/true, stream);
-  if (!growing.empty()) {
-    const GrowDesc* d_grow = grow_in(d_block);
-    const unsigned columns =
-        static_cast<unsigned>(std::min<long long>(BlocksOf(largest_growing, 256), 4096));
-    for (size_t first = 0; first < growing.size(); first += 65535) {
-      const unsigned rows = static_cast<unsigned>(std::min<size_t>(growing.size() - first, 65535));
-      BatchGrowKernel<<<dim3(columns, rows), 256, 0, stream>>>(d_grow + first);
-    }
-  }
+  if (!growing.empty())
+    LaunchBatchGrow(grow_in(d_block), growing.size(), largest_growing, stream);
   for (const LaunchSet& set : sets) {
     const int n = set.end - set.begin;
     const Grid2DInsertionDesc* descs = descs_in(d_block) + set.begin;

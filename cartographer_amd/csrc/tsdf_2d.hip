@@ -22,121 +22,24 @@
 // "known = non-zero" for cropping.  A created plane that already carries the marker on a cell
 // is never updated there (SetCell returns early) and keeps the bit.
 //
-// Host and device split.  The O(N) per-hit work runs on the host with the libm the reference
-// uses, so that it is bit-exact without restating any transcendental: GrowAsNeeded, the sort,
+// Host and device split.  The O(N) per-hit work runs on the host (tsdf_2d_host.h, shared with
+// cmx_tsdf2d_insert_batch of tsdf_2d_batch.hip; the device pieces both share are in
+// tsdf_2d_internal.h) with the libm the reference uses, so that it is bit-exact without restating any transcendental: GrowAsNeeded, the sort,
 // EstimateNormals, the angle kernel, the range weight (std::pow), cos / sin of the normal and
 // the superscaled ray ends.  Per cell, on the device: GetCellCenter, the distance to the origin
 // (f32 norm, terms left to right), the projection on the normal, the clamp, GaussianKernel of
 // the distance (a float of a double exp), the weighted average and the value converters.
 #include <algorithm>
-#include <cmath>
 #include <cstring>
-#include <limits>
 #include <memory>
 #include <vector>
 
-#include "ray_mask_2d.h"
-#include "scan_matching_2d.h"
-
-struct cmx_tsdf2d {
-  int device = 0;
-  double resolution = 0., max_x = 0., max_y = 0.;
-  int nx = 0, ny = 0;
-  float max_tsd = 0.f, max_weight = 0.f;                 // the grid's TSDValueConverter
-  uint16_t* tsd = nullptr;                               // device, nx * ny
-  uint16_t* weight = nullptr;                            // device, nx * ny
-  int32_t* owner = nullptr;                              // device, nx * ny; kNoOwner between calls
-  unsigned long long version = 1;                        // bumped whenever the planes change
-  mutable cmx::Tsdf2DImageCache rt_image;                // byte images of the batched matcher
-};
+#include "tsdf_2d_internal.h"
 
 namespace cmx {
 namespace {
 
-constexpr uint16_t kUpdateMarker = 1u << 15;
-constexpr int kNoOwner = 0x7f7f7f7f;                     // hipMemset(0x7f): above any hit index
-
 // ---- device ----------------------------------------------------------------------
-// One hit of the sorted range data, prepared on the host.
-struct TsdfRay {
-  int2 begin, end;                 // superscaled ray ends (SuperscaleRay, :53-67)
-  float hit_x, hit_y, range;
-  float weight_factor;             // weight_factor_range * weight_factor_angle_ray_normal
-  float cos_normal, sin_normal;    // projection on the scan normal
-};
-
-struct TsdfParams {
-  uint16_t* tsd;
-  uint16_t* weight;
-  int* owner;
-  int nx, ny;
-  double resolution, max_x, max_y;
-  float origin_x, origin_y;
-  float truncation;                // the inserter's truncation_distance (f32, :133-134)
-  float maximum_weight;            // the inserter's maximum_weight (f32, :237)
-  int project, distance_kernel;
-  double kernel_scale, kernel_sigma2;  // 1.0 / (kSqrtTwoPi * sigma), double(sigma * sigma)
-  float max_tsd, tsd_resolution;   // the grid's TSDValueConverter
-  float max_weight, weight_resolution;
-  int* error;
-};
-
-__device__ __forceinline__ float ClampF(float v, float lo, float hi) {   // common::Clamp
-  if (v > hi) return hi;
-  if (v < lo) return lo;
-  return v;
-}
-
-// ValueConversionTables::GetConversionTable(unknown = lower, lower, upper) for one value; the
-// update marker is masked.
-__device__ __forceinline__ float ValueToBounded(unsigned raw, float lower, float upper) {
-  const unsigned v = raw & 32767u;
-  if (v == 0) return lower;
-  const float scale = (upper - lower) / 32766.f;
-  return static_cast<float>(v) * scale + (lower - scale);
-}
-
-// TSDValueConverter::TSDToValue / WeightToValue (tsd_value_converter.h:39-57).
-__device__ __forceinline__ uint16_t TsdToValue(const TsdfParams& P, float tsd) {
-  return static_cast<uint16_t>(
-      LRoundF32((ClampF(tsd, -P.max_tsd, P.max_tsd) - -P.max_tsd) * P.tsd_resolution) + 1);
-}
-__device__ __forceinline__ uint16_t WeightToValue(const TsdfParams& P, float weight) {
-  return static_cast<uint16_t>(
-      LRoundF32((ClampF(weight, 0.f, P.max_weight) - 0.f) * P.weight_resolution) + 1);
-}
-
-// InsertHit's per-cell update (:206-222): the clamped tsd and the update weight of `cell` for
-// `ray`.  GetCellCenter (map_limits.h:79-82) takes (x, y) = (max_x - r (iy + .5), max_y - r (ix + .5)).
-__device__ __forceinline__ float2 CellUpdate(const TsdfParams& P, const TsdfRay& ray, int cx,
-                                             int cy) {
-  const float center_x = static_cast<float>(P.max_x - P.resolution * (cy + 0.5));
-  const float center_y = static_cast<float>(P.max_y - P.resolution * (cx + 0.5));
-  const float dx = center_x - P.origin_x, dy = center_y - P.origin_y;
-  const float distance_cell_to_origin = sqrtf(dx * dx + dy * dy);
-  float update_tsd = ray.range - distance_cell_to_origin;
-  if (P.project) {
-    update_tsd = (center_x - ray.hit_x) * ray.cos_normal + (center_y - ray.hit_y) * ray.sin_normal;
-  }
-  update_tsd = ClampF(update_tsd, -P.truncation, P.truncation);
-  float update_weight = ray.weight_factor;
-  if (P.distance_kernel) {
-    // GaussianKernel (:49-51): float of 1.0 / (kSqrtTwoPi * sigma) * exp(-0.5 x x / (sigma sigma))
-    const double e = -0.5 * static_cast<double>(update_tsd) * static_cast<double>(update_tsd) /
-                     P.kernel_sigma2;
-    update_weight *= static_cast<float>(P.kernel_scale * exp(e));
-  }
-  return make_float2(update_tsd, update_weight);
-}
-
-__device__ __forceinline__ bool Inside(const TsdfParams& P, int cx, int cy) {
-  if (static_cast<unsigned>(cx) < static_cast<unsigned>(P.nx) &&
-      static_cast<unsigned>(cy) < static_cast<unsigned>(P.ny))
-    return true;
-  *P.error = 1;                                          // the host checked the ray ends
-  return false;
-}
-
 // Pass 1: the lowest hit index with a non-zero update weight claims each cell.
 __global__ void __launch_bounds__(256)
 TsdfOwnerKernel(TsdfParams P, const TsdfRay* __restrict__ rays, int num_rays) {
@@ -198,107 +101,8 @@ __global__ void TsdfCropKernel(TsdfParams P, int off_x, int off_y, uint16_t* __r
 }
 
 // ---- host ------------------------------------------------------------------------
-struct P3 { float x, y, z; };
-struct V2 { float x, y; };
-
-// The stand-in Eigen's fixed-size norms: terms left to right; normalized() = v / sqrt(z) if
-// z = squaredNorm > 0, else v (Eigen 3.3 Dot.h).
-float Norm2(float x, float y) { return std::sqrt(x * x + y * y); }
-float Norm3(const P3& v) { return std::sqrt((v.x * v.x + v.y * v.y) + v.z * v.z); }
-V2 Normalized2(float x, float y) {
-  const float z = x * x + y * y;
-  if (z > 0.f) {
-    const float n = std::sqrt(z);
-    return {x / n, y / n};
-  }
-  return {x, y};
-}
-P3 Normalized3(const P3& v) {
-  const float z = (v.x * v.x + v.y * v.y) + v.z * v.z;
-  if (z > 0.f) {
-    const float n = std::sqrt(z);
-    return {v.x / n, v.y / n, v.z / n};
-  }
-  return v;
-}
-P3 Sub3(const P3& a, const P3& b) { return {a.x - b.x, a.y - b.y, a.z - b.z}; }
-
-// GaussianKernel (:49-51) on the host.
-float GaussianKernel(float x, float sigma) {
-  const float kSqrtTwoPi = std::sqrt(2.0 * M_PI);
-  return 1.0 / (kSqrtTwoPi * sigma) * std::exp(-0.5 * x * x / (sigma * sigma));
-}
-
-// common::NormalizeAngleDifference<float>.
-float NormalizeAngleDifference(float difference) {
-  const float kPi = float(M_PI);
-  while (difference > kPi) difference -= 2. * kPi;
-  while (difference < -kPi) difference += 2. * kPi;
-  return difference;
-}
-
-// EstimateNormal / EstimateNormals (normal_estimation_2d.cc:31-110).
-float EstimateNormal(const std::vector<P3>& returns, size_t estimation_point_index,
-                     size_t sample_window_begin, size_t sample_window_end, const P3& origin) {
-  const P3& estimation_point = returns[estimation_point_index];
-  if (sample_window_end - sample_window_begin < 2) {
-    const P3 d = Sub3(origin, estimation_point);
-    return std::atan2(d.y, d.x);
-  }
-  P3 mean_normal{0.f, 0.f, 0.f};
-  const P3 estimation_point_to_observation = Sub3(origin, estimation_point);
-  for (size_t k = sample_window_begin; k < sample_window_end; ++k) {
-    if (k == estimation_point_index) continue;
-    const P3 tangent = Sub3(estimation_point, returns[k]);
-    P3 sample_normal{-tangent.y, tangent.x, 0.f};
-    constexpr float kMinNormalLength = 1e-6f;
-    if (Norm3(sample_normal) < kMinNormalLength) continue;
-    const P3& o = estimation_point_to_observation;
-    if ((sample_normal.x * o.x + sample_normal.y * o.y) + sample_normal.z * o.z < 0) {
-      sample_normal = {-sample_normal.x, -sample_normal.y, -sample_normal.z};
-    }
-    sample_normal = Normalized3(sample_normal);
-    mean_normal.x += sample_normal.x;
-    mean_normal.y += sample_normal.y;
-    mean_normal.z += sample_normal.z;
-  }
-  return std::atan2(mean_normal.y, mean_normal.x);
-}
-
-std::vector<float> EstimateNormals(const std::vector<P3>& returns, const P3& origin,
-                                   int num_normal_samples, double sample_radius_d) {
-  std::vector<float> normals;
-  normals.reserve(returns.size());
-  const size_t max_num_samples = num_normal_samples;
-  const float sample_radius = sample_radius_d;
-  for (size_t current = 0; current < returns.size(); ++current) {
-    const P3& hit = returns[current];
-    size_t begin = current;
-    for (; begin > 0 && current - begin < max_num_samples / 2 &&
-           Norm3(Sub3(hit, returns[begin - 1])) < sample_radius;
-         --begin) {
-    }
-    size_t end = current;
-    for (; end < returns.size() && end - current < ceil(max_num_samples / 2.0) + 1 &&
-           Norm3(Sub3(hit, returns[end])) < sample_radius;
-         ++end) {
-    }
-    normals.push_back(EstimateNormal(returns, current, begin, end, origin));
-  }
-  return normals;
-}
-
-// MapLimits::GetCellIndex (map_limits.h:69-76).
-void CellIndex(double resolution, double max_x, double max_y, float px, float py, int* ix,
-               int* iy) {
-  *ix = static_cast<int>(std::lround((max_y - py) / resolution - 0.5));
-  *iy = static_cast<int>(std::lround((max_x - px) / resolution - 0.5));
-}
-
 bool Contains(const cmx_tsdf2d& g, float px, float py) {
-  int ix, iy;
-  CellIndex(g.resolution, g.max_x, g.max_y, px, py, &ix, &iy);
-  return ix >= 0 && ix < g.nx && iy >= 0 && iy < g.ny;
+  return tsdf2d::Contains(tsdf2d::Limits{g.resolution, g.max_x, g.max_y, g.nx, g.ny}, px, py);
 }
 
 void ResetOwner(cmx_tsdf2d* g, hipStream_t stream) {
@@ -344,23 +148,6 @@ void GrowLimits(cmx_tsdf2d* g, Workspace& ws, float px, float py) {
     g->ny *= 2;
     ResetOwner(g, ws.stream);
   }
-}
-
-TsdfParams MakeParams(const cmx_tsdf2d& g) {
-  TsdfParams P{};
-  P.tsd = g.tsd;
-  P.weight = g.weight;
-  P.owner = g.owner;
-  P.nx = g.nx;
-  P.ny = g.ny;
-  P.resolution = g.resolution;
-  P.max_x = g.max_x;
-  P.max_y = g.max_y;
-  P.max_tsd = g.max_tsd;
-  P.tsd_resolution = 32766.f / (g.max_tsd - -g.max_tsd);
-  P.max_weight = g.max_weight;
-  P.weight_resolution = 32766.f / (g.max_weight - 0.f);
-  return P;
 }
 
 }  // namespace
@@ -464,122 +251,35 @@ extern "C" cmx_status cmx_tsdf2d_insert(cmx_tsdf2d* grid, const float* origin_xy
   return Guard([&] {
     CMX_REQUIRE(grid && origin_xyz && options, "null argument");
     CMX_REQUIRE(num_returns >= 0 && (num_returns == 0 || returns_xyz), "bad range data");
-    CMX_REQUIRE(options->num_normal_samples > 0, "num_normal_samples must be > 0");   // :64-74
-    CMX_REQUIRE(options->sample_radius > 0., "sample_radius must be > 0");
+    RequireInserterOptions(options);
     const cmx_tsdf_inserter_options_2d& o = *options;
     WorkspaceLease ws(grid->device);
-    const float truncation_distance = static_cast<float>(o.truncation_distance);
-    const P3 origin{origin_xyz[0], origin_xyz[1], origin_xyz[2]};
-    std::vector<P3> returns(num_returns);
-    if (num_returns) std::memcpy(returns.data(), returns_xyz, sizeof(P3) * num_returns);
 
-    // GrowAsNeeded (:33-47): the box of origin.xy and hit + t * direction, direction in 3D.
-    float lo_x = origin.x, hi_x = origin.x, lo_y = origin.y, hi_y = origin.y;
-    for (const P3& hit : returns) {
-      const P3 direction = Normalized3(Sub3(hit, origin));
-      const float end_x = hit.x + truncation_distance * direction.x;
-      const float end_y = hit.y + truncation_distance * direction.y;
-      lo_x = std::min(lo_x, end_x); hi_x = std::max(hi_x, end_x);
-      lo_y = std::min(lo_y, end_y); hi_y = std::max(hi_y, end_y);
-    }
+    // The sort, the normals and the per-hit part of InsertHit (tsdf_2d_host.h), then
+    // GrowAsNeeded (:33-47) on the box they give.
+    const tsdf2d::PreparedScan scan = tsdf2d::PrepareScan(origin_xyz, returns_xyz, num_returns, o);
     constexpr float kPadding = 1e-6f;
-    GrowLimits(grid, *ws, lo_x - kPadding * 1.f, lo_y - kPadding * 1.f);
-    GrowLimits(grid, *ws, hi_x + kPadding * 1.f, hi_y + kPadding * 1.f);
+    GrowLimits(grid, *ws, scan.lo_x - kPadding * 1.f, scan.lo_y - kPadding * 1.f);
+    GrowLimits(grid, *ws, scan.hi_x + kPadding * 1.f, scan.hi_y + kPadding * 1.f);
 
-    // Normals, on the returns sorted by RangeDataSorter (:69-88, :139-152).
-    const double angle_bandwidth = o.update_weight_angle_scan_normal_to_ray_kernel_bandwidth;
-    const double distance_bandwidth = o.update_weight_distance_cell_to_hit_kernel_bandwidth;
-    const bool angle_kernel = angle_bandwidth != 0.f;
-    std::vector<float> normals;
-    if (o.project_sdf_distance_to_scan_normal || angle_kernel) {
-      const V2 o2{origin.x, origin.y};
-      std::sort(returns.begin(), returns.end(), [o2](const P3& lhs, const P3& rhs) {
-        const V2 delta_lhs = Normalized2(lhs.x - o2.x, lhs.y - o2.y);
-        const V2 delta_rhs = Normalized2(rhs.x - o2.x, rhs.y - o2.y);
-        if ((delta_lhs.y < 0.f) != (delta_rhs.y < 0.f)) {
-          return delta_lhs.y < 0.f;
-        } else if (delta_lhs.y < 0.f) {
-          return delta_lhs.x < delta_rhs.x;
-        } else {
-          return delta_lhs.x > delta_rhs.x;
-        }
-      });
-      normals = EstimateNormals(returns, origin, o.num_normal_samples, o.sample_radius);
-    }
-
-    // InsertHit's per-hit part (:171-201); hits closer than the truncation distance add no ray.
-    const double fine_resolution = grid->resolution / kSubpixelScale;
-    std::vector<TsdfRay> rays;
-    rays.reserve(returns.size());
-    for (size_t i = 0; i < returns.size(); ++i) {
-      const V2 hit{returns[i].x, returns[i].y};
-      const float normal = normals.empty() ? std::numeric_limits<float>::quiet_NaN() : normals[i];
-      const V2 ray{hit.x - origin.x, hit.y - origin.y};
-      const float range = Norm2(ray.x, ray.y);
-      if (range < truncation_distance) continue;
-      const float truncation_ratio = truncation_distance / range;
-      V2 begin{origin.x, origin.y};
-      if (!o.update_free_space) {
-        const float s = 1.0f - truncation_ratio;
-        begin = {origin.x + s * ray.x, origin.y + s * ray.y};
-      }
-      const float e = 1.0f + truncation_ratio;
-      const V2 end{origin.x + e * ray.x, origin.y + e * ray.y};
-      TsdfRay r{};
-      CellIndex(fine_resolution, grid->max_x, grid->max_y, begin.x, begin.y, &r.begin.x,
-                &r.begin.y);
-      CellIndex(fine_resolution, grid->max_x, grid->max_y, end.x, end.y, &r.end.x, &r.end.y);
-      // Every pixel of the mask lies in the box of the two end pixels.
-      for (const int2 c : {r.begin, r.end}) {
-        CMX_REQUIRE(c.x >= 0 && c.y >= 0 && c.x / kSubpixelScale < grid->nx &&
-                        c.y / kSubpixelScale < grid->ny,
-                    "range data leaves the grid limits after GrowAsNeeded (hit %zu; z != 0?)", i);
-      }
-      float weight_factor_angle_ray_normal = 1.f;
-      if (angle_kernel) {
-        const float angle_ray_normal =
-            NormalizeAngleDifference(normal - std::atan2(-ray.y, -ray.x));
-        weight_factor_angle_ray_normal = GaussianKernel(angle_ray_normal, angle_bandwidth);
-      }
-      float weight_factor_range = 1.f;
-      if (o.update_weight_range_exponent != 0) {               // ComputeRangeWeightFactor
-        weight_factor_range = 0.f;
-        if (std::abs(range) > 1e-6f)
-          weight_factor_range = 1.f / (std::pow(range, o.update_weight_range_exponent));
-      }
-      r.hit_x = hit.x;
-      r.hit_y = hit.y;
-      r.range = range;
-      r.weight_factor = weight_factor_range * weight_factor_angle_ray_normal;
-      if (o.project_sdf_distance_to_scan_normal) {
-        r.cos_normal = std::cos(normal);
-        r.sin_normal = std::sin(normal);
-      }
-      rays.push_back(r);
-    }
+    // The ray table, straight into the upload buffer; hits closer than the truncation distance
+    // add no ray.
+    const int num_rays = static_cast<int>(scan.rays.size());
+    TsdfRay* h_rays = ws->pinned[0].ReserveAs<TsdfRay>(std::max(num_rays, 1));
+    const long outside = tsdf2d::BuildRays(
+        scan, tsdf2d::Limits{grid->resolution, grid->max_x, grid->max_y, grid->nx, grid->ny},
+        h_rays);
+    CMX_REQUIRE(outside < 0,
+                "range data leaves the grid limits after GrowAsNeeded (hit %ld; z != 0?)", outside);
 
     ++grid->version;
-    const int num_rays = static_cast<int>(rays.size());
     if (num_rays == 0) {
       CMX_HIP(hipStreamSynchronize(ws->stream));
       return;
     }
     TsdfParams P = MakeParams(*grid);
-    P.origin_x = origin.x;
-    P.origin_y = origin.y;
-    P.truncation = truncation_distance;
-    P.maximum_weight = static_cast<float>(o.maximum_weight);
-    P.project = o.project_sdf_distance_to_scan_normal != 0;
-    P.distance_kernel = distance_bandwidth != 0.f;
-    if (P.distance_kernel) {
-      const float sigma = static_cast<float>(distance_bandwidth);
-      const float kSqrtTwoPi = std::sqrt(2.0 * M_PI);
-      P.kernel_scale = 1.0 / (kSqrtTwoPi * sigma);
-      P.kernel_sigma2 = sigma * sigma;
-    }
+    SetInsertion(&P, origin_xyz, o);
     P.error = ws->dev[2].ReserveAs<int>(1);
-    TsdfRay* h_rays = ws->pinned[0].ReserveAs<TsdfRay>(num_rays);
-    std::memcpy(h_rays, rays.data(), sizeof(TsdfRay) * num_rays);
     TsdfRay* d_rays = ws->dev[0].ReserveAs<TsdfRay>(num_rays);
     CMX_HIP(hipMemsetAsync(P.error, 0, sizeof(int), ws->stream));
     CMX_HIP(hipMemcpyAsync(d_rays, h_rays, sizeof(TsdfRay) * num_rays, hipMemcpyHostToDevice,

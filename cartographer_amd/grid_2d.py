@@ -129,6 +129,68 @@ def insert_batch_plan(limits, insertions):
              num_y_cells=f.num_y_cells) for f in final]
 
 
+def _tsdf_options(truncation_distance, maximum_weight, update_free_space, num_normal_samples,
+                  sample_radius, project_sdf_distance_to_scan_normal,
+                  update_weight_range_exponent, angle_kernel_bandwidth, distance_kernel_bandwidth):
+    """cmx_tsdf_inserter_options_2d from the keywords of ``TSDF2DOnDevice.insert``."""
+    return TSDFInserterOptions2D(
+        truncation_distance, maximum_weight, int(update_free_space), int(num_normal_samples),
+        sample_radius, int(project_sdf_distance_to_scan_normal),
+        int(update_weight_range_exponent), angle_kernel_bandwidth, distance_kernel_bandwidth)
+
+
+def _origin_xyz(origin_xyz, kept):
+    origin = np.ascontiguousarray(origin_xyz, np.float32).reshape(-1)[:3].copy()
+    kept[id(origin)] = (origin, origin)
+    return origin.ctypes.data
+
+
+def tsdf_insert_batch(insertions, **options):
+    """cmx_tsdf2d_insert_batch: ``grid.insert(origin_xyz, returns_xyz, **options)`` for every
+    ``(TSDF2DOnDevice, origin_xyz, returns_xyz)`` of the list, in list order and bit for bit, in
+    shared launches with one synchronisation.  A grid may appear several times; an array object
+    passed several times is one scan: it reaches the library by one pointer and, where the origins
+    are equal too, is sorted and has its normals estimated once."""
+    insertions = list(insertions)
+    opts = _tsdf_options(**options)
+    kept = {}                       # id(array) -> (array, float32 copy): alive until the call returns
+    items = (_lib.TSDF2DInsertion * max(len(insertions), 1))()
+    for item, (grid, origin_xyz, returns_xyz) in zip(items, insertions):
+        item.grid, item.origin_xyz = grid._h, _origin_xyz(origin_xyz, kept)
+        item.returns_xyz, item.num_returns = _points(returns_xyz, kept)
+    check(_lib.lib().cmx_tsdf2d_insert_batch(items, len(insertions), C.byref(opts)))
+
+
+def tsdf_insert_batch_plan(limits, insertions, **options):
+    """cmx_debug_tsdf2d_insert_plan: what one ``tsdf_insert_batch`` call would do to grids of the
+    given limits (dicts with resolution, max_x, max_y, num_x_cells, num_y_cells), without a
+    device.  ``insertions``: ``(grid index, origin_xyz, returns_xyz)``.  Returns, per insertion,
+    the round, the limits its grid has at that insertion and the number of rays, and the number of
+    distinct scans the call prepares."""
+    insertions = list(insertions)
+    opts = _tsdf_options(**options)
+    lims = (Grid2DLimits * len(limits))(*[
+        Grid2DLimits(l["resolution"], l["max_x"], l["max_y"], l["num_x_cells"], l["num_y_cells"],
+                     0.0, 0.0) for l in limits])
+    kept = {}
+    n = len(insertions)
+    items = (_lib.DebugTSDF2DInsertion * max(n, 1))()
+    for item, (grid, origin_xyz, returns_xyz) in zip(items, insertions):
+        item.grid, item.origin_xyz = int(grid), _origin_xyz(origin_xyz, kept)
+        item.returns_xyz, item.num_returns = _points(returns_xyz, kept)
+    rounds = np.empty(max(n, 1), np.int32)
+    rays = np.empty(max(n, 1), np.int32)
+    at = (Grid2DLimits * max(n, 1))()
+    scans = C.c_int32()
+    check(_lib.lib().cmx_debug_tsdf2d_insert_plan(lims, len(limits), items, n, C.byref(opts),
+                                                  rounds.ctypes.data, at, rays.ctypes.data,
+                                                  C.byref(scans)))
+    return ([int(r) for r in rounds[:n]],
+            [dict(resolution=f.resolution, max_x=f.max_x, max_y=f.max_y,
+                  num_x_cells=f.num_x_cells, num_y_cells=f.num_y_cells) for f in at[:n]],
+            [int(r) for r in rays[:n]], int(scans.value))
+
+
 class TSDF2DOnDevice:
     """TSDF2D(limits, truncation_distance, max_weight) in HBM: the tsd and weight planes (uint16,
     0 = unknown).  The constructor takes the arguments of the test suite's ``ReferenceTSDF2D``;
@@ -180,10 +242,10 @@ class TSDF2DOnDevice:
         ReferenceTSDF2D.insert, so one dict drives both."""
         origin = np.ascontiguousarray(origin_xyz, np.float32).reshape(-1)[:3].copy()
         ret = np.ascontiguousarray(returns_xyz, np.float32).reshape(-1, 3)
-        options = TSDFInserterOptions2D(
-            truncation_distance, maximum_weight, int(update_free_space), int(num_normal_samples),
-            sample_radius, int(project_sdf_distance_to_scan_normal),
-            int(update_weight_range_exponent), angle_kernel_bandwidth, distance_kernel_bandwidth)
+        options = _tsdf_options(
+            truncation_distance, maximum_weight, update_free_space, num_normal_samples,
+            sample_radius, project_sdf_distance_to_scan_normal, update_weight_range_exponent,
+            angle_kernel_bandwidth, distance_kernel_bandwidth)
         check(_lib.lib().cmx_tsdf2d_insert(self._h, origin.ctypes.data,
                                            ret.ctypes.data if ret.shape[0] else None,
                                            ret.shape[0], C.byref(options)))

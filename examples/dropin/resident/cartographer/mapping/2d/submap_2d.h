@@ -6,7 +6,8 @@
 // cmx_grid2d_crop, and grid() hands the matchers a Grid2D that is also a
 // dropin::DeviceGrid2DView, so that the adapters take the *_match_grid entry points: per scan
 // only the point clouds cross PCIe.  With grid_type = "TSDF"
-// the submap is a cmx_tsdf2d instead: cmx_tsdf2d_insert (TSDFRangeDataInserter2D::Insert),
+// the submap is a cmx_tsdf2d instead: cmx_tsdf2d_insert_batch (TSDFRangeDataInserter2D::Insert for
+// both active submaps in one call, the scan sorted and its normals estimated once),
 // cmx_tsdf2d_crop, and a TSDF2D view that is a dropin::DeviceTsdf2DView, so that the matchers take
 // cmx_rt2d_match_tsdf_grid and cmx_ceres2d_match_tsdf_grid.
 #ifndef DROPIN_RESIDENT_SUBMAP_2D_H_
@@ -131,34 +132,18 @@ class Submap2D {
   int num_range_data() const { return num_range_data_; }
   bool insertion_finished() const { return insertion_finished_; }
 
-  // The probability-grid insertion itself is made by ActiveSubmaps2D::InsertRangeData, for both
-  // active submaps in one cmx_grid2d_insert_batch call; these two are Submap2D::InsertRangeData's
-  // bookkeeping before and after it.
+  // The insertion itself is made by ActiveSubmaps2D::InsertRangeData, for both active submaps
+  // in one cmx_grid2d_insert_batch (cmx_tsdf2d_insert_batch) call; these are
+  // Submap2D::InsertRangeData's bookkeeping before and after it.
   cmx_grid2d* BeginInsertRangeData() {
     CHECK(!insertion_finished_);
     return device_grid_;
   }
-  void EndInsertRangeData() {
-    RefreshView();
-    ++num_range_data_;
-  }
-  // TSDFRangeDataInserter2D::Insert on the device (tsdf_range_data_inserter_2d.cc:131-240).
-  void InsertRangeData(const sensor::RangeData& range_data,
-                       const proto::TSDFRangeDataInserterOptions2D& o) {
+  cmx_tsdf2d* BeginInsertTsdfRangeData() {
     CHECK(!insertion_finished_);
-    const float origin[3] = {range_data.origin.x(), range_data.origin.y(), range_data.origin.z()};
-    const std::vector<float> returns = Flatten(range_data.returns);
-    const cmx_tsdf_inserter_options_2d options{
-        o.truncation_distance(), o.maximum_weight(), o.update_free_space() ? 1 : 0,
-        o.normal_estimation_options().num_normal_samples(),
-        o.normal_estimation_options().sample_radius(),
-        o.project_sdf_distance_to_scan_normal() ? 1 : 0, o.update_weight_range_exponent(),
-        o.update_weight_angle_scan_normal_to_ray_kernel_bandwidth(),
-        o.update_weight_distance_cell_to_hit_kernel_bandwidth()};
-    DropinCheckOk(cmx_tsdf2d_insert(device_tsdf_, origin,
-                                    returns.empty() ? nullptr : returns.data(),
-                                    static_cast<int32_t>(range_data.returns.size()), &options),
-                  "cmx_tsdf2d_insert");
+    return device_tsdf_;
+  }
+  void EndInsertRangeData() {
     RefreshView();
     ++num_range_data_;
   }
@@ -239,8 +224,7 @@ class ActiveSubmaps2D {
       AddSubmap(range_data.origin.head<2>());
     }
     if (tsdf()) {
-      for (auto& submap : submaps_)
-        submap->InsertRangeData(range_data, options_.tsdf_range_data_inserter_options_2d());
+      InsertIntoTsdfGrids(range_data);
     } else {
       InsertIntoProbabilityGrids(range_data);
     }
@@ -271,6 +255,31 @@ class ActiveSubmaps2D {
                                           static_cast<float>(options.miss_probability()),
                                           options.insert_free_space() ? 1 : 0),
                   "cmx_grid2d_insert_batch");
+    for (auto& submap : submaps_) submap->EndInsertRangeData();
+  }
+  // TSDFRangeDataInserter2D::Insert (tsdf_range_data_inserter_2d.cc:131-240) likewise: the scan is
+  // flattened once and passed by the same pointers, so that it is sorted and its normals are
+  // estimated once for both submaps.
+  void InsertIntoTsdfGrids(const sensor::RangeData& range_data) {
+    const proto::TSDFRangeDataInserterOptions2D& o = options_.tsdf_range_data_inserter_options_2d();
+    const float origin[3] = {range_data.origin.x(), range_data.origin.y(), range_data.origin.z()};
+    const std::vector<float> returns = Submap2D::Flatten(range_data.returns);
+    const cmx_tsdf_inserter_options_2d options{
+        o.truncation_distance(), o.maximum_weight(), o.update_free_space() ? 1 : 0,
+        o.normal_estimation_options().num_normal_samples(),
+        o.normal_estimation_options().sample_radius(),
+        o.project_sdf_distance_to_scan_normal() ? 1 : 0, o.update_weight_range_exponent(),
+        o.update_weight_angle_scan_normal_to_ray_kernel_bandwidth(),
+        o.update_weight_distance_cell_to_hit_kernel_bandwidth()};
+    std::vector<cmx_tsdf2d_insertion> insertions;
+    for (auto& submap : submaps_) {
+      insertions.push_back(cmx_tsdf2d_insertion{
+          submap->BeginInsertTsdfRangeData(), origin, returns.empty() ? nullptr : returns.data(),
+          static_cast<int32_t>(range_data.returns.size())});
+    }
+    DropinCheckOk(cmx_tsdf2d_insert_batch(insertions.data(),
+                                          static_cast<int32_t>(insertions.size()), &options),
+                  "cmx_tsdf2d_insert_batch");
     for (auto& submap : submaps_) submap->EndInsertRangeData();
   }
   void AddSubmap(const Eigen::Vector2f& origin) {

@@ -38,6 +38,9 @@
  *                                  pairs in one call: the two insertions of
  *                                  ActiveSubmaps2D::InsertRangeData (mapping/2d/submap_2d.cc:161-174),
  *                                  or those of many trajectories
+ *   cmx_tsdf2d_insert_batch        TSDFRangeDataInserter2D::Insert for many (grid, scan) pairs in
+ *                                  one call: the same two insertions on grid_type = "TSDF"
+ *                                  (mapping/internal/2d/tsdf_range_data_inserter_2d.cc:131-240)
  *   cmx_grid3d_insert_batch        RangeDataInserter3D::Insert for many (grid, cloud) pairs in one
  *                                  call: the four insertions of ActiveSubmaps3D::InsertData
  *                                  (mapping/3d/submap_3d.cc:271-287,310-329), or those of many
@@ -316,6 +319,7 @@ cmx_status cmx_rt2d_match_grid_batch_resident(const cmx_rt_options* options,
  *                         in the map frame, xyz triples; `origin_xyz` is the sensor origin.
  *                         Range data whose rays leave the grown limits (z != 0 shortens the
  *                         box GrowAsNeeded builds from 3D directions) is CMX_INVALID_ARGUMENT.
+ *   cmx_tsdf2d_insert_batch  the same for many (grid, range data) pairs in one call (below)
  *   cmx_tsdf2d_crop       grid = grid->ComputeCroppedGrid() (tsdf_2d.cc:118-135)
  *   cmx_rt2d_match_tsdf_grid  cmx_rt2d_match_tsdf with the planes read from HBM
  *   cmx_fast2d_create_from_tsdf  FastCorrelativeScanMatcher2D of the tsd plane over the cost
@@ -347,6 +351,44 @@ cmx_status cmx_tsdf2d_download(const cmx_tsdf2d* grid, uint16_t* tsd_cells,
 cmx_status cmx_tsdf2d_insert(cmx_tsdf2d* grid, const float* origin_xyz, const float* returns_xyz,
                              int32_t num_returns, const cmx_tsdf_inserter_options_2d* options);
 cmx_status cmx_tsdf2d_crop(cmx_tsdf2d* grid);
+
+/* One insertion of a cmx_tsdf2d_insert_batch call: the arguments of cmx_tsdf2d_insert that differ
+ * from insertion to insertion. */
+typedef struct cmx_tsdf2d_insertion {
+  cmx_tsdf2d* grid;
+  const float* origin_xyz;     /* 3 floats */
+  const float* returns_xyz;    /* num_returns xyz triples, map frame */
+  int32_t num_returns;
+} cmx_tsdf2d_insertion;
+
+/* cmx_tsdf2d_insert(insertions[i] ..., options) for i = 0 .. num_insertions - 1 in list order, bit
+ * for bit (both planes, the limits and the staleness of the cached matcher images), in shared
+ * launches: what ActiveSubmaps2D::InsertRangeData does to its two submaps on grid_type = "TSDF",
+ * or a fleet to the active submaps of every robot after one cmx_rt2d_match_tsdf_grid_batch.
+ *   - A grid may appear several times: its insertions apply in list order.  The r-th insertion of
+ *     every grid forms round r; a round is two launches (owner, apply) over all its insertions, so
+ *     the number of launches grows with the most insertions any one grid has, not with the number
+ *     of grids.  One upload and one synchronisation per call.
+ *   - Insertions with equal returns_xyz pointers and equal origin values are the same scan: it is
+ *     sorted and its normals are estimated once per call (distinct scans in parallel on the host).
+ *     Equal pointers must come with equal counts.
+ *   - An insertion may have no returns (the grid still grows around the origin), or only returns
+ *     closer than the truncation distance (no rays; the hits are still sorted and feed the
+ *     normals), as in the single call.  One set of options holds for the whole call.
+ *   - All or nothing, which is stricter than the single call: every check of the single call is
+ *     made for every insertion before the device is touched, against the limits its grid has at
+ *     that insertion -- null pointers and counts, num_normal_samples and sample_radius, a grid
+ *     beyond 2^30 cells, range data that leaves the limits after GrowAsNeeded.
+ *     CMX_INVALID_ARGUMENT names `insertion <index>` in cmx_last_error and no grid has changed,
+ *     neither its size nor its cells.  num_insertions < 1, null `insertions`, a null grid or origin
+ *     and grids on different devices are invalid.
+ *   - Every grid is grown once, to the size its last insertion needs, before anything is inserted.
+ *     When a device allocation fails there (CMX_OUT_OF_MEMORY), no grid has changed: neither its
+ *     size nor its cells, and no insertion has been applied. */
+cmx_status cmx_tsdf2d_insert_batch(const cmx_tsdf2d_insertion* insertions,
+                                   int32_t num_insertions,
+                                   const cmx_tsdf_inserter_options_2d* options);
+
 cmx_status cmx_rt2d_match_tsdf_grid(const cmx_rt_options* options, const cmx_tsdf2d* grid,
                                     const cmx_pose2d* initial_pose_estimate,
                                     const float* point_cloud_xyz, int32_t num_points,

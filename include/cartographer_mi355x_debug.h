@@ -77,6 +77,32 @@ cmx_status cmx_debug_grid2d_insert_plan(const cmx_grid2d_limits* limits, int32_t
                                         int32_t num_insertions, int32_t* rounds,
                                         cmx_grid2d_limits* final_limits);
 
+/* The plan of one cmx_tsdf2d_insert_batch call from the limits of its grids, the range data and
+ * the options alone: for every insertion its round (how many earlier insertions of the list go to
+ * the same grid), the limits its grid has AT that insertion (GrowAsNeeded of the insertions up to
+ * and including it replayed in list order; the cost bounds are copied from `limits`) and its number
+ * of rays (hits whose f32 range is at least the truncation distance); for the call the number of
+ * distinct scans the host prepares (sort, normals, weights): insertions with the same returns_xyz
+ * pointer and bitwise equal origin values share one.  The launch path asks the same functions;
+ * this entry launches nothing and needs no device.  `limits` [num_grids] are the grids' limits
+ * before the call; an insertion names its grid by index.  `rounds`, `limits_at`, `num_rays`
+ * [num_insertions] and `num_scans` [1] out.  The errors are those of the call itself, naming the
+ * insertion: a grid beyond 2^30 cells, range data that leaves the limits after GrowAsNeeded, one
+ * pointer with two counts. */
+typedef struct cmx_debug_tsdf2d_insertion {
+  int32_t grid;                /* index into `limits` */
+  int32_t num_returns;
+  const float* origin_xyz;     /* 3 floats */
+  const float* returns_xyz;
+} cmx_debug_tsdf2d_insertion;
+
+cmx_status cmx_debug_tsdf2d_insert_plan(const cmx_grid2d_limits* limits, int32_t num_grids,
+                                        const cmx_debug_tsdf2d_insertion* insertions,
+                                        int32_t num_insertions,
+                                        const cmx_tsdf_inserter_options_2d* options,
+                                        int32_t* rounds, cmx_grid2d_limits* limits_at,
+                                        int32_t* num_rays, int32_t* num_scans);
+
 /* The plan of one cmx_grid3d_insert_batch call from the state of its grids before the call and the
  * box of voxels every insertion touches (what the call's extent pass reads back): the round of
  * every insertion (how many earlier insertions of the list go to the same grid) and the brick
