@@ -94,6 +94,30 @@ class DebugGrid3DInsertion(C.Structure):
     _fields_ = [("grid", C.c_int32), ("reserved", C.c_int32), ("box", C.c_int32 * 6)]
 
 
+FILTER_VOXEL, FILTER_ADAPTIVE = 0, 1
+
+
+class FilterJob(C.Structure):
+    """cmx_filter_job: one filter of cmx_filter_batch, on a host cloud or on an earlier job's
+    output."""
+    _fields_ = [("point_cloud_xyz", C.c_void_p), ("num_points", C.c_int32),
+                ("input_job", C.c_int32), ("mode", C.c_int32), ("length", C.c_float),
+                ("min_num_points", C.c_float), ("max_range", C.c_float),
+                ("kept_indices", C.c_void_p), ("filtered_xyz", C.c_void_p)]
+
+
+class DebugFilterJobPlan(C.Structure):
+    """cmx_debug_filter_job_plan: where a job of cmx_filter_batch runs."""
+    _fields_ = [("set", C.c_int32), ("stage", C.c_int32), ("launch", C.c_int32), ("N", C.c_int32),
+                ("lds_bytes", C.c_int64), ("cloud_slot", C.c_int32), ("single", C.c_int32)]
+
+
+class DebugFilterCallPlan(C.Structure):
+    """cmx_debug_filter_call_plan: the launches and the staging of a cmx_filter_batch call."""
+    _fields_ = [("staged_bytes", C.c_int64), ("num_launches", C.c_int32),
+                ("num_sets", C.c_int32)]
+
+
 class TSDFInserterOptions2D(C.Structure):
     """cmx_tsdf_inserter_options_2d = proto::TSDFRangeDataInserterOptions2D (+ the
     NormalEstimationOptions2D it holds)."""
@@ -259,7 +283,7 @@ EXPORTED_SYMBOLS = [
     "cmx_fast2d_match_sharded", "cmx_fast3d_match_sharded", "cmx_shard_range",
     "cmx_pack_best_key", "cmx_unpack_best_key",
     "cmx_voxel_filter", "cmx_voxel_filter_indices", "cmx_adaptive_voxel_filter",
-    "cmx_adaptive_voxel_filter_indices",
+    "cmx_adaptive_voxel_filter_indices", "cmx_filter_batch",
     "cmx_compute_histogram",
     "cmx_intensity_grid3d_create", "cmx_intensity_grid3d_destroy",
     "cmx_grid3d_insert_with_intensities", "cmx_intensity_grid3d_download",
@@ -269,7 +293,7 @@ EXPORTED_SYMBOLS = [
 # include/cartographer_mi355x_debug.h (test and tool switches, not part of the boundary).
 DEBUG_SYMBOLS = ["cmx_debug_set", "cmx_debug_reset", "cmx_debug_fast2d_plan",
                  "cmx_debug_grid2d_insert_plan", "cmx_debug_grid3d_insert_plan",
-                 "cmx_debug_tsdf2d_insert_plan"]
+                 "cmx_debug_tsdf2d_insert_plan", "cmx_debug_filter_batch_plan"]
 
 _lib = None
 
@@ -452,6 +476,10 @@ def lib():
                                             C.c_float, C.c_int32, C.c_void_p, P(C.c_int32)]
     L.cmx_adaptive_voxel_filter_indices.argtypes = [C.c_void_p, C.c_int32, C.c_float, C.c_float,
                                                     C.c_float, C.c_int32, C.c_void_p, P(C.c_int32)]
+    if hasattr(L, "cmx_filter_batch"):   # (absent from an older library an A/B tool loads)
+        L.cmx_filter_batch.argtypes = [P(FilterJob), C.c_int32, C.c_int32, C.c_void_p]
+        L.cmx_debug_filter_batch_plan.argtypes = [P(FilterJob), C.c_int32, P(DebugFilterJobPlan),
+                                                  P(DebugFilterCallPlan)]
     L.cmx_compute_histogram.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]
     L.cmx_comm_init.argtypes = [C.c_void_p, C.c_int32, P(C.c_void_p)]
     L.cmx_comm_destroy.argtypes = [C.c_void_p]

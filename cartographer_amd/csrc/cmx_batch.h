@@ -1,5 +1,5 @@
 // What the batched calls share (cmx_{fast2d,fast3d}_create_batch,
-// cmx_{grid2d,grid3d,tsdf2d}_insert_batch):
+// cmx_{grid2d,grid3d,tsdf2d}_insert_batch, cmx_filter_batch):
 // a block finds the item of the call it works for, and the host lays out one upload block, stages
 // every distinct host array once, sorts the items into rounds and cuts them into launches.
 // Plain C++17 without HIP types or CMX_REQUIRE (a failure goes to a callback, the call site words

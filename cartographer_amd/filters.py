@@ -59,6 +59,72 @@ def adaptive_voxel_filter_indices(point_cloud, max_length, min_num_points, max_r
     return out[:kept.value].copy()
 
 
+def _filter_jobs(jobs):
+    """The cmx_filter_job array of `jobs`, the clouds it borrows and the root of every job."""
+    items = (_lib.FilterJob * max(len(jobs), 1))()
+    clouds, roots = {}, []
+    for k, job in enumerate(jobs):
+        item = items[k]
+        parent = job.get("input_job", -1)
+        cloud = job.get("cloud")
+        if cloud is not None:
+            # the same array object is the same cloud of the call: converted and staged once
+            if id(cloud) not in clouds:
+                clouds[id(cloud)] = (cloud, _cloud(cloud)[0])
+            xyz = clouds[id(cloud)][1]
+            item.point_cloud_xyz, item.num_points = xyz.ctypes.data, xyz.shape[0]
+        item.input_job = parent
+        mode = job.get("mode", "voxel")
+        item.mode = {"voxel": _lib.FILTER_VOXEL, "adaptive": _lib.FILTER_ADAPTIVE}.get(mode, mode)
+        item.length = job["length"]
+        item.min_num_points = job.get("min_num_points", 0.0)
+        item.max_range = job.get("max_range", 0.0)
+        roots.append(parent if isinstance(parent, int) and 0 <= parent < k else k)
+    return items, clouds, roots
+
+
+def filter_batch(jobs, device=0):
+    """Many filters in one call (``cmx_filter_batch``), a filter's output handed to the next on
+    the device.  A job is a dict: ``cloud`` (points of a root; the same array object twice is one
+    cloud, uploaded once) or ``input_job`` (index of an earlier root: this job filters the points
+    that one kept), ``mode`` ("voxel" or "adaptive"), ``length`` (resolution / max_length),
+    ``min_num_points`` and ``max_range`` (adaptive), ``indices`` and ``points`` (which outputs are
+    wanted, both by default).  Returns per job a dict with ``indices`` (ascending, into the job's
+    own input) and ``points``, None where not wanted: what ``voxel_filter(_indices)`` /
+    ``adaptive_voxel_filter(_indices)`` return for the job's input."""
+    items, clouds, roots = _filter_jobs(jobs)
+    outputs = []
+    for k, job in enumerate(jobs):
+        room = max(items[roots[k]].num_points, 1)
+        indices = np.empty(room, np.int32) if job.get("indices", True) else None
+        points = np.empty((room, 3), np.float32) if job.get("points", True) else None
+        items[k].kept_indices = None if indices is None else indices.ctypes.data
+        items[k].filtered_xyz = None if points is None else points.ctypes.data
+        outputs.append((indices, points))
+    kept = np.zeros(max(len(jobs), 1), np.int32)
+    _lib.check(_lib.lib().cmx_filter_batch(items, len(jobs), device, kept.ctypes.data))
+    return [dict(indices=None if i is None else i[:n].copy(),
+                 points=None if p is None else p[:n].copy())
+            for (i, p), n in zip(outputs, kept)]
+
+
+def filter_batch_plan(jobs):
+    """Where the jobs of ``filter_batch(jobs)`` would run (``cmx_debug_filter_batch_plan``; no
+    device needed): per job a dict of set, stage, launch, N, lds_bytes, cloud_slot and single,
+    and for the call a dict of num_launches, num_sets and staged_bytes."""
+    items, clouds, roots = _filter_jobs(jobs)
+    wanted = np.zeros(4, np.float32)      # (the plan looks at which outputs are wanted, never into them)
+    for k, job in enumerate(jobs):
+        items[k].kept_indices = wanted.ctypes.data if job.get("indices", True) else None
+        items[k].filtered_xyz = wanted.ctypes.data if job.get("points", True) else None
+    plans = (_lib.DebugFilterJobPlan * max(len(jobs), 1))()
+    call = _lib.DebugFilterCallPlan()
+    _lib.check(_lib.lib().cmx_debug_filter_batch_plan(items, len(jobs), plans, C.byref(call)))
+    return ([{name: getattr(plans[k], name) for name, _ in _lib.DebugFilterJobPlan._fields_}
+             for k in range(len(jobs))],
+            {name: getattr(call, name) for name, _ in _lib.DebugFilterCallPlan._fields_})
+
+
 def compute_histogram(point_cloud, histogram_size, device=0):
     xyz, n = _cloud(point_cloud)
     out = np.zeros(histogram_size, np.float32)

@@ -45,6 +45,10 @@
  *                                  call: the four insertions of ActiveSubmaps3D::InsertData
  *                                  (mapping/3d/submap_3d.cc:271-287,310-329), or those of many
  *                                  trajectories
+ *   cmx_filter_batch               sensor::VoxelFilter / AdaptiveVoxelFilter for many clouds in one
+ *                                  call, a filter's output handed to the next on the device: the
+ *                                  filter chains of LocalTrajectoryBuilder2D / 3D::AddRangeData
+ *                                  (sensor/internal/voxel_filter.cc), or those of many trajectories
  *
  * Conventions
  *   - Plain C, POD only.  Host pointers are borrowed for the duration of the
@@ -1054,6 +1058,39 @@ cmx_status cmx_adaptive_voxel_filter_indices(const float* point_cloud_xyz, int32
                                              float max_length, float min_num_points,
                                              float max_range, int32_t device,
                                              int32_t* kept_indices, int32_t* num_filtered);
+/* Many filters in one call, and chains of them: the VoxelFilter and AdaptiveVoxelFilter that
+ * LocalTrajectoryBuilder2D runs one on the other's output (2d/local_trajectory_builder_2d.cc),
+ * the VoxelFilter and the two AdaptiveVoxelFilters of LocalTrajectoryBuilder3D
+ * (3d/local_trajectory_builder_3d.cc), for one robot or for a fleet.  Job i returns, bit for
+ * bit, what cmx_voxel_filter(_indices) / cmx_adaptive_voxel_filter(_indices) return for its
+ * input.  A chained job (input_job >= 0) filters the points an earlier job kept, which never
+ * leave the device in between; its indices refer to THAT cloud.  A job may have several chained
+ * jobs, a chained job none (chains of two).  Output arrays need room for the num_points of the
+ * host cloud the job goes back to; a job without output pointers is valid only if a job is
+ * chained on it.  Equal point_cloud_xyz pointers are one cloud, with equal num_points, and are
+ * uploaded once.  A job without points yields 0, and so do the jobs chained on it.
+ * Host clouds of up to 4096 points and the jobs chained on them run one workgroup per job: all
+ * host clouds in a first stage of launches, all chained jobs in a second, one synchronisation at
+ * the end (calls that stage more than 32 MB go out in consecutive parts).  A host cloud above
+ * 4096 points, and every job chained on it, runs inside the call as the single calls do, one
+ * after the other with the host between the stages: same results, nothing gained.
+ * Every argument check is made for every job before the device is touched; CMX_INVALID_ARGUMENT
+ * names the job ("job <index>") in cmx_last_error.  num_jobs >= 1. */
+enum { CMX_FILTER_VOXEL = 0, CMX_FILTER_ADAPTIVE = 1 };
+typedef struct cmx_filter_job {
+  const float* point_cloud_xyz; /* host cloud, xyz triples; NULL iff input_job >= 0 */
+  int32_t num_points;           /* of the host cloud; 0 iff input_job >= 0 */
+  int32_t input_job;            /* -1: the host cloud.  Else the index of an EARLIER job whose own
+                                   input_job is -1: this job filters that job's output */
+  int32_t mode;                 /* CMX_FILTER_VOXEL / CMX_FILTER_ADAPTIVE */
+  float length;                 /* resolution (voxel) / max_length (adaptive); > 0 */
+  float min_num_points;         /* adaptive only */
+  float max_range;              /* adaptive only */
+  int32_t* kept_indices;        /* may be NULL; indices into THIS job's input, ascending */
+  float* filtered_xyz;          /* may be NULL */
+} cmx_filter_job;
+cmx_status cmx_filter_batch(const cmx_filter_job* jobs, int32_t num_jobs, int32_t device,
+                            int32_t* num_filtered /* [num_jobs] */);
 /* RotationalScanMatcher::ComputeHistogram (SM3/rotational_scan_matcher.cc:164-177): slices of
  * 0.2 m, points sorted by angle around the slice centroid, one weighted vote per point pair.
  * Same accumulation order as the reference; atan2f is the device's (<= 1 ulp from libm's). */

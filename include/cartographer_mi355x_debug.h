@@ -129,6 +129,38 @@ cmx_status cmx_debug_grid3d_insert_plan(const cmx_debug_grid3d_state* grids, int
                                         int32_t num_insertions, int32_t* rounds,
                                         cmx_debug_grid3d_state* final_states);
 
+/* The plan of one cmx_filter_batch call from its jobs alone (no cloud is read): which jobs take a
+ * workgroup of which launch.  Host clouds are stage 0, chained jobs stage 1; a stage is at most two
+ * launches, `launch` 0 for N <= 2048 (a compute unit holds two such workgroups) and 1 for N = 4096,
+ * each with the dynamic LDS of its largest N.  N is the LDS carve: a host cloud's points rounded up
+ * to a power of two, at least 64; a chained job takes its parent's.  A job without input (no
+ * points, or chained on such a job) takes no workgroup: set and launch -1, N 0.  A host cloud above
+ * 4096 points and the jobs chained on it run as the single calls do: `single` 1, set and launch
+ * -1.  `set` counts the consecutive parts a call goes out in (switch filter_batch_set_kb: the
+ * bound on a part's staged clouds and on its result slots, default 32 MB).  The launch path asks
+ * the same function; this entry launches nothing and needs no device.  The errors are those of
+ * the call itself, naming the job. */
+typedef struct cmx_debug_filter_job_plan {
+  int32_t set;
+  int32_t stage;               /* 0: a host cloud, 1: chained */
+  int32_t launch;              /* within its stage */
+  int32_t N;
+  int64_t lds_bytes;           /* the dynamic LDS its N asks for */
+  int32_t cloud_slot;          /* a host cloud with points: which of the call's distinct clouds
+                                  (equal pointers, equal slot); else -1 */
+  int32_t single;
+} cmx_debug_filter_job_plan;
+
+typedef struct cmx_debug_filter_call_plan {
+  int64_t staged_bytes;        /* the clouds uploaded for the workgroups of all sets */
+  int32_t num_launches;
+  int32_t num_sets;
+} cmx_debug_filter_call_plan;
+
+cmx_status cmx_debug_filter_batch_plan(const cmx_filter_job* jobs, int32_t num_jobs,
+                                       cmx_debug_filter_job_plan* job_plans,
+                                       cmx_debug_filter_call_plan* call_plan);
+
 #ifdef __cplusplus
 }
 #endif
