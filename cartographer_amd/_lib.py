@@ -118,6 +118,13 @@ class DebugFilterCallPlan(C.Structure):
                 ("num_sets", C.c_int32)]
 
 
+class DebugRt3DMatchPlan(C.Structure):
+    """cmx_debug_rt3d_match_plan: window, route and blocks of a match of cmx_rt3d_match_grid_batch."""
+    _fields_ = [("L", C.c_int32), ("A", C.c_int32), ("T", C.c_int64), ("R", C.c_int64),
+                ("route", C.c_int32), ("set", C.c_int32), ("first_block", C.c_int32),
+                ("blocks", C.c_int32)]
+
+
 class TSDFInserterOptions2D(C.Structure):
     """cmx_tsdf_inserter_options_2d = proto::TSDFRangeDataInserterOptions2D (+ the
     NormalEstimationOptions2D it holds)."""
@@ -288,12 +295,14 @@ EXPORTED_SYMBOLS = [
     "cmx_intensity_grid3d_create", "cmx_intensity_grid3d_destroy",
     "cmx_grid3d_insert_with_intensities", "cmx_intensity_grid3d_download",
     "cmx_ceres3d_match_grids_intensity",
+    "cmx_rt3d_match_grid_batch", "cmx_ceres3d_match_grids_batch",
 ]
 
 # include/cartographer_mi355x_debug.h (test and tool switches, not part of the boundary).
 DEBUG_SYMBOLS = ["cmx_debug_set", "cmx_debug_reset", "cmx_debug_fast2d_plan",
                  "cmx_debug_grid2d_insert_plan", "cmx_debug_grid3d_insert_plan",
-                 "cmx_debug_tsdf2d_insert_plan", "cmx_debug_filter_batch_plan"]
+                 "cmx_debug_tsdf2d_insert_plan", "cmx_debug_filter_batch_plan",
+                 "cmx_debug_rt3d_batch_plan"]
 
 _lib = None
 
@@ -466,6 +475,15 @@ def lib():
                                       P(C.c_float), P(Pose3d), P(MatchStats)]
     L.cmx_ceres3d_match_grids.argtypes = [P(Ceres3DOptions), C.c_void_p, P(Pose3d), P(C.c_void_p),
                                           P(C.c_void_p), C.c_void_p, P(Pose3d), P(CeresSummary)]
+    if hasattr(L, "cmx_rt3d_match_grid_batch"):   # (absent from an older library an A/B tool loads)
+        L.cmx_rt3d_match_grid_batch.argtypes = [P(RtOptions), P(C.c_void_p), C.c_int32, C.c_void_p,
+                                                P(C.c_void_p), C.c_void_p, C.c_void_p, C.c_void_p,
+                                                P(MatchStats)]
+        L.cmx_ceres3d_match_grids_batch.argtypes = [P(Ceres3DOptions), C.c_int32, C.c_void_p,
+                                                    C.c_void_p, P(C.c_void_p), P(C.c_void_p),
+                                                    C.c_void_p, C.c_void_p, C.c_void_p]
+        L.cmx_debug_rt3d_batch_plan.argtypes = [P(RtOptions), C.c_int32, C.c_void_p, C.c_void_p,
+                                                C.c_void_p, P(DebugRt3DMatchPlan)]
     L.cmx_fast3d_refine_batch.argtypes = [P(Ceres3DOptions), P(C.c_void_p), C.c_int32, C.c_void_p,
                                           C.c_void_p, P(NodeData3D), C.c_void_p, C.c_void_p]
     L.cmx_voxel_filter.argtypes = [C.c_void_p, C.c_int32, C.c_float, C.c_int32, C.c_void_p,

@@ -24,6 +24,7 @@
 // thread carries the (identical) minimizer state.
 #include <cmath>
 
+#include "cmx_batch.h"
 #include "scan_matching_3d.h"
 
 namespace cmx {
@@ -908,6 +909,97 @@ extern "C" cmx_status cmx_ceres3d_match_grids_intensity(
     double out[12];
     SolveProblems(*ws, &P, 1, cloud_floats, h_xyz, d_xyz, out);
     WriteResult(out, pose_estimate, summary);
+  });
+}
+
+// The same refinement for many trajectories (what follows cmx_rt3d_match_grid_batch): one
+// workgroup per match as ever, but one upload block -- problems | clouds, each distinct pointer
+// once | the zero brick of the empty grids -- one launch and one synchronisation for the call.
+extern "C" cmx_status cmx_ceres3d_match_grids_batch(
+    const cmx_ceres3d_options* options, int32_t num_matches, const double* target_translations_xyz,
+    const cmx_pose3d* initial_pose_estimates, const cmx_grid3d* const* grids,
+    const float* const* point_clouds_xyz, const int32_t* num_points, cmx_pose3d* pose_estimates,
+    cmx_ceres_summary* summaries) {
+  using namespace cmx;
+  return Guard([&] {
+    CMX_REQUIRE(num_matches >= 1, "num_matches %d < 1", num_matches);
+    CMX_REQUIRE(options && target_translations_xyz && initial_pose_estimates && grids &&
+                    point_clouds_xyz && num_points,
+                "null argument");
+    CMX_REQUIRE(pose_estimates != nullptr, "pose_estimates must not be null");
+    CheckOptions(*options);
+    const int pairs = options->num_pairs;
+    std::vector<Ceres3DProblem> problems(num_matches);
+    StagedArrays clouds(3);
+    int device = -1;
+    for (int i = 0; i < num_matches; ++i) {
+      Ceres3DProblem& P = problems[i];
+      P = Ceres3DProblem{};
+      SetOptions(*options, &P);
+      for (int k = 0; k < pairs; ++k) {
+        const size_t at = static_cast<size_t>(i) * pairs + k;
+        CMX_REQUIRE(grids[at] != nullptr, "match %d: grid %d is null", i, k);
+        CMX_REQUIRE(point_clouds_xyz[at] && num_points[at] >= 1 && num_points[at] <= (1 << 24),
+                    "match %d: bad point cloud %d", i, k);
+        int d = 0;
+        Grid3DBrick(grids[at], &P.pair[k].grid, &P.pair[k].resolution, &d);
+        CMX_REQUIRE(device < 0 || d == device, "match %d: the grids live on different devices", i);
+        device = d;
+        clouds.Add(i, point_clouds_xyz[at], num_points[at], [](int item, int there, int here) {
+          CMX_REQUIRE(false,
+                      "match %d: point cloud given by the pointer of an earlier cloud of the call, "
+                      "%d points there and %d here",
+                      item, there, here);
+        });
+      }
+    }
+    WorkspaceLease ws(device);
+    BlockLayout block;
+    const auto problems_in = block.Add<Ceres3DProblem>(num_matches);
+    const auto points_in = block.Add<float>(clouds.floats());
+    const auto zero_in = block.Add<uint16_t>(8);
+    const size_t upload_bytes = block.bytes;
+    const auto out_in = block.Add<double>(12 * static_cast<size_t>(num_matches));
+    char* h_block = static_cast<char*>(ws->pinned[0].Reserve(block.bytes));
+    char* d_block = static_cast<char*>(ws->dev[0].Reserve(block.bytes));
+    clouds.CopyTo(points_in(h_block), [](int n, const std::function<void(int)>& copy) {
+      ParallelFor(n, 8, copy);
+    });
+    std::memset(zero_in(h_block), 0, 16);
+    for (int i = 0; i < num_matches; ++i) {
+      Ceres3DProblem& P = problems[i];
+      for (int k = 0; k < pairs; ++k) {
+        const size_t at = static_cast<size_t>(i) * pairs + k;
+        if (P.pair[k].grid.cells == nullptr) {
+          // A HybridGrid nothing was inserted into: every lookup is value 0 (kMinProbability).
+          P.pair[k].grid = Brick{};
+          P.pair[k].grid.cells = zero_in(d_block);
+          P.pair[k].grid.nx = P.pair[k].grid.ny = P.pair[k].grid.nz = 1;
+        }
+        P.pair[k].n = num_points[at];
+        P.pair[k].xyz = points_in(d_block) + clouds.OffsetOf(point_clouds_xyz[at]);
+        P.pair[k].scaling =
+            options->occupied_space_weight[k] / std::sqrt(static_cast<double>(num_points[at]));
+      }
+      for (int a = 0; a < 3; ++a) {
+        P.target[a] = target_translations_xyz[3 * static_cast<size_t>(i) + a];
+        P.init[a] = initial_pose_estimates[i].t[a];
+      }
+      for (int a = 0; a < 4; ++a) P.init[3 + a] = initial_pose_estimates[i].q[a];
+      P.out = out_in(d_block) + 12 * static_cast<size_t>(i);
+    }
+    std::memcpy(problems_in(h_block), problems.data(), sizeof(Ceres3DProblem) * num_matches);
+    SmallCopyAsync(d_block, h_block, upload_bytes, /*to_device=*/true, ws->stream);
+    RecordEvent(ws->ev_begin, ws->stream);
+    Ceres3DKernel<<<num_matches, kCeres3DThreads, 0, ws->stream>>>(problems_in(d_block));
+    CMX_HIP(hipGetLastError());
+    RecordEvent(ws->ev_end, ws->stream);
+    SmallCopyAsync(out_in(h_block), out_in(d_block), 12 * sizeof(double) * num_matches,
+                   /*to_device=*/false, ws->stream);
+    CMX_HIP(hipStreamSynchronize(ws->stream));
+    for (int i = 0; i < num_matches; ++i)
+      WriteResult(out_in(h_block) + 12 * static_cast<size_t>(i), pose_estimates + i,
+                  summaries ? summaries + i : nullptr);
   });
 }
 

@@ -144,7 +144,8 @@ cmx_status Guard(F&& body) {
   X(rt3d_group_float)     /* 1: group centres in f32 instead of fixed point */                     \
   X(rt3d_cand_threads)    /* threads per candidate-pass workgroup */                               \
   X(rt3d_cand_rotations)  /* rotations per candidate work list */                                  \
-  X(rt3d_cand_tile_kb)    /* LDS tile capacity of the candidate pass */
+  X(rt3d_cand_tile_kb)    /* LDS tile capacity of the candidate pass */                            \
+  X(rt3d_batch_route)     /* cmx_rt3d_match_grid_batch: 1 every match with a finite cloud on the segmented route, 2 every match through the single path (0: by size) */
 struct DebugOptions {
 #define CMX_DEBUG_FIELD(name) int name = 0;
   CMX_DEBUG_OPTIONS(CMX_DEBUG_FIELD)

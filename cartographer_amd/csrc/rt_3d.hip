@@ -98,30 +98,30 @@ void FillBlockTables(Rt3DSearchSpace* S) {
       });
 }
 
-Rt3DSearchSpace BuildSearchSpace(const cmx_rt_options& options, float resolution,
-                                 const cmx_pose3d& initial_pose_estimate,
-                                 const float* point_cloud_xyz, int n) {
+}  // namespace
+
+Rt3DSearchSpace SearchSpaceOf(const Rt3DWindow& W, float resolution,
+                              const cmx_pose3d& initial_pose_estimate, int n) {
   Rt3DSearchSpace S;
   S.n = n;
   S.resolution = resolution;
-  S.L = static_cast<int>(std::lround(options.linear_search_window / resolution));
-  float max_scan_range = 3.f * resolution;
-  for (int i = 0; i < n; ++i) {
-    const h3::V3 p{point_cloud_xyz[3 * i], point_cloud_xyz[3 * i + 1], point_cloud_xyz[3 * i + 2]};
-    max_scan_range = std::max(h3::Norm(p), max_scan_range);
-  }
-  const float kSafetyMargin = 1.f - 1e-3f;
-  S.step = kSafetyMargin * std::acos(1.f - (resolution * (resolution * 1.f)) /
-                                               (2.f * (max_scan_range * (max_scan_range * 1.f))));
-  S.A = static_cast<int>(std::lround(options.angular_search_window / S.step));
-  CMX_REQUIRE(S.L >= 0 && S.L < 512 && S.A >= 0 && S.A < 64, "unsupported search window");
+  S.L = W.L; S.A = W.A; S.step = W.step;
   S.side_t = 2 * S.L + 1; S.side_r = 2 * S.A + 1;
-  S.T = 1ll * S.side_t * S.side_t * S.side_t;
-  S.R = 1ll * S.side_r * S.side_r * S.side_r;
-  S.num_candidates = S.T * S.R;
-  CMX_REQUIRE(S.num_candidates < (1ll << 31), "search window too large");
+  S.T = W.T; S.R = W.R; S.num_candidates = W.num_candidates;
   S.init = h3::FromPose(initial_pose_estimate);
   FillCandidateTables(&S);
+  return S;
+}
+
+namespace {
+
+Rt3DSearchSpace BuildSearchSpace(const cmx_rt_options& options, float resolution,
+                                 const cmx_pose3d& initial_pose_estimate,
+                                 const float* point_cloud_xyz, int n) {
+  const Rt3DWindow W =
+      Rt3DWindowOf(options, resolution, Rt3DScanRange(resolution, point_cloud_xyz, n));
+  CMX_REQUIRE(W.unsupported == nullptr, "%s", W.unsupported);
+  Rt3DSearchSpace S = SearchSpaceOf(W, resolution, initial_pose_estimate, n);
   FillBlockTables(&S);
   return S;
 }
@@ -257,8 +257,10 @@ void UploadTables(Workspace& ws, const Rt3DSearchSpace& S, const cmx_rt_options&
   P.wr = options.rotation_delta_cost_weight;
 }
 
+}  // namespace
+
 // Exact weighting and the strict '>' running maximum of :44-50.
-void PickBest(const Rt3DSearchSpace& S, const Rt3DParams& P, const Rt3DFinalists& fin,
+void PickBest(const Rt3DSearchSpace& S, double wt, double wr, const Rt3DFinalists& fin,
               float* score, cmx_pose3d* pose_estimate) {
   CMX_REQUIRE(!fin.index.empty(), "internal error: no candidate collected");
   float best_score = -1.f;
@@ -267,8 +269,8 @@ void PickBest(const Rt3DSearchSpace& S, const Rt3DParams& P, const Rt3DFinalists
     const long long c = fin.index[i];
     const long long t = c / S.R, r = c % S.R;
     float sc = fin.acc[i];
-    const double penalty = static_cast<double>(S.trans[t].w) * P.wt +
-                           static_cast<double>(S.angle[r]) * P.wr;
+    const double penalty = static_cast<double>(S.trans[t].w) * wt +
+                           static_cast<double>(S.angle[r]) * wr;
     sc *= std::exp(-(penalty * (penalty * 1.)));
     if (sc > best_score) { best_score = sc; best = c; }
   }
@@ -279,6 +281,8 @@ void PickBest(const Rt3DSearchSpace& S, const Rt3DParams& P, const Rt3DFinalists
   *pose_estimate = h3::ToPose(candidate);
   *score = best_score;
 }
+
+namespace {
 
 // Bounds search: the search space is covered by bounds -- the group bounds plus the candidates
 // scored one by one; `candidates_scored` stays the size of the search space (what the
@@ -299,6 +303,8 @@ cmx_match_stats StatsOf(Workspace& ws, const Rt3DSearchSpace& S, const Rt3DFinal
   if (fin.second_pairs_pass) st.expansion_ms += ElapsedMs(ws.ev_x0, ws.ev_x1);
   return st;
 }
+
+}  // namespace
 
 // RealTimeCorrelativeScanMatcher3D::Match: the bounds search where its limits hold (ModeOf) and
 // it narrows the search down, else the exhaustive search; the reference's weighting and
@@ -329,9 +335,11 @@ void Rt3DMatch(const cmx_rt_options* options, float grid_resolution, const cmx_v
   RecordEvent(ws->ev_begin, ws->stream);
   const bool done = mode.use_bulk && RunBoundsSearch(*ws, S, mode, geo, D, grid, &finalists);
   if (!done) RunExhaustiveSearch(*ws, S, D, &finalists);
-  PickBest(S, D.P, finalists, score, pose_estimate);
+  PickBest(S, D.P.wt, D.P.wr, finalists, score, pose_estimate);
   if (stats) *stats = StatsOf(*ws, S, finalists);
 }
+
+namespace {
 
 cmx_status Rt3DMatchImpl(const cmx_rt_options* options, float grid_resolution,
                          const cmx_voxel* voxels, int64_t num_voxels, const Brick* resident,

@@ -5,6 +5,8 @@
 //   rt_3d_bounds.hip  integer bounds: q bricks, the gather passes, selection, the stages of the
 //                     bounds search
 //   rt_3d_tiles.hip   the same integer sums on LDS tiles: bin sort, chunk boxes, tile kernel
+//   rt_3d_batch.hip   cmx_rt3d_match_grid_batch: the exhaustive search of many small matches in
+//                     one segmented launch, on the resident uint16 bricks (rt_3d_batch_plan.h)
 // (dense_brick_3d.hip, declared in scan_matching_3d.h, has the dense-brick helpers every 3D
 // matcher uses.)  Every unit owns its kernels and exposes the host functions declared here; no
 // kernel is launched from another file than the one that defines it.  The functions that cross
@@ -16,6 +18,7 @@
 #include <optional>
 #include <vector>
 
+#include "rt_3d_batch_plan.h"
 #include "rt_3d_device.h"
 
 namespace cmx {
@@ -245,6 +248,20 @@ inline Rt3DBulkParams CandidateParams(const Rt3DBoundsSearch& run) {
   }
   return p;
 }
+
+// ---- rt_3d.hip (what the batched call of rt_3d_batch.hip shares with the single one)
+// The search space of a window Rt3DWindowOf found supported, without the rotation blocks and
+// translation groups of the bounds search.
+Rt3DSearchSpace SearchSpaceOf(const Rt3DWindow& W, float resolution,
+                              const cmx_pose3d& initial_pose_estimate, int n);
+// Exact weighting and the strict '>' first-maximum rule over the finalists.
+void PickBest(const Rt3DSearchSpace& S, double wt, double wr, const Rt3DFinalists& fin,
+              float* score, cmx_pose3d* pose_estimate);
+// The single match: cmx_rt3d_match (a voxel list) and cmx_rt3d_match_grid (`resident`).
+void Rt3DMatch(const cmx_rt_options* options, float grid_resolution, const cmx_voxel* voxels,
+               int64_t num_voxels, const Brick* resident, const cmx_pose3d* initial_pose_estimate,
+               const float* point_cloud_xyz, int32_t num_points, int32_t device, float* score,
+               cmx_pose3d* pose_estimate, cmx_match_stats* stats);
 
 // ---- rt_3d_exact.hip
 // Padded f32 probability brick over the box D->brick names (no cells yet), filled with

@@ -67,6 +67,32 @@ class RealTimeCorrelativeScanMatcher3D:
         self.last_stats = stats.as_dict()
         return float(score.value), Rigid3d.from_c(pose)
 
+    def match_grid_batch(self, initial_poses, clouds, grids):
+        """``match_grid`` for many (pose, cloud, grid) triples in one call
+        (``cmx_rt3d_match_grid_batch``): entry i bit for bit what ``match_grid(initial_poses[i],
+        clouds[i], grids[i])`` returns.  The same array object at several places of ``clouds`` is
+        one cloud, staged once.  Returns ``(scores, poses, stats)``: float32 scores, a list of
+        Rigid3d, the call's summed stats."""
+        num = len(grids)
+        assert len(initial_poses) == num and len(clouds) == num
+        xyz, seen = [], {}
+        for c in clouds:
+            if id(c) not in seen:
+                seen[id(c)] = _cloud(c)[0]
+            xyz.append(seen[id(c)])
+        handles = (C.c_void_p * num)(*[g._h for g in grids])
+        pointers = (C.c_void_p * num)(*[a.ctypes.data for a in xyz])
+        counts = np.ascontiguousarray([a.shape[0] for a in xyz], np.int32)
+        inits = (Pose3d * num)(*[p.to_c() for p in initial_poses])
+        scores = np.zeros(num, np.float32)
+        poses = (Pose3d * num)()
+        stats = MatchStats()
+        check(_lib.lib().cmx_rt3d_match_grid_batch(
+            C.byref(self.options), handles, num, C.cast(inits, C.c_void_p), pointers,
+            counts.ctypes.data, scores.ctypes.data, C.cast(poses, C.c_void_p), C.byref(stats)))
+        self.last_stats = stats.as_dict()
+        return scores, [Rigid3d.from_c(p) for p in poses], self.last_stats
+
     def match(self, initial_pose_estimate, point_cloud, grid_resolution, grid_voxels):
         vox, nv = _voxels(grid_voxels)
         xyz, n = _cloud(point_cloud)
@@ -193,6 +219,36 @@ class CeresScanMatcher3D:
                                                  C.byref(summary)))
         return Rigid3d.from_c(pose), summary.as_dict()
 
+    def match_grids_batch(self, target_translations, initial_poses, point_clouds_and_grids):
+        """``match_grids`` (without intensity terms) for many trajectories in one upload, launch
+        and synchronisation (``cmx_ceres3d_match_grids_batch``): entry i is ``[(point_cloud, grid),
+        ...]`` with one pair per occupied_space_weight and is bit for bit what
+        ``match_grids(target_translations[i], initial_poses[i], point_clouds_and_grids[i])``
+        returns.  The same array object at several places is one cloud, staged once.  Returns
+        ``(poses, summaries)``."""
+        num, pairs = len(point_clouds_and_grids), self.options.num_pairs
+        assert len(target_translations) == num and len(initial_poses) == num
+        xyz, seen, handles = [], {}, []
+        for entry in point_clouds_and_grids:
+            assert len(entry) == pairs
+            for cloud, grid in entry:
+                if id(cloud) not in seen:
+                    seen[id(cloud)] = _cloud(cloud)[0]
+                xyz.append(seen[id(cloud)])
+                handles.append(grid._h)
+        handles = (C.c_void_p * (num * pairs))(*handles)
+        pointers = (C.c_void_p * (num * pairs))(*[a.ctypes.data for a in xyz])
+        counts = np.ascontiguousarray([a.shape[0] for a in xyz], np.int32)
+        targets = np.ascontiguousarray(target_translations, np.float64).reshape(num, 3)
+        inits = (Pose3d * num)(*[p.to_c() for p in initial_poses])
+        poses = (Pose3d * num)()
+        summaries = (CeresSummary * num)()
+        check(_lib.lib().cmx_ceres3d_match_grids_batch(
+            C.byref(self.options), num, targets.ctypes.data, C.cast(inits, C.c_void_p), handles,
+            pointers, counts.ctypes.data, C.cast(poses, C.c_void_p),
+            C.cast(summaries, C.c_void_p)))
+        return [Rigid3d.from_c(p) for p in poses], [s.as_dict() for s in summaries]
+
     def refine_batch(self, matchers, found, pose_estimates, constant_data):
         """ConstraintBuilder3D::ComputeConstraint's refinement of a node's search results
         (constraint_builder_3d.cc:263-276): entry i against the high- and low-resolution grids
@@ -228,6 +284,30 @@ class CeresScanMatcher3D:
             pointers, C.cast(poses_out, C.c_void_p), C.cast(summaries, C.c_void_p)))
         del keep
         return [Rigid3d.from_c(p) for p in poses_out], [s.as_dict() for s in summaries]
+
+
+def rt3d_batch_plan(matcher, resolutions, num_points, max_point_norms):
+    """Where the matches of ``matcher.match_grid_batch`` would run
+    (``cmx_debug_rt3d_batch_plan``; needs no grid and no device): per match a dict with the search
+    window in steps ``L``, ``A``, its ``T`` translations and ``R`` rotations, the ``route`` (0: the
+    segmented exhaustive launches, 1: the single path), the launch ``set`` and the match's
+    ``first_block`` and ``blocks`` in it.  ``max_point_norms[i]``: the largest norm of a point of
+    cloud i (NaN or infinity: a cloud with a non-finite coordinate)."""
+    num = len(resolutions)
+    res = np.ascontiguousarray(resolutions, np.float32)
+    counts = np.ascontiguousarray(num_points, np.int32)
+    norms = np.ascontiguousarray(max_point_norms, np.float32)
+    assert counts.shape[0] == num and norms.shape[0] == num
+    plans = (_lib.DebugRt3DMatchPlan * num)()
+    check(_lib.lib().cmx_debug_rt3d_batch_plan(C.byref(matcher.options), num, res.ctypes.data,
+                                               counts.ctypes.data, norms.ctypes.data, plans))
+    return [{k: getattr(p, k) for k, _ in p._fields_} for p in plans]
+
+
+def ceres_match_grids_batch(matcher, target_translations, initial_poses, point_clouds_and_grids):
+    """``matcher.match_grids_batch(...)``: the refinement that follows
+    ``RealTimeCorrelativeScanMatcher3D.match_grid_batch`` for a fleet, one call."""
+    return matcher.match_grids_batch(target_translations, initial_poses, point_clouds_and_grids)
 
 
 def _node_data_pointers(constant_datas):

@@ -29,6 +29,10 @@
  *                                  CeresScanMatcher3D::Match, SM3/ceres_scan_matcher_3d.cc:90-156
  *   cmx_rt3d_match                 RealTimeCorrelativeScanMatcher3D::Match
  *                                  SM3/real_time_correlative_scan_matcher_3d.h:47-50, .cc:34-53
+ *   cmx_rt3d_match_grid_batch, cmx_ceres3d_match_grids_batch
+ *                                  LocalTrajectoryBuilder3D::ScanMatch's two matchers
+ *                                  (mapping/internal/3d/local_trajectory_builder_3d.cc:96-123) for
+ *                                  many trajectories in one call each, on resident grids
  *   cmx_fast3d_*                   FastCorrelativeScanMatcher3D ctor / Match / MatchFullSubmap
  *                                  SM3/fast_correlative_scan_matcher_3d.h:75-101, .cc:112-170
  *   cmx_fast3d_create_batch        the same ctor for many submaps in one call (the
@@ -820,6 +824,27 @@ cmx_status cmx_rt3d_match_grid(const cmx_rt_options* options, const cmx_grid3d* 
                                const float* point_cloud_xyz, int32_t num_points, float* score,
                                cmx_pose3d* pose_estimate, cmx_match_stats* stats);
 
+/* `num_matches` independent cmx_rt3d_match_grid calls (one per trajectory / robot: scan i against
+ * grid i around pose i) in one call; scores[i] and pose_estimates[i] are bit for bit what the
+ * single call returns for entry i.  One set of options for the call; grids of different
+ * resolutions may share it, a grid may appear in several matches, a grid nothing was inserted into
+ * is valid.  Equal point_clouds_xyz pointers are one cloud, staged once (their num_points must
+ * agree).  The grids are read where they lie and nothing derived from them is kept between calls.
+ * Small searches (the 0.15 m / 1 degree window of trajectory_builder_3d.lua: 42 875 candidates, a
+ * few hundred points) share two launches, one upload and one synchronisation; larger ones run as
+ * the single call does, one after the other inside the call.  Every argument check, and the
+ * limits of the search window (fewer than 512 linear and 64 angular steps, fewer than 2^31
+ * candidates), are made for every match before the device is touched: CMX_INVALID_ARGUMENT names
+ * "match <index>" in cmx_last_error and no output is written.  `stats` (may be NULL) is one struct
+ * for the call: candidates_scored, coarse_candidates, num_scans and nodes_expanded summed over the
+ * matches, device_ms the span of the shared launches plus the device time of the other matches. */
+cmx_status cmx_rt3d_match_grid_batch(const cmx_rt_options* options,
+                                     const cmx_grid3d* const* grids, int32_t num_matches,
+                                     const cmx_pose3d* initial_pose_estimates,
+                                     const float* const* point_clouds_xyz,
+                                     const int32_t* num_points, float* scores,
+                                     cmx_pose3d* pose_estimates, cmx_match_stats* stats);
+
 /* CeresScanMatcher3D::Match as LocalTrajectoryBuilder3D::ScanMatch calls it
  * (mapping/internal/3d/local_trajectory_builder_3d.cc:96-123) against the ACTIVE submap: pair k is
  * (point_clouds_xyz[k], num_points[k]) with the resident HybridGrid grids[k] (its resolution is
@@ -832,6 +857,25 @@ cmx_status cmx_ceres3d_match_grids(const cmx_ceres3d_options* options,
                                    const float* const* point_clouds_xyz,
                                    const int32_t* num_points, cmx_pose3d* pose_estimate,
                                    cmx_ceres_summary* summary);
+
+/* `num_matches` independent cmx_ceres3d_match_grids calls (the refinement that follows
+ * cmx_rt3d_match_grid_batch for a fleet) in one upload, one launch and one synchronisation; entry
+ * i is bit for bit the single call on target_translations_xyz + 3 i, initial_pose_estimates[i] and
+ * the options->num_pairs pairs grids / point_clouds_xyz / num_points [i * num_pairs ..].  The
+ * target translation is an argument of its own: after a real-time match it differs from the
+ * initial pose's (local_trajectory_builder_3d.cc:96-123).  Equal cloud pointers are one cloud,
+ * staged once (their num_points must agree); all grids live on one device; a grid nothing was
+ * inserted into is valid.  Checks are made before the device is touched and name "match <index>".
+ * There is no batch form with intensity terms: cmx_ceres3d_match_grids_intensity stays a single
+ * call.  `summaries` [num_matches] may be NULL. */
+cmx_status cmx_ceres3d_match_grids_batch(const cmx_ceres3d_options* options, int32_t num_matches,
+                                         const double* target_translations_xyz,
+                                         const cmx_pose3d* initial_pose_estimates,
+                                         const cmx_grid3d* const* grids,
+                                         const float* const* point_clouds_xyz,
+                                         const int32_t* num_points,
+                                         cmx_pose3d* pose_estimates,
+                                         cmx_ceres_summary* summaries);
 
 /* ---- IntensityHybridGrid in HBM -------------------------------------------
  * mapping/3d/hybrid_grid.h:543-571: AverageIntensityData {sum, count} per voxel.

@@ -161,6 +161,31 @@ cmx_status cmx_debug_filter_batch_plan(const cmx_filter_job* jobs, int32_t num_j
                                        cmx_debug_filter_job_plan* job_plans,
                                        cmx_debug_filter_call_plan* call_plan);
 
+/* The plan of one cmx_rt3d_match_grid_batch call from the options and, per match, the resolution
+ * of its grid, its number of points and the largest norm of a point (a NaN or infinity stands for
+ * a cloud with a non-finite coordinate, planned with the window of the smallest range, three
+ * cells): the search window in steps (L, A) with its T = (2L + 1)^3
+ * translations and R = (2A + 1)^3 rotations, the route (0: the segmented exhaustive launches, 1:
+ * the single path), and for the segmented route the set of launches, the first block and the
+ * number of blocks the match has in either launch of its set (single path: set -1, no blocks).
+ * The switch rt3d_batch_route applies as it does to the call.  The launch path asks the same
+ * functions; this entry needs no grid and no device.  A window beyond the limits of the library
+ * (L < 512, A < 64, fewer than 2^31 candidates) is CMX_INVALID_ARGUMENT naming the match, as in
+ * the call itself. */
+typedef struct cmx_debug_rt3d_match_plan {
+  int32_t L, A;
+  int64_t T, R;
+  int32_t route;
+  int32_t set;
+  int32_t first_block;
+  int32_t blocks;
+} cmx_debug_rt3d_match_plan;
+
+cmx_status cmx_debug_rt3d_batch_plan(const cmx_rt_options* options, int32_t num_matches,
+                                     const float* resolutions, const int32_t* num_points,
+                                     const float* max_point_norms,
+                                     cmx_debug_rt3d_match_plan* plans);
+
 #ifdef __cplusplus
 }
 #endif
