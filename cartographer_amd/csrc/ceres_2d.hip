@@ -19,7 +19,8 @@
 // from the grid in HBM / L2), two Catmull-Rom passes, the residual and its three partials,
 // accumulated as cost, J^T r and J^T J in f64 (ten numbers per thread), reduced across the
 // wavefront with DPP-free shuffles and across the four wavefronts through LDS in a FIXED
-// order -- results do not depend on scheduling.  Thread 0 then runs the trust-region logic.
+// order -- results do not depend on scheduling.  The trust-region logic is the loop shared with
+// the 3D kernel (ceres_trust_region.h), its state replicated in every thread.
 // Residual + Jacobian are evaluated together at every candidate (the Jacobian of a rejected
 // candidate is wasted; evaluating it separately would be a second pass over the points).
 //
@@ -39,6 +40,7 @@
 #include <map>
 #include <vector>
 
+#include "ceres_trust_region.h"
 #include "scan_matching_2d.h"
 
 struct cmx_grid2d;   // grid_2d.hip
@@ -53,7 +55,6 @@ void Tsdf2DDevicePlanes(const cmx_tsdf2d* grid, cmx_grid2d_limits* limits, const
 namespace cmx {
 namespace {
 
-constexpr int kCeresThreads = 256;
 constexpr int kPadding = INT_MAX / 4;   // occupied_space_cost_function_2d.cc:78
 
 struct Ceres2DProblem {
@@ -193,12 +194,6 @@ struct Sums {
   double v[kCount];
 };
 
-__device__ __forceinline__ double WaveSumF64(double v) {
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
-
 // Residual blocks at `x`: leaves 1/2 |r|^2, J^T r and J^T J (valid in every thread).  False when
 // the cost function fails (a TSDF with S == 0); the outputs are then undefined.
 template <bool kTsdf>
@@ -251,18 +246,8 @@ __device__ bool Evaluate(const Ceres2DProblem& P, const double x[3],
       acc.v[7] += j1 * j1; acc.v[8] += j1 * j2; acc.v[9] += j2 * j2;
     }
   }
-  const int wave = threadIdx.x >> 6;
-#pragma unroll
-  for (int k = 0; k < kCount; ++k) {
-    const double t = WaveSumF64(acc.v[k]);
-    if ((threadIdx.x & 63) == 0) scratch[wave][k] = t;
-  }
-  __syncthreads();
   double total[kCount];
-#pragma unroll
-  for (int k = 0; k < kCount; ++k)
-    total[k] = ((scratch[0][k] + scratch[1][k]) + scratch[2][k]) + scratch[3][k];
-  __syncthreads();
+  BlockSumF64<kCount>(acc.v, scratch, total);
   if constexpr (kTsdf) {
     const double S = total[10];
     if (S == 0.) return false;                      // tsdf_match_cost_function_2d.cc:61
@@ -294,39 +279,37 @@ __device__ bool Evaluate(const Ceres2DProblem& P, const double x[3],
   return true;
 }
 
-// Cholesky solve of the symmetric positive definite 3 x 3 system; false if not SPD.
-__device__ bool SolveSpd3(const double A[3][3], const double b[3], double x[3]) {
-  double L[3][3] = {{0., 0., 0.}, {0., 0., 0.}, {0., 0., 0.}};
-  for (int i = 0; i < 3; ++i) {
-    for (int j = 0; j <= i; ++j) {
-      double sum = A[i][j];
-      for (int k = 0; k < j; ++k) sum -= L[i][k] * L[j][k];
-      if (i == j) {
-        if (!(sum > 0.)) return false;
-        L[i][i] = sqrt(sum);
-      } else {
-        L[i][j] = sum / L[j][j];
-      }
-    }
-  }
-  double y[3];
-  for (int i = 0; i < 3; ++i) {
-    double sum = b[i];
-    for (int k = 0; k < i; ++k) sum -= L[i][k] * y[k];
-    y[i] = sum / L[i][i];
-  }
-  for (int i = 2; i >= 0; --i) {
-    double sum = y[i];
-    for (int k = i + 1; k < 3; ++k) sum -= L[k][i] * x[k];
-    x[i] = sum / L[i][i];
-  }
-  return isfinite(x[0]) && isfinite(x[1]) && isfinite(x[2]);
-}
+// What MinimizeTrustRegion asks of CeresScanMatcher2D's problem: three unknowns without a local
+// parameterization.
+template <bool kTsdf>
+struct Pose2DProblem {
+  static constexpr int kAmbient = 3, kMaxLocal = 3;
+  // Only a TSDF's evaluation fails (S == 0); on a probability grid Evaluate returns true and the
+  // compiler folds the branches away.
+  static constexpr bool kEvaluationCanFail = true;
+  const Ceres2DProblem& P;
+  double (*scratch)[Sums<kTsdf>::kCount];
 
-// The trust-region loop of oracle/oracle_ceres_2d.cc (Ceres: trust_region_minimizer.cc,
-// levenberg_marquardt_strategy.cc, trust_region_step_evaluator.cc), statement for statement.
-// Every thread carries the (identical) minimizer state: no broadcast is needed, the block
-// only meets inside Evaluate.
+  __device__ __forceinline__ int LocalSize() const { return 3; }
+  __device__ __forceinline__ bool Evaluate(const double* x, TrEvaluation<3>* e) {
+    return cmx::Evaluate<kTsdf>(P, x, scratch, &e->cost, e->g, e->H);
+  }
+  __device__ __forceinline__ void Plus(const double* x, const double* delta, double* out) const {
+    for (int a = 0; a < 3; ++a) out[a] = x[a] + delta[a];
+  }
+  __device__ __forceinline__ double GradientMaxNorm(const double*, const TrEvaluation<3>& e) const {
+    return fmax(fabs(e.g[0]), fmax(fabs(e.g[1]), fabs(e.g[2])));
+  }
+  __device__ __forceinline__ double StepNorm(const double*, const double*, const double* delta) const {
+    return sqrt(delta[0] * delta[0] + delta[1] * delta[1] + delta[2] * delta[2]);
+  }
+  // The radius update's (2 rho - 1)^3 as a product (oracle_ceres_2d.cc takes std::pow; the two
+  // agree up to rounding, and the parity tests pin this form).
+  __device__ __forceinline__ double Cube(double t) const { return t * t * t; }
+};
+
+// One workgroup per problem: the prologue of the entry points (nothing to refine, a failed
+// initial evaluation), then the shared trust-region loop.
 template <bool kTsdf>
 __global__ void __launch_bounds__(kCeresThreads)
 Ceres2DKernel(const Ceres2DProblem* __restrict__ problems) {
@@ -339,15 +322,10 @@ Ceres2DKernel(const Ceres2DProblem* __restrict__ problems) {
     }
     return;
   }
-  const double kFunctionTolerance = 1e-6, kGradientTolerance = 1e-10, kParameterTolerance = 1e-8;
-  const double kMinRelativeDecrease = 1e-3, kMinLmDiagonal = 1e-6, kMaxLmDiagonal = 1e32;
-  const double kMaxRadius = 1e16, kMinRadius = 1e-32;
-  const int kMaxConsecutiveInvalidSteps = 5;
-  const int max_consecutive_nonmonotonic_steps = P.use_nonmonotonic_steps ? 5 : 0;
-
-  double x[3] = {P.init[0], P.init[1], P.init[2]};
-  double x_cost, g[3], H[3][3];
-  if (!Evaluate<kTsdf>(P, x, scratch, &x_cost, g, H)) {
+  Pose2DProblem<kTsdf> problem{P, scratch};
+  TrResult<3> r;
+  if (!MinimizeTrustRegion(problem, P.init, P.use_nonmonotonic_steps != 0, P.max_num_iterations,
+                           &r)) {
     // The initial evaluation failed: FAILURE, the pose untouched, and the summary fields keep
     // ceres::Solver::Summary's initial values.
     if (threadIdx.x == 0) {
@@ -356,133 +334,10 @@ Ceres2DKernel(const Ceres2DProblem* __restrict__ problems) {
     }
     return;
   }
-  const double initial_cost = x_cost;
-  double scale[3];
-  for (int a = 0; a < 3; ++a) scale[a] = 1. / (1. + sqrt(H[a][a]));
-  double x_norm = sqrt(x[0] * x[0] + x[1] * x[1] + x[2] * x[2]);
-  double radius = 1e4, decrease_factor = 2.;
-  bool reuse_diagonal = false;
-  double diagonal[3] = {0., 0., 0.};
-  double minimum_cost = x_cost, current_cost = x_cost, reference_cost = x_cost,
-         candidate_cost_eval = x_cost;
-  double accumulated_reference_model_cost_change = 0., accumulated_candidate_model_cost_change = 0.;
-  int num_consecutive_nonmonotonic_steps = 0, num_consecutive_invalid_steps = 0;
-  double best_x[3] = {x[0], x[1], x[2]};
-  double best_cost = x_cost;
-  int successful = 0, unsuccessful = 0;
-  int termination = 1;   // NO_CONVERGENCE
-  const auto gradient_max_norm = [&]() {
-    return fmax(fabs(g[0]), fmax(fabs(g[1]), fabs(g[2])));
-  };
-  bool done = gradient_max_norm() <= kGradientTolerance;
-  if (done) termination = 0;
-  bool last_step_successful = false;
-  for (int iteration = 1; !done; ++iteration) {
-    if (iteration - 1 >= P.max_num_iterations) { termination = 1; break; }
-    if (last_step_successful && gradient_max_norm() <= kGradientTolerance) { termination = 0; break; }
-    if (radius < kMinRadius) { termination = 0; break; }
-    last_step_successful = false;
-
-    double Hs[3][3], gs[3];
-    for (int a = 0; a < 3; ++a) {
-      gs[a] = g[a] * scale[a];
-      for (int b = 0; b < 3; ++b) Hs[a][b] = H[a][b] * scale[a] * scale[b];
-    }
-    if (!reuse_diagonal) {
-      for (int a = 0; a < 3; ++a) diagonal[a] = fmin(fmax(Hs[a][a], kMinLmDiagonal), kMaxLmDiagonal);
-    }
-    double A[3][3], step[3];
-    for (int a = 0; a < 3; ++a)
-      for (int b = 0; b < 3; ++b) A[a][b] = Hs[a][b] + (a == b ? diagonal[a] / radius : 0.);
-    const bool solved = SolveSpd3(A, gs, step);
-    for (int a = 0; a < 3; ++a) step[a] = -step[a];
-    reuse_diagonal = true;
-    double model_cost_change = 0.;
-    if (solved) {
-      double sg = 0., sHs = 0.;
-      for (int a = 0; a < 3; ++a) {
-        sg += step[a] * gs[a];
-        for (int b = 0; b < 3; ++b) sHs += step[a] * Hs[a][b] * step[b];
-      }
-      model_cost_change = -(sg + 0.5 * sHs);
-    }
-    if (!solved || !(model_cost_change > 0.)) {
-      if (++num_consecutive_invalid_steps >= kMaxConsecutiveInvalidSteps) { termination = 2; break; }
-      radius *= 0.5;
-      reuse_diagonal = false;
-      ++unsuccessful;
-      continue;
-    }
-    num_consecutive_invalid_steps = 0;
-    double delta[3], candidate[3];
-    for (int a = 0; a < 3; ++a) {
-      delta[a] = step[a] * scale[a];
-      candidate[a] = x[a] + delta[a];
-    }
-    double candidate_cost, cg[3], cH[3][3];
-    if (!Evaluate<kTsdf>(P, candidate, scratch, &candidate_cost, cg, cH)) candidate_cost = DBL_MAX;
-
-    const double step_norm = sqrt(delta[0] * delta[0] + delta[1] * delta[1] + delta[2] * delta[2]);
-    if (step_norm <= kParameterTolerance * (x_norm + kParameterTolerance)) { termination = 0; break; }
-    const double cost_change = x_cost - candidate_cost;
-    if (fabs(cost_change) <= kFunctionTolerance * x_cost) { termination = 0; break; }
-    const double relative_decrease_now = (current_cost - candidate_cost) / model_cost_change;
-    const double historical_relative_decrease =
-        (reference_cost - candidate_cost) /
-        (accumulated_reference_model_cost_change + model_cost_change);
-    // A failed candidate evaluation is never a successful step (StepQuality: lowest()).
-    const double relative_decrease = candidate_cost >= DBL_MAX
-                                         ? -DBL_MAX
-                                         : fmax(relative_decrease_now, historical_relative_decrease);
-    if (relative_decrease > kMinRelativeDecrease) {
-      for (int a = 0; a < 3; ++a) {
-        x[a] = candidate[a];
-        g[a] = cg[a];
-        for (int b = 0; b < 3; ++b) H[a][b] = cH[a][b];
-      }
-      x_norm = sqrt(x[0] * x[0] + x[1] * x[1] + x[2] * x[2]);
-      x_cost = candidate_cost;
-      last_step_successful = true;
-      ++successful;
-      if (x_cost < best_cost) {
-        best_cost = x_cost;
-        for (int a = 0; a < 3; ++a) best_x[a] = x[a];
-      }
-      const double t = 2. * relative_decrease - 1.;
-      radius = radius / fmax(1. / 3., 1. - t * t * t);
-      radius = fmin(kMaxRadius, radius);
-      decrease_factor = 2.;
-      reuse_diagonal = false;
-      current_cost = candidate_cost;
-      accumulated_candidate_model_cost_change += model_cost_change;
-      accumulated_reference_model_cost_change += model_cost_change;
-      if (candidate_cost < minimum_cost) {
-        minimum_cost = candidate_cost;
-        num_consecutive_nonmonotonic_steps = 0;
-        candidate_cost_eval = candidate_cost;
-        accumulated_candidate_model_cost_change = 0.;
-      } else {
-        ++num_consecutive_nonmonotonic_steps;
-        if (candidate_cost > candidate_cost_eval) {
-          candidate_cost_eval = candidate_cost;
-          accumulated_candidate_model_cost_change = 0.;
-        }
-      }
-      if (num_consecutive_nonmonotonic_steps == max_consecutive_nonmonotonic_steps) {
-        reference_cost = candidate_cost_eval;
-        accumulated_reference_model_cost_change = accumulated_candidate_model_cost_change;
-      }
-    } else {
-      radius = radius / decrease_factor;
-      decrease_factor *= 2.;
-      reuse_diagonal = true;
-      ++unsuccessful;
-    }
-  }
   if (threadIdx.x == 0) {
-    P.out[0] = best_x[0]; P.out[1] = best_x[1]; P.out[2] = best_x[2];
-    P.out[3] = initial_cost; P.out[4] = best_cost;
-    P.out[5] = successful; P.out[6] = unsuccessful; P.out[7] = termination;
+    P.out[0] = r.x[0]; P.out[1] = r.x[1]; P.out[2] = r.x[2];
+    P.out[3] = r.initial_cost; P.out[4] = r.final_cost;
+    P.out[5] = r.successful; P.out[6] = r.unsuccessful; P.out[7] = r.termination;
   }
 }
 
@@ -501,17 +356,8 @@ TsdfResidualsKernel(const Ceres2DProblem* __restrict__ problem) {
     TsdfPoint(P, x, c, s, ns, i, &u, &w);
     acc[0] += w.a; acc[1] += w.v[0]; acc[2] += w.v[1]; acc[3] += w.v[2];
   }
-  const int wave = threadIdx.x >> 6;
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    const double t = WaveSumF64(acc[k]);
-    if ((threadIdx.x & 63) == 0) scratch[wave][k] = t;
-  }
-  __syncthreads();
   double total[4];
-#pragma unroll
-  for (int k = 0; k < 4; ++k)
-    total[k] = ((scratch[0][k] + scratch[1][k]) + scratch[2][k]) + scratch[3][k];
+  BlockSumF64<4>(acc, scratch, total);
   // out: [0] valid, [1, 1 + n) residuals, [1 + n, 1 + 4n) Jacobian rows.
   if (threadIdx.x == 0) P.out[0] = total[0] == 0. ? 0. : 1.;
   if (total[0] == 0.) return;

@@ -24,13 +24,13 @@
 // thread carries the (identical) minimizer state.
 #include <cmath>
 
+#include "ceres_trust_region.h"
 #include "cmx_batch.h"
 #include "scan_matching_3d.h"
 
 namespace cmx {
 namespace {
 
-constexpr int kCeres3DThreads = 256;
 constexpr int kMaxLocal = 6;
 constexpr int kMaxPairs = 3;
 constexpr int kNumSums = 1 + kMaxLocal + kMaxLocal * (kMaxLocal + 1) / 2;   // 28
@@ -138,17 +138,7 @@ __device__ __forceinline__ void QuatProduct(const double z[4], const double w[4]
   zw[3] = z[0] * w[3] + z[1] * w[2] - z[2] * w[1] + z[3] * w[0];
 }
 
-__device__ __forceinline__ double WaveSumF64(double v) {
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
-
-struct Eval3D {
-  double cost;
-  double g[kMaxLocal];
-  double H[kMaxLocal][kMaxLocal];
-};
+using Eval3D = TrEvaluation<kMaxLocal>;
 
 // Local (tangent-space) row of one residual: J_local = J_ambient * PlusJacobian.
 __device__ __forceinline__ void Accumulate(double r, const double local[kMaxLocal], int K,
@@ -224,29 +214,15 @@ __device__ void Evaluate3D(const Ceres3DProblem& P, const double x[7], int K,
     }
     Accumulate(r, local, K, acc);
   };
-  const int wave = threadIdx.x >> 6;
-  // Block-wide sums of a thread-local accumulator, in a FIXED order (valid in every thread).
-  const auto reduce = [&](const double* acc, double* total) {
-#pragma unroll
-    for (int k = 0; k < kNumSums; ++k) {
-      const double t = WaveSumF64(acc[k]);
-      if ((threadIdx.x & 63) == 0) scratch[wave][k] = t;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < kNumSums; ++k)
-      total[k] = ((scratch[0][k] + scratch[1][k]) + scratch[2][k]) + scratch[3][k];
-    __syncthreads();
-  };
   double acc[kNumSums];
 #pragma unroll
   for (int k = 0; k < kNumSums; ++k) acc[k] = 0.;
   for (int pi = 0; pi < P.num_pairs; ++pi) {
     const Ceres3DPair& pr = P.pair[pi];
-    for (int i = threadIdx.x; i < pr.n; i += kCeres3DThreads) point_row(pr, i, false, acc);
+    for (int i = threadIdx.x; i < pr.n; i += kCeresThreads) point_row(pr, i, false, acc);
   }
   double total[kNumSums];
-  reduce(acc, total);
+  BlockSumF64<kNumSums>(acc, scratch, total);
   // Intensity blocks: ceres::HuberLoss acts on the BLOCK's squared norm s (residual_block.cc,
   // corrector.cc with rho'' <= 0): cost 1/2 rho(s), J^T r and J^T J times rho'(s).
   for (int pi = 0; pi < P.num_pairs; ++pi) {
@@ -254,10 +230,10 @@ __device__ void Evaluate3D(const Ceres3DProblem& P, const double x[7], int K,
     if (!pr.has_intensity) continue;                          // (uniform)
 #pragma unroll
     for (int k = 0; k < kNumSums; ++k) acc[k] = 0.;
-    for (int i = threadIdx.x; i < pr.n; i += kCeres3DThreads)
+    for (int i = threadIdx.x; i < pr.n; i += kCeresThreads)
       if (!(pr.intensities[i] > pr.intensity_threshold)) point_row(pr, i, true, acc);
     double block[kNumSums];
-    reduce(acc, block);
+    BlockSumF64<kNumSums>(acc, scratch, block);
     const double s = block[0], b_ = pr.huber_a * pr.huber_a;
     double rho0 = s, rho1 = 1.;
     if (s > b_) {
@@ -299,38 +275,6 @@ __device__ void Evaluate3D(const Ceres3DProblem& P, const double x[7], int K,
   }
 }
 
-__device__ bool SolveSpd(int k, const double A[kMaxLocal][kMaxLocal], const double* b, double* x) {
-  double L[kMaxLocal][kMaxLocal];
-  for (int i = 0; i < kMaxLocal; ++i)
-    for (int j = 0; j < kMaxLocal; ++j) L[i][j] = 0.;
-  for (int i = 0; i < k; ++i) {
-    for (int j = 0; j <= i; ++j) {
-      double sum = A[i][j];
-      for (int m = 0; m < j; ++m) sum -= L[i][m] * L[j][m];
-      if (i == j) {
-        if (!(sum > 0.)) return false;
-        L[i][i] = sqrt(sum);
-      } else {
-        L[i][j] = sum / L[j][j];
-      }
-    }
-  }
-  double y[kMaxLocal];
-  for (int i = 0; i < k; ++i) {
-    double sum = b[i];
-    for (int m = 0; m < i; ++m) sum -= L[i][m] * y[m];
-    y[i] = sum / L[i][i];
-  }
-  for (int i = k - 1; i >= 0; --i) {
-    double sum = y[i];
-    for (int m = i + 1; m < k; ++m) sum -= L[m][i] * x[m];
-    x[i] = sum / L[i][i];
-  }
-  for (int i = 0; i < k; ++i)
-    if (!isfinite(x[i])) return false;
-  return true;
-}
-
 // QuaternionParameterization::Plus / YawOnlyQuaternionPlus.
 __device__ void PlusRotation(bool yaw_only, const double q[4], const double* delta, double out[4]) {
   double q_delta[4];
@@ -350,34 +294,28 @@ __device__ void PlusRotation(bool yaw_only, const double q[4], const double* del
   QuatProduct(q_delta, q, out);
 }
 
-// The trust-region loop of oracle/oracle_ceres_3d.cc, statement for statement.
-__global__ void __launch_bounds__(kCeres3DThreads)
-Ceres3DKernel(const Ceres3DProblem* __restrict__ problems) {
-  const Ceres3DProblem& P = problems[blockIdx.x];
-  __shared__ double scratch[4][kNumSums];
-  const double kFunctionTolerance = 1e-6, kGradientTolerance = 1e-10, kParameterTolerance = 1e-8;
-  const double kMinRelativeDecrease = 1e-3, kMinLmDiagonal = 1e-6, kMaxLmDiagonal = 1e32;
-  const double kMaxRadius = 1e16, kMinRadius = 1e-32;
-  const int kMaxConsecutiveInvalidSteps = 5;
-  const int max_consecutive_nonmonotonic_steps = P.use_nonmonotonic_steps ? 5 : 0;
-  const bool yaw_only = P.yaw_only != 0;
-  const int K = 3 + (yaw_only ? 1 : 3);
+// What MinimizeTrustRegion asks of CeresScanMatcher3D's problem: x = (t, q) with the rotation's
+// local parameterization, K = 6 or (yaw only) 4 local unknowns.
+struct Pose3DProblem {
+  static constexpr int kAmbient = 7, kMaxLocal = cmx::kMaxLocal;
+  static constexpr bool kEvaluationCanFail = false;
+  const Ceres3DProblem& P;
+  double (*scratch)[kNumSums];
+  bool yaw_only;
+  int K;
 
-  double x[7];
-  for (int a = 0; a < 7; ++a) x[a] = P.init[a];
-  Eval3D at_x;
-  Evaluate3D(P, x, K, scratch, &at_x);
-  const double initial_cost = at_x.cost;
-  double scale[kMaxLocal];
-  for (int a = 0; a < K; ++a) scale[a] = 1. / (1. + sqrt(at_x.H[a][a]));
-  const auto norm7 = [](const double* v) {
-    double s = 0.;
-    for (int a = 0; a < 7; ++a) s += v[a] * v[a];
-    return sqrt(s);
-  };
+  __device__ __forceinline__ int LocalSize() const { return K; }
+  __device__ __forceinline__ bool Evaluate(const double* x, Eval3D* e) {
+    Evaluate3D(P, x, K, scratch, e);
+    return true;
+  }
+  __device__ __forceinline__ void Plus(const double* x, const double* delta, double* out) const {
+    for (int a = 0; a < 3; ++a) out[a] = x[a] + delta[a];
+    PlusRotation(yaw_only, x + 3, delta + 3, out + 3);
+  }
   // TrustRegionMinimizer::ComputeGradientMaxNorm: |x - Plus(x, -g)|_inf over the ambient
-  // coordinates (`x` is always the point the evaluation was taken at).
-  const auto gradient_max_norm = [K, yaw_only, &x](const Eval3D& e) {
+  // coordinates (`x` is the point the evaluation was taken at).
+  __device__ __forceinline__ double GradientMaxNorm(const double* x, const Eval3D& e) const {
     double m = 0.;
     for (int a = 0; a < 3; ++a) m = fmax(m, fabs(e.g[a]));
     double negative[3] = {0., 0., 0.}, projected[4];
@@ -385,130 +323,31 @@ Ceres3DKernel(const Ceres3DProblem* __restrict__ problems) {
     PlusRotation(yaw_only, x + 3, negative, projected);
     for (int a = 0; a < 4; ++a) m = fmax(m, fabs(x[3 + a] - projected[a]));
     return m;
-  };
-  double x_cost = at_x.cost, x_norm = norm7(x);
-  double radius = 1e4, decrease_factor = 2.;
-  bool reuse_diagonal = false;
-  double diagonal[kMaxLocal] = {0., 0., 0., 0., 0., 0.};
-  double minimum_cost = x_cost, current_cost = x_cost, reference_cost = x_cost,
-         candidate_cost_eval = x_cost;
-  double accumulated_reference_model_cost_change = 0., accumulated_candidate_model_cost_change = 0.;
-  int num_consecutive_nonmonotonic_steps = 0, num_consecutive_invalid_steps = 0;
-  double best_x[7];
-  for (int a = 0; a < 7; ++a) best_x[a] = x[a];
-  double best_cost = x_cost;
-  int successful = 0, unsuccessful = 0;
-  int termination = 1;   // NO_CONVERGENCE
-  bool done = gradient_max_norm(at_x) <= kGradientTolerance;
-  if (done) termination = 0;
-  bool last_step_successful = false;
-  for (int iteration = 1; !done; ++iteration) {
-    if (iteration - 1 >= P.max_num_iterations) { termination = 1; break; }
-    if (last_step_successful && gradient_max_norm(at_x) <= kGradientTolerance) {
-      termination = 0;
-      break;
-    }
-    if (radius < kMinRadius) { termination = 0; break; }
-    last_step_successful = false;
-
-    double Hs[kMaxLocal][kMaxLocal], gs[kMaxLocal];
-    for (int a = 0; a < K; ++a) {
-      gs[a] = at_x.g[a] * scale[a];
-      for (int b = 0; b < K; ++b) Hs[a][b] = at_x.H[a][b] * scale[a] * scale[b];
-    }
-    if (!reuse_diagonal)
-      for (int a = 0; a < K; ++a) diagonal[a] = fmin(fmax(Hs[a][a], kMinLmDiagonal), kMaxLmDiagonal);
-    double A[kMaxLocal][kMaxLocal], step[kMaxLocal];
-    for (int a = 0; a < K; ++a)
-      for (int b = 0; b < K; ++b) A[a][b] = Hs[a][b] + (a == b ? diagonal[a] / radius : 0.);
-    const bool solved = SolveSpd(K, A, gs, step);
-    for (int a = 0; a < K; ++a) step[a] = -step[a];
-    reuse_diagonal = true;
-    double model_cost_change = 0.;
-    if (solved) {
-      double sg = 0., sHs = 0.;
-      for (int a = 0; a < K; ++a) {
-        sg += step[a] * gs[a];
-        for (int b = 0; b < K; ++b) sHs += step[a] * Hs[a][b] * step[b];
-      }
-      model_cost_change = -(sg + 0.5 * sHs);
-    }
-    if (!solved || !(model_cost_change > 0.)) {
-      if (++num_consecutive_invalid_steps >= kMaxConsecutiveInvalidSteps) { termination = 2; break; }
-      radius *= 0.5;
-      reuse_diagonal = false;
-      ++unsuccessful;
-      continue;
-    }
-    num_consecutive_invalid_steps = 0;
-    double delta[kMaxLocal], candidate[7];
-    for (int a = 0; a < K; ++a) delta[a] = step[a] * scale[a];
-    for (int a = 0; a < 3; ++a) candidate[a] = x[a] + delta[a];
-    PlusRotation(yaw_only, x + 3, delta + 3, candidate + 3);
-    Eval3D at_candidate;
-    Evaluate3D(P, candidate, K, scratch, &at_candidate);
-    const double candidate_cost = at_candidate.cost;
-
+  }
+  __device__ __forceinline__ double StepNorm(const double* x, const double* candidate,
+                                             const double*) const {
     double step_sq = 0.;
     for (int a = 0; a < 7; ++a) step_sq += (x[a] - candidate[a]) * (x[a] - candidate[a]);
-    if (sqrt(step_sq) <= kParameterTolerance * (x_norm + kParameterTolerance)) {
-      termination = 0;
-      break;
-    }
-    const double cost_change = x_cost - candidate_cost;
-    if (fabs(cost_change) <= kFunctionTolerance * x_cost) { termination = 0; break; }
-    const double relative_decrease_now = (current_cost - candidate_cost) / model_cost_change;
-    const double historical_relative_decrease =
-        (reference_cost - candidate_cost) /
-        (accumulated_reference_model_cost_change + model_cost_change);
-    const double relative_decrease = fmax(relative_decrease_now, historical_relative_decrease);
-    if (relative_decrease > kMinRelativeDecrease) {
-      for (int a = 0; a < 7; ++a) x[a] = candidate[a];
-      x_norm = norm7(x);
-      at_x = at_candidate;
-      x_cost = candidate_cost;
-      last_step_successful = true;
-      ++successful;
-      if (x_cost < best_cost) {
-        best_cost = x_cost;
-        for (int a = 0; a < 7; ++a) best_x[a] = x[a];
-      }
-      // std::pow(t, 3) of the restatement is t * t * t for these arguments up to rounding;
-      // pow is evaluated here as well so that both sides take the same value.
-      radius = radius / fmax(1. / 3., 1. - pow(2. * relative_decrease - 1., 3.));
-      radius = fmin(kMaxRadius, radius);
-      decrease_factor = 2.;
-      reuse_diagonal = false;
-      current_cost = candidate_cost;
-      accumulated_candidate_model_cost_change += model_cost_change;
-      accumulated_reference_model_cost_change += model_cost_change;
-      if (candidate_cost < minimum_cost) {
-        minimum_cost = candidate_cost;
-        num_consecutive_nonmonotonic_steps = 0;
-        candidate_cost_eval = candidate_cost;
-        accumulated_candidate_model_cost_change = 0.;
-      } else {
-        ++num_consecutive_nonmonotonic_steps;
-        if (candidate_cost > candidate_cost_eval) {
-          candidate_cost_eval = candidate_cost;
-          accumulated_candidate_model_cost_change = 0.;
-        }
-      }
-      if (num_consecutive_nonmonotonic_steps == max_consecutive_nonmonotonic_steps) {
-        reference_cost = candidate_cost_eval;
-        accumulated_reference_model_cost_change = accumulated_candidate_model_cost_change;
-      }
-    } else {
-      radius = radius / decrease_factor;
-      decrease_factor *= 2.;
-      reuse_diagonal = true;
-      ++unsuccessful;
-    }
+    return sqrt(step_sq);
   }
+  // std::pow(t, 3) of the restatement is t * t * t for these arguments up to rounding; pow is
+  // evaluated here as well so that both sides take the same value.
+  __device__ __forceinline__ double Cube(double t) const { return pow(t, 3.); }
+};
+
+// One workgroup per match: the shared trust-region loop over Pose3DProblem.
+__global__ void __launch_bounds__(kCeresThreads)
+Ceres3DKernel(const Ceres3DProblem* __restrict__ problems) {
+  const Ceres3DProblem& P = problems[blockIdx.x];
+  __shared__ double scratch[4][kNumSums];
+  const bool yaw_only = P.yaw_only != 0;
+  Pose3DProblem problem{P, scratch, yaw_only, 3 + (yaw_only ? 1 : 3)};
+  TrResult<7> r;
+  MinimizeTrustRegion(problem, P.init, P.use_nonmonotonic_steps != 0, P.max_num_iterations, &r);
   if (threadIdx.x == 0) {
-    for (int a = 0; a < 7; ++a) P.out[a] = best_x[a];
-    P.out[7] = initial_cost; P.out[8] = best_cost;
-    P.out[9] = successful; P.out[10] = unsuccessful; P.out[11] = termination;
+    for (int a = 0; a < 7; ++a) P.out[a] = r.x[a];
+    P.out[7] = r.initial_cost; P.out[8] = r.final_cost;
+    P.out[9] = r.successful; P.out[10] = r.unsuccessful; P.out[11] = r.termination;
   }
 }
 
@@ -601,7 +440,7 @@ void SolveProblems(Workspace& ws, Ceres3DProblem* problems, int num, size_t clou
   SmallCopyAsync(d_xyz, h_xyz, sizeof(float) * cloud_floats, /*to_device=*/true, ws.stream);
   SmallCopyAsync(d_misc, h_misc, prob_bytes, /*to_device=*/true, ws.stream);
   RecordEvent(ws.ev_begin, ws.stream);
-  Ceres3DKernel<<<num, kCeres3DThreads, 0, ws.stream>>>(
+  Ceres3DKernel<<<num, kCeresThreads, 0, ws.stream>>>(
       reinterpret_cast<const Ceres3DProblem*>(d_misc));
   CMX_HIP(hipGetLastError());
   RecordEvent(ws.ev_end, ws.stream);
@@ -991,7 +830,7 @@ extern "C" cmx_status cmx_ceres3d_match_grids_batch(
     std::memcpy(problems_in(h_block), problems.data(), sizeof(Ceres3DProblem) * num_matches);
     SmallCopyAsync(d_block, h_block, upload_bytes, /*to_device=*/true, ws->stream);
     RecordEvent(ws->ev_begin, ws->stream);
-    Ceres3DKernel<<<num_matches, kCeres3DThreads, 0, ws->stream>>>(problems_in(d_block));
+    Ceres3DKernel<<<num_matches, kCeresThreads, 0, ws->stream>>>(problems_in(d_block));
     CMX_HIP(hipGetLastError());
     RecordEvent(ws->ev_end, ws->stream);
     SmallCopyAsync(out_in(h_block), out_in(d_block), 12 * sizeof(double) * num_matches,
