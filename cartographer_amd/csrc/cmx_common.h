@@ -115,6 +115,7 @@ cmx_status Guard(F&& body) {
   X(fast2d_queue_blocks)  /* workgroups of the work-queue tree search (0: default) */              \
   X(fast2d_queue_capacity) /* nodes per sub-queue (tests: forces the overflow path) */             \
   X(fast2d_queue_lost)    /* lost races after which a wavefront stops looking for work (0: 3) */   \
+  X(fast2d_chain)         /* 1: the work-queue tree search loads the bound, and waits for it, wherever it uses it (TreeQueueKernel<1>, the parity partner of the lean chain step; 0: lean) */ \
   X(fast2d_create_chain)  /* most matchers per chain of launches of cmx_fast2d_create_batch (0: default; tests: splits a batch) */ \
   X(fast3d_create_chain)  /* most matchers per chain of launches of cmx_fast3d_create_batch (0: default; tests: splits a batch) */ \
   X(grid2d_insert_chain)  /* most insertions per set of launches of a round of cmx_grid2d_insert_batch (0: default; tests: splits a round) */ \

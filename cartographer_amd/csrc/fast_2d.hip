@@ -1505,6 +1505,17 @@ __device__ __forceinline__ void RecordLeafAgent(const Node2D& leaf, const NodeLi
     __hip_atomic_store(&at[k], v[k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
+// kChain (debug switch fast2d_chain): 1 = the bound (`best_bits`) loaded and waited for wherever it
+// is used (the parity partner); 0 = two of those waits taken out.  The bound only rises, so a value
+// that is a trip older prunes a little less and decides nothing; the queue protocol, the order of
+// the list and every other load are the same either way.
+//   * The best node of a list round is picked before the bound is looked at (the choice never
+//     depended on it), and ONE load of the bound then decides about the round and about the node
+//     (kChain = 1: a load for the round, a second one for the node).
+//   * A chain step loads the bound WITH the first gathers of its level, not behind the child
+//     scores: one trip to memory less per step.
+// What else was measured and left out: DESIGN 5.2.
+template <int kChain>
 __global__ void __launch_bounds__(256)
 TreeQueueKernel(const Fast2DProblem* __restrict__ problems, ProblemState* __restrict__ states, int n,
                 NodeList in, TreeQueue Q, NodeList leaves, Counters* __restrict__ counters,
@@ -1513,6 +1524,8 @@ TreeQueueKernel(const Fast2DProblem* __restrict__ problems, ProblemState* __rest
                 const unsigned* __restrict__ tail_dev, unsigned* __restrict__ tail_host,
                 int tail_words, int counters_trace, int max_lost) {
   static_assert(sizeof(Node2D) == 32, "a node is eight words: eight granules, four leaf stores");
+  static_assert(kChain == 0 || kChain == 1, "0: the lean step and pop, 1: every trip waited for");
+  constexpr bool kLean = kChain == 0;
   const int lane = threadIdx.x & 63;
   const int wave_id = blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int num_waves = gridDim.x * 4;
@@ -1549,6 +1562,7 @@ TreeQueueKernel(const Fast2DProblem* __restrict__ problems, ProblemState* __rest
   bool round_loaded = false, share_done = false;
   bool pushed_any = false;
   Node2D nd;
+  unsigned listed_top = 0;     // kLean: the score bits of the node taken from the list round
   for (;;) {
     bool have = false;
     while (!have && !share_done) {
@@ -1568,9 +1582,13 @@ TreeQueueKernel(const Fast2DProblem* __restrict__ problems, ProblemState* __rest
         round_loaded = true;
       }
       const unsigned top = static_cast<unsigned>(WaveMax(static_cast<int>(mine_bits)));
-      const float bound_now = __uint_as_float(LoadAgent(&states[0].best_bits));
       // (the bound of problem 0 only prunes rounds of a single search; batches check per node)
-      if (top == 0 || (num_problems == 1 && __uint_as_float(top) < bound_now)) {
+      // kLean: which node is next does not depend on the bound, so it is taken first and the round
+      // is tested below, against the bound loaded for the node
+      float bound_now = 0.f;
+      if constexpr (kLean) listed_top = top;
+      else bound_now = __uint_as_float(LoadAgent(&states[0].best_bits));
+      if (top == 0 || (!kLean && num_problems == 1 && __uint_as_float(top) < bound_now)) {
         round_loaded = false;      // nothing left in this round that can matter
         continue;
       }
@@ -1586,7 +1604,7 @@ TreeQueueKernel(const Fast2DProblem* __restrict__ problems, ProblemState* __rest
           __uint_as_float(__builtin_amdgcn_readlane(__float_as_uint(mine.coarse_score), l));
       if (lane == l) mine_bits = 0;
       have = true;
-      ++q_listed;
+      if constexpr (!kLean) ++q_listed;
     }
     if (!have) {
       // its own sub-queue first (whoever publishes nodes is who guarantees that they are taken:
@@ -1601,6 +1619,17 @@ TreeQueueKernel(const Fast2DProblem* __restrict__ problems, ProblemState* __rest
     const Fast2DProblem& P = problems[problem];
     ProblemState& st = states[problem];
     float best = __uint_as_float(LoadAgent(&st.best_bits));
+    if constexpr (kLean) {
+      if (have) {
+        // from the list: the round's best node.  Below the bound (a single search's), nothing
+        // left in the round can matter
+        if (num_problems == 1 && __uint_as_float(listed_top) < best) {
+          round_loaded = false;
+          continue;
+        }
+        ++q_listed;
+      }
+    }
     if (nd.score < best) continue;                       // the bound has risen since the push
     if (problem != stat_problem) { flush_stats(); stat_problem = problem; }
     ++q_chains;
@@ -1628,8 +1657,11 @@ TreeQueueKernel(const Fast2DProblem* __restrict__ problems, ProblemState* __rest
         ChainGather<decltype(first_tag)::value, decltype(count_tag)::value, true>(L, cell, &even,
                                                                                   &odd, &seen_max);
       };
+      unsigned step_bits = 0;
+      if constexpr (kLean) step_bits = LoadAgent(&st.best_bits);
       gather(std::integral_constant<int, 0>{}, std::integral_constant<int, 4>{});
       gathers += 4;
+      if constexpr (kLean) best = fmaxf(best, __uint_as_float(step_bits));
       if (n > 4 * kWave) {
         // what the best child of this lane's points still lacks to the parent (see
         // ExpandWaveKernel): no child can reach the bound -> the rest of the gathers is skipped
@@ -1665,7 +1697,7 @@ TreeQueueKernel(const Fast2DProblem* __restrict__ problems, ProblemState* __rest
 #pragma unroll
       for (int o = 0; o < 4; ++o)
         if (o != k && sc[o] >= 0.f && (sc[o] > mine || (sc[o] == mine && o < k))) ++rank;
-      best = fmaxf(best, __uint_as_float(LoadAgent(&st.best_bits)));
+      if constexpr (!kLean) best = fmaxf(best, __uint_as_float(LoadAgent(&st.best_bits)));
       const bool keep = lane < 4 && mine >= 0.f && mine >= best;
       // the best valid child (rank 0; child 0 is always valid)
       const int kbest = __ffsll(static_cast<long long>(__ballot(lane < 4 && mine >= 0.f && rank == 0))) - 1;
@@ -1998,7 +2030,9 @@ QueueOutcome RunQueueSearch(SearchRun& run, std::unique_ptr<LaunchTurn> turn) {
   const int blocks = Debug().fast2d_queue_blocks > 0
                          ? Debug().fast2d_queue_blocks
                          : std::min(2048, 256 * std::max(1, (num + 3) / 4));
-  TreeQueueKernel<<<blocks, 256, 0, ws.stream>>>(
+  // (debug switch fast2d_chain: 1 = the bound waited for wherever it is used, the parity partner)
+  const auto tree_kernel = Debug().fast2d_chain == 1 ? TreeQueueKernel<1> : TreeQueueKernel<0>;
+  tree_kernel<<<blocks, 256, 0, ws.stream>>>(
       batch.d_problems, batch.d_states, n, run.Front(0), queue, run.leaf_list, run.d_counters,
       run.d_tail.sel, run.d_tail.best, num, run.d_tail.states, run.d_tail.summary,
       run.d_tail.words(), run.PublishTo(), run.h_tail.num_words(),
