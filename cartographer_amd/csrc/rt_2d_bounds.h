@@ -40,10 +40,11 @@
 // as the parity partner (tests/test_gpu_r2_paths.py).
 #ifndef CMX_RT_2D_BOUNDS_H_
 #define CMX_RT_2D_BOUNDS_H_
+// (the sizes the host's plan shares with these kernels -- kBoundMinMatches, kBoundMaxBlocks,
+// kBoundListCap, BoundSumWords, BoundTailLds, BoundTail4Lds, ... -- at file scope of rt_2d_tiles.hip)
+#include "rt_2d_plan.h"
 
 constexpr int kBoundThreads = 512;          // eight wavefronts; two workgroups per CU
-constexpr int kBoundMinMatches = 96;        // matches per call from which the bound kernel is the default
-constexpr int kBoundMaxBlocks = 8;          // block columns in one ds_read_b64: side <= 16
 #ifndef CMX_RT2D_BOUND_BITS
 #define CMX_RT2D_BOUND_BITS 5
 #endif
@@ -232,6 +233,7 @@ struct BoundDisc {
   float2 rot;
   int lo, ix_hi, iy_hi;
 };
+static_assert(sizeof(BoundDisc) == kBoundDiscBytes, "rt_2d_plan.h sizes the kernels' LDS with it");
 __device__ __forceinline__ BoundDisc MakeBoundDisc(const Rt2DTileParams& P, float2 rot) {
   BoundDisc D;
   const double inv_res = P.inv_res;
@@ -267,13 +269,6 @@ __device__ __forceinline__ void BoundCellOf(const BoundDisc& D, const Rt2DFrame&
     *ix = min(max(static_cast<int>(nY), D.lo), D.ix_hi);
     *iy = min(max(static_cast<int>(nX), D.lo), D.iy_hi);
   }
-}
-
-constexpr int kBoundListCap = 128;           // blocks phase C sums per match; more: the per-candidate kernels
-// words of the block-sum region: the sums of the match's blocks, later the summed candidates
-// (index, quantised sum) the fused finish looks at
-__host__ __device__ constexpr size_t BoundSumWords(int blocks) {
-  return (static_cast<size_t>(blocks > 8 * (kBoundListCap + 1) ? blocks : 8 * (kBoundListCap + 1)) + 3) & ~size_t{3};
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -856,17 +851,6 @@ Rt2DBoundKernel(const Rt2DTileParams* __restrict__ params, const int4* __restric
 //   rots[num_scans] | ub[BoundSumWords] | list[kBoundListCap] | sums[kBoundListCap][4]
 // ---------------------------------------------------------------------------------------------
 constexpr int kBoundTailThreads = 512;
-constexpr int kBoundTailGroup = 2;           // finalists per round of f32 chains (LDS rows)
-__host__ __device__ constexpr size_t BoundTailRegion(int n_pad, int num_scans) {
-  const size_t fin = 4 * static_cast<size_t>(n_pad) + static_cast<size_t>(kBoundTailGroup) * 4 * (static_cast<size_t>(n_pad) + 4) +
-                     4 * ((static_cast<size_t>(num_scans) + 3) & ~size_t{3}) + 12 * static_cast<size_t>(kStage1Cap);
-  const size_t cloud = 8 * static_cast<size_t>(n_pad);
-  return ((fin > cloud ? fin : cloud) + 15) & ~size_t{15};
-}
-__host__ __device__ constexpr size_t BoundTailLds(int n_pad, int num_scans, int nb) {
-  return BoundTailRegion(n_pad, num_scans) + 8 * ((static_cast<size_t>(num_scans) + 1) & ~size_t{1}) +
-         4 * BoundSumWords(num_scans * nb * nb) + 20 * size_t{kBoundListCap};
-}
 
 template <int NB>
 __global__ void __launch_bounds__(kBoundTailThreads)
@@ -940,21 +924,6 @@ Rt2DBoundTailKernel(const Rt2DTileParams* __restrict__ params, const int* __rest
 #define CMX_RT2D_TAIL4_THREADS 512
 #endif
 constexpr int kBoundTail4Threads = CMX_RT2D_TAIL4_THREADS;
-constexpr int kList4Cap = 96;                // 4 x 4 blocks summed per match besides the best; more: the per-candidate kernels
-                                             // (a wavefront per block: a match with hundreds of them holds its
-                                             // whole launch up for longer than its repeat takes)
-constexpr int kCand4Cap = 512;               // candidates handed to the finish; more (a landscape of ties): the same
-__host__ __device__ constexpr size_t Tail4Region(int lp, int lh, int n_pad, int num_scans) {
-  const size_t fin = BoundTailRegion(n_pad, num_scans);
-  const size_t own = static_cast<size_t>(lh) * lp + ((4 * static_cast<size_t>(lp) + 16 + 15) & ~size_t{15}) +
-                     8 * static_cast<size_t>(n_pad);
-  return ((fin > own ? fin : own) + 15) & ~size_t{15};
-}
-__host__ __device__ constexpr size_t BoundTail4Lds(int lp, int lh, int n_pad, int num_scans, int nb4) {
-  return Tail4Region(lp, lh, n_pad, num_scans) + sizeof(BoundDisc) * static_cast<size_t>(num_scans) +
-         4 * ((static_cast<size_t>(num_scans) * nb4 * nb4 + 3) & ~size_t{3}) +
-         4 * static_cast<size_t>(16 + kList4Cap + 2 * kCand4Cap) + 64;
-}
 
 template <int NB4>
 __global__ void __launch_bounds__(kBoundTail4Threads, 4)

@@ -11,16 +11,11 @@ namespace cmx {
 // Integer bulk pass (rt_2d_tiles.hip): cells enter LDS as q = u >> kQShift, u = 32767 - value.
 constexpr int kQShift = 5;
 constexpr int kQ8Shift = 7;                  // the byte image of the bound kernel's tail: q8 = u >> 7 <= 255
-constexpr int kRt2DMaxPoints = 8192;        // points per scan the tile path takes
 // Finalists of a match: (candidate index, f32 score bits) pairs -- the first kFinalistHead next
 // to the counters (they travel back with them), the rest in the overflow region.
 constexpr int kFinalistCap = 4096;
 constexpr int kFinalistHead = 61;           // 2 + 2 * 61 words, then two bound and two stage counters: 512 bytes per match
-constexpr int kMaxRowsPerLane = 8;
-#ifndef CMX_RT2D_TASK_ITERS
-#define CMX_RT2D_TASK_ITERS 64
-#endif
-constexpr int kPairTaskIters = CMX_RT2D_TASK_ITERS;          // iterations (entries per stream) of one task
+// (kRt2DMaxPoints, kMaxRowsPerLane, kPairTaskIters: rt_2d_plan.h, with the host's plan)
 
 // Slack of a score bound for the rounding of the reference's N-term f32 chain: the chain's
 // result differs from the real sum of the N probabilities (each <= 0.9, each rounded by the

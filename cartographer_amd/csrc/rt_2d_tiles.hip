@@ -33,6 +33,10 @@
 //   Rt2DFinishKernel    one workgroup per match: bounds, exact integer re-sums, f32 finalists.
 // Grids of any size stay on this path: the image a workgroup holds depends on the tile size, not
 // on the grid.
+//
+// What the host decides before a launch -- tile geometry, every LDS size, work items, the launch
+// grid, the scratch offsets and the layout of the upload block -- is rt_2d_plan.h: plain C++ in
+// named stages, with the sizing constants the kernels here share with it.
 #include <algorithm>
 #include <atomic>
 #include <chrono>
@@ -42,6 +46,7 @@
 #include <unordered_map>
 
 #include "rt_2d_device.h"
+#include "rt_2d_plan.h"
 #include "scan_matching_2d.h"
 
 namespace cmx {
@@ -50,13 +55,7 @@ namespace {
 constexpr int kTileMaxThreads = 1024;        // a tile workgroup: 1024 threads alone on a CU (one tile
                                             // per match), or 512 with two per CU (several tiles)
 constexpr int kFinishThreads = 512;
-#ifndef CMX_RT2D_JOB_CHUNKS
-#define CMX_RT2D_JOB_CHUNKS 8
-#endif
-constexpr int kJobChunks = CMX_RT2D_JOB_CHUNKS;                // chunks of 64 points of one rotation a wavefront discretises in one job
-constexpr int kFusedMaxPoints = 2048;        // (clouds beyond: the prep kernel, more rotations per workgroup)
-constexpr int kMaxTiles = 16;               // tiles of a match's bounding box (x 4 phases = 64 keys)
-constexpr int kStage1Cap = 1024;            // candidates the exact integer pass takes per match
+// (kJobChunks, kFusedMaxPoints, kMaxTiles, kStage1Cap: rt_2d_plan.h)
 constexpr unsigned kFlat = 0xffffffffu;     // misc[1]: more candidates than the lists hold
 constexpr unsigned kOutOfBox = 0x80000000u; // misc[0] (next to the prep tickets): a point fell outside the predicted box
 constexpr unsigned kBoundFlat = 0x20000000u;       // misc[0]: more blocks reach the bound than the bound kernel lists (flat landscape)
@@ -1163,68 +1162,6 @@ Rt2DFinishKernel(const Rt2DTileParams* __restrict__ params, int group,
 
 #include "rt_2d_bounds.h"
 
-size_t Align16(size_t v) { return (v + 15) & ~static_cast<size_t>(15); }
-
-// Conflict-free LDS row pitch (bytes, a multiple of 16, >= min_bytes; 0: none exists): the H x B
-// 8-byte blocks a half-wavefront reads in one LDS cycle fall into 2 H B distinct banks for every
-// base address.  The bank pattern depends on the pitch modulo 256 only: the sixteen residues are
-// tested once per (H, B).
-int ConflictFreePitch(int H, int B, int min_bytes) {
-  static std::mutex mu;
-  static int valid[33][33];                  // bit k: pitch = 16 k (mod 256) is conflict-free; -1 unset
-  static bool init = false;
-  unsigned mask;
-  {
-    std::lock_guard<std::mutex> lock(mu);
-    if (!init) {
-      for (auto& row : valid) for (int& v : row) v = -1;
-      init = true;
-    }
-    if (valid[H][B] < 0) {
-      int m = 0;
-      for (int k = 0; k < 16; ++k) {
-        const int cand = 16 * k + 256;
-        unsigned long long used = 0;
-        bool ok = true;
-        for (int r = 0; r < H && ok; ++r)
-          for (int b = 0; b < B && ok; ++b)
-            for (int w = 0; w < 2; ++w) {
-              const int bank = ((r * cand + b * 8) / 4 + w) & 63;
-              if (used >> bank & 1) ok = false;
-              used |= 1ull << bank;
-            }
-        if (ok) m |= 1 << k;
-      }
-      valid[H][B] = m;
-    }
-    mask = static_cast<unsigned>(valid[H][B]);
-  }
-  if (mask == 0) return 0;
-  for (int cand = (min_bytes + 15) & ~15;; cand += 16)
-    if (mask >> ((cand >> 4) & 15) & 1) return cand;
-}
-
-struct TileGeometry {
-  int B, H, hl, ht, gpitch, grows;
-  int box_x0, box_y0, T, ntx, nty, lp, th_img, tile_image_bytes;
-  int cap_s, gmin, gmax, target, rw, list_lds, task_cap;
-  int groups;               // fused: the rotation groups (work items) of this match, chosen by the host
-  size_t lds;               // of the tile kernel
-  size_t image_bytes;       // of the grid image in HBM: quantised image + pooled planes
-  size_t q_bytes;           // of the quantised image alone (the planes start behind it)
-  int m2_pitch, m2_rows;    // pooled planes (0: window beyond 16 x 16, no planes)
-  int b_lpb, b_lh;          // bound kernel: LDS copy of the planes
-  size_t b_lds;             // bound kernel: dynamic LDS of this match
-  size_t b_finish_room;     // of it: planes | zeros | cloud, which its fused finish lays out anew
-  size_t b_tail_at;         // where the rest starts: behind those, and behind what the finish needs
-  int m4_pitch, m4_rows;    // 4 x 4 pooled planes (round 6)
-  size_t q8_bytes;          // the byte image behind them
-  int b8_lp, b8_lh;         // tail kernel: LDS box of the byte image
-  size_t t4_lds;
-  int b4_lpb, b4_lh, b4_pstride;
-  size_t b4_tail_at, b4_lds;
-};
-
 }  // namespace
 
 // ---------------------------------------------------------------------------------------------
@@ -1437,32 +1374,38 @@ struct Rt2DTileCall::Impl {
   const Rt2DItem* items;
   const Rt2DSearch* search;
   int num, device;
-  std::vector<TileGeometry> geo;
-  int rpl = 1, max_scans = 0, common_stride = -1, group = 8, cus = 256;
+  int cus = 256;
   int share = 1;                        // calls sharing the device (the parts of a batch)
   int batch_matches = 0;                // matches of the whole batch (>= num)
-  size_t tile_lds = 0, prep_lds = 0, finish_lds = 0;
-  size_t lists_total = 0, hdr_total = 0, qsum_total = 0;
-  long long work_cap = 0, entries_total = 0;
-  int tile_grid = 0, tile_threads = 512;
-  bool fused = false;                   // one tile per match, prep fused into the tile kernel
-  bool bounds = false;                  // block bounds first (rt_2d_bounds.h): fused shape only
-  bool split = false;                   // ... with the tail of every match in a kernel of its own
-  bool level4 = false;                  // ... and blocks of 4 x 4 translations first (always split)
-  size_t tail_lds = 0;
-  size_t bound4_lds = 0, tail4_lds = 0;
-  int bound_nb = 0;                     // blocks per window axis (launch-wide: the largest)
-  size_t bound_lds = 0;
+  Rt2DPlan plan;                        // rt_2d_plan.h: geometry, LDS sizes, work items, grid, offsets
+  Rt2DStaging staging;                  // ... and the layout of the upload block
   // (the per-rotation (cos, sin) pairs of every match, libm: worked out by Plan() -- off the
   // calling thread when the batch goes out in parts -- and copied into the staging buffer)
   std::vector<float2> tables;
-  std::vector<size_t> table_at;
   std::unique_ptr<WorkspaceLease> ws;
   CacheHolds holds;
   unsigned* h_misc = nullptr;
   unsigned* d_overflow = nullptr;
   unsigned long long* d_timeline = nullptr;
   bool enqueued = false, synced = false;
+  // Enqueue(): its buffers, and its steps in the order they run
+  char* h_in = nullptr;
+  char* d_in = nullptr;
+  uint16_t* d_lists = nullptr;
+  uint32_t* d_hdr = nullptr;
+  int* d_qsum = nullptr;
+  int4* d_work = nullptr;
+  unsigned* d_misc = nullptr;
+  int* d_counters = nullptr;
+  int* d_ub = nullptr;
+  int timeline_tile_slots = 0;
+  std::vector<uint16_t*> image_of;
+  std::vector<int> build_image;
+  void ReserveBuffers(hipStream_t on_stream);
+  void AcquireImages();
+  void FillParams();
+  void LaunchImageKernels(const Rt2DTileParams* d_params);
+  void LaunchMatchKernels(const Rt2DTileParams* d_params);
 };
 
 Rt2DTileCall::Rt2DTileCall(const cmx_rt_options* options, const Rt2DItem* items,
@@ -1483,452 +1426,73 @@ Rt2DTileCall::~Rt2DTileCall() {
 bool Rt2DTileCall::Plan() {
   Impl& I = *impl_;
   const DebugOptions& dbg = Debug();
-  const Rt2DItem* items = I.items;
   const Rt2DSearch* search = I.search;
   const int num = I.num;
   (void)hipDeviceGetAttribute(&I.cus, hipDeviceAttributeMultiprocessorCount, I.device);
-  const int cus = I.cus;
-  std::vector<TileGeometry>& geo = I.geo;
-  geo.assign(num, TileGeometry{});
-  // ---- window geometry per item; launch-wide rows per lane: the largest any item needs.
-  // (H = the most rows of B blocks a half-wavefront holds for which a conflict-free pitch of whole
-  // 16-byte DMA pieces exists: e.g. 8 rather than 10 rows of 3 blocks)
-  int rpl = 1;
+  std::vector<Rt2DPlanMatch> in(num);
   for (int m = 0; m < num; ++m) {
-    const int side = 2 * search[m].nl + 1;
-    const int B = (side + 3 + 3) / 4;
-    if (B > 32 || items[m].n > kRt2DMaxPoints || search[m].num_scans > 4096) return false;
-    if (items[m].limits->num_x_cells > 32000 || items[m].limits->num_y_cells > 32000)
-      return false;                                        // (cells travel as int16 pairs)
-    int H = m > 0 && geo[m - 1].B == B ? geo[m - 1].H : 32 / B;
-    while (H > 1 && ConflictFreePitch(H, B, 16) == 0) --H;
-    geo[m].B = B;
-    geo[m].H = H;
-    rpl = std::max(rpl, (side + H - 1) / H);
+    const Rt2DItem& it = I.items[m];
+    in[m] = Rt2DPlanMatch{it.n, it.limits->num_x_cells, it.limits->num_y_cells, it.limits->resolution,
+                          it.limits->max_x, it.limits->max_y, it.initial->x, it.initial->y,
+                          search[m].nl, search[m].num_scans, search[m].max_range,
+                          it.device_xyz != nullptr, it.device_cells != nullptr};
   }
-  if (rpl > kMaxRowsPerLane) return false;
-  if (rpl == 5) rpl = 6;
-  if (rpl == 7) rpl = 8;                         // (instantiated: 1, 2, 3, 4, 6, 8 rows per lane)
-  I.rpl = rpl;
-  // ---- per item: the box of window starts the scan can reach.  Every rotated point lies within
-  // max_range of the initial translation (plus a cell for the f32 roundings of rotation and
-  // index, plus the half cell of lround); cells are clamped to [-(nl + 1), n + nl] as on the
-  // device.  Items with the same window (the usual batch) share ONE tile geometry, chosen for the
-  // largest box, cloud and rotation count among them.
-  struct Class { int nl, span_x, span_y, n_pad, scans, items; TileGeometry g; };
-  std::vector<Class> classes;
-  std::vector<int> class_of(num), span_x(num), span_y(num);
-  for (int m = 0; m < num; ++m) {
-    const Rt2DItem& it = items[m];
-    const Rt2DSearch& sr = search[m];
-    TileGeometry& g = geo[m];
-    const int nx = it.limits->num_x_cells, ny = it.limits->num_y_cells, nl = sr.nl;
-    g.hl = (2 * nl + 1 + 7) & ~7;
-    g.ht = 2 * nl + 1;
-    const double res = it.limits->resolution;
-    const double reach = (sr.max_range * (1.0 + 1e-5)) / res + 2.0;
-    const double cxc = (it.limits->max_y - it.initial->y) / res - 0.5;   // cell x from the map's y
-    const double cyc = (it.limits->max_x - it.initial->x) / res - 0.5;
-    const auto clampi = [](double v, int lo, int hi) {
-      return static_cast<int>(std::min<double>(std::max<double>(v, lo), hi));
-    };
-    const int ix_lo = clampi(std::floor(cxc - reach), -(nl + 1), nx + nl);
-    const int ix_hi = clampi(std::ceil(cxc + reach), -(nl + 1), nx + nl);
-    const int iy_lo = clampi(std::floor(cyc - reach), -(nl + 1), ny + nl);
-    const int iy_hi = clampi(std::ceil(cyc + reach), -(nl + 1), ny + nl);
-    g.box_x0 = (ix_lo - nl + g.hl) & ~7;
-    g.box_y0 = iy_lo - nl + g.ht;
-    span_x[m] = ix_hi - nl + g.hl - g.box_x0 + 1;
-    span_y[m] = iy_hi - nl + g.ht - g.box_y0 + 1;
-    const int n_pad = (it.n + 63) / 64 * 64;
-    int c = 0;
-    while (c < static_cast<int>(classes.size()) && classes[c].nl != nl) ++c;
-    if (c == static_cast<int>(classes.size())) classes.push_back(Class{nl, 0, 0, 0, 0, 0, g});
-    Class& k = classes[c];
-    k.span_x = std::max(k.span_x, span_x[m]); k.span_y = std::max(k.span_y, span_y[m]);
-    k.n_pad = std::max(k.n_pad, n_pad); k.scans = std::max(k.scans, sr.num_scans);
-    ++k.items;
-    class_of[m] = c;
-    I.entries_total += static_cast<long long>(it.n) * sr.num_scans;
-  }
-  // Two shapes.  (1) ONE tile per match, a workgroup of 1024 threads alone on its CU (up to
-  // 150 KB of LDS): whenever the whole box of a match fits -- the items of a match are then its
-  // rotation groups, all of one size, their sums plain stores.  C1's box (217 window starts per
-  // axis at 5 cm) is such a case: as four tiles one of them held most of the points, and the
-  // planner's smaller items each paid the ~4 us before their first window update.  (2) Several
-  // tiles, workgroups of 512 threads, two per CU (76 KB each): boxes beyond that (long-range
-  // scans, fine grids), sums by atomics.
-  const size_t kLdsTwoPerCu = (dbg.rt2d_lds_kb > 0 ? dbg.rt2d_lds_kb : 76) * size_t{1024};
-  const size_t kLdsOnePerCu = 150 * size_t{1024};
-  bool single_tile = dbg.rt2d_tile <= 0;
-  bool want_fused = !dbg.rt2d_unfused;
-  for (const Class& k : classes) want_fused = want_fused && k.n_pad <= kFusedMaxPoints;
-  for (Class& k : classes) {
-    TileGeometry& g = k.g;
-    const int side = 2 * k.nl + 1;
-    const int rows_extra = rpl * g.H;
-    const int cap_tile = k.n_pad + 64;                // a rotation's entries of ONE tile, padded
-    const bool fuse = want_fused;
-    const auto try_tile = [&](int T, size_t budget, bool one_tile, TileGeometry* out) {
-      const int ntx = (k.span_x + T - 1) / T, nty = (k.span_y + T - 1) / T;
-      if (ntx * nty > (one_tile ? 1 : kMaxTiles)) return false;
-      const int lp = ConflictFreePitch(g.H, g.B, 2 * (T + 4 * g.B));
-      if (lp == 0) return false;
-      const int th_img = T + rows_extra;
-      const int image = ((th_img + rows_extra) * lp + 1023) & ~1023;
-      // rotations a workgroup's LDS holds: all of them (the planner gives a light tile ONE item)
-      // or -- one tile per match -- as many as fit beside the image
-      for (int gmin = std::max(1, (k.scans + 63) / 64); gmin <= k.scans; ++gmin) {
-        const int rw = (k.scans + gmin - 1) / gmin;
-        const bool fused_shape = one_tile && fuse;
-        // (fused: rw = the rotations of one ROUND; a discretisation job's region of the list buffer
-        // holds its chunks' entries plus the padding of four sub-lists, its tasks two more than its
-        // chunks: Rt2DTileKernel)
-        const int jpr = (k.n_pad / 64 + kJobChunks - 1) / kJobChunks;
-        const int cap_rot = fused_shape ? k.n_pad + 64 * jpr : cap_tile;
-        const int task_cap = fused_shape ? rw * jpr * (kJobChunks + 2) : rw * (k.n_pad / kPairTaskIters + 2);
-        size_t fixed = static_cast<size_t>(image) + 4 * ((static_cast<size_t>(rw) * side * side + 3) & ~size_t{3}) +
-                       16 * static_cast<size_t>(rw) + 4 * ((static_cast<size_t>(rw) + 1 + 3) & ~size_t{3}) +
-                       16 * static_cast<size_t>(task_cap) + 64;
-        if (fused_shape) {
-          // (all rotations of the match, the cloud rotated by the initial yaw)
-          fixed += 8 * ((static_cast<size_t>(k.scans) + 1) & ~size_t{1}) + 8 * static_cast<size_t>(k.n_pad);
-        }
-        if (fixed + 2 * static_cast<size_t>(cap_rot) > budget) {
-          if (!one_tile) return false;
-          continue;                                      // fewer rotations per workgroup
-        }
-        // list buffer: what is left, at most every rotation's entries at once
-        const size_t want = static_cast<size_t>(rw) * cap_rot;
-        const size_t room = (budget - fixed) / 2;
-        if (one_tile && room < want) continue;           // (all of an item's lists in one round)
-        out->list_lds = static_cast<int>(std::min(want, room) & ~size_t{7});
-        out->T = T; out->ntx = ntx; out->nty = nty; out->lp = lp; out->th_img = th_img;
-        out->tile_image_bytes = image; out->gmin = gmin; out->rw = rw; out->task_cap = task_cap;
-        out->lds = fixed + 2 * static_cast<size_t>(out->list_lds);
-        return true;
-      }
-      return false;
-    };
-    bool found = false;
-    if (single_tile) {
-      const int T = (std::max(k.span_x, k.span_y) + 7) & ~7;
-      found = try_tile(T, kLdsOnePerCu, true, &g);
-      if (!found) single_tile = false;
-    }
-    if (!found) {
-      // The largest tile core that leaves room for two workgroups per CU, then the smallest core
-      // with the same number of tiles (less image to stage, more room for lists).
-      const int t_first = dbg.rt2d_tile > 0 ? (dbg.rt2d_tile & ~7) : 128;
-      for (int T = t_first; T >= 16 && !found; T -= 8) found = try_tile(T, kLdsTwoPerCu, false, &g);
-      if (found && dbg.rt2d_tile <= 0) {
-        TileGeometry smaller = g;
-        for (int T = g.T - 8; T >= 16; T -= 8) {
-          if ((k.span_x + T - 1) / T != g.ntx || (k.span_y + T - 1) / T != g.nty) break;
-          if (try_tile(T, kLdsTwoPerCu, false, &smaller)) g = smaller;
-        }
-      }
-    }
-    if (!found) return false;
-  }
-  // (classes of one launch share the shape: a class that needs several tiles puts all on shape 2)
-  if (!single_tile) {
-    for (Class& k : classes) {
-      if (k.g.ntx * k.g.nty == 1 && k.g.lds > kLdsTwoPerCu) {
-        // re-plan this class with the two-per-CU budget
-        TileGeometry& g = k.g;
-        const int side = 2 * k.nl + 1;
-        const int rows_extra = rpl * g.H;
-        const int cap_tile = k.n_pad + 64;
-        bool found = false;
-        for (int T = 128; T >= 16 && !found; T -= 8) {
-          const int ntx = (k.span_x + T - 1) / T, nty = (k.span_y + T - 1) / T;
-          if (ntx * nty > kMaxTiles) break;
-          const int lp = ConflictFreePitch(g.H, g.B, 2 * (T + 4 * g.B));
-          if (lp == 0) continue;
-          const int th_img = T + rows_extra;
-          const int image = ((th_img + rows_extra) * lp + 1023) & ~1023;
-          const int gmin = std::max(1, (k.scans + 63) / 64);
-          const int rw = (k.scans + gmin - 1) / gmin;
-          const int task_cap = rw * (k.n_pad / kPairTaskIters + 2);
-          const size_t fixed = static_cast<size_t>(image) + 4 * ((static_cast<size_t>(rw) * side * side + 3) & ~size_t{3}) +
-                               16 * static_cast<size_t>(rw) + 4 * ((static_cast<size_t>(rw) + 1 + 3) & ~size_t{3}) +
-                               16 * static_cast<size_t>(task_cap) + 64;
-          if (fixed + 2 * static_cast<size_t>(cap_tile) > kLdsTwoPerCu) continue;
-          const size_t want = static_cast<size_t>(rw) * cap_tile;
-          const size_t room = (kLdsTwoPerCu - fixed) / 2;
-          g.list_lds = static_cast<int>(std::min(want, room) & ~size_t{7});
-          g.T = T; g.ntx = ntx; g.nty = nty; g.lp = lp; g.th_img = th_img;
-          g.tile_image_bytes = image; g.gmin = gmin; g.rw = rw; g.task_cap = task_cap;
-          g.lds = fixed + 2 * static_cast<size_t>(g.list_lds);
-          found = true;
-        }
-        if (!found) return false;
-      }
-    }
-  }
-  I.tile_threads = single_tile ? 1024 : 512;
-  I.fused = single_tile && want_fused;
-  // Entries per work item: the whole batch in about two items per resident workgroup (an item
-  // costs ~4 us before its first window update: ticket, headers, lists, tasks, image), not less
-  // than two thousand entries (sixteen tasks: one per wavefront).
-  int launch_nb = 1;                     // block bounds: blocks per window axis, launch-wide
-  for (int m = 0; m < num; ++m) launch_nb = std::max(launch_nb, search[m].nl + 1);
-  const int tile_slots = std::max(1, (single_tile ? cus : 2 * cus) / I.share);
-  const int target = dbg.rt2d_target > 0
-                         ? dbg.rt2d_target
-                         : static_cast<int>(std::min<long long>(16384, std::max<long long>(2048, I.entries_total / (2ll * tile_slots))));
-  for (int m = 0; m < num; ++m) {
-    const Rt2DItem& it = items[m];
-    const Rt2DSearch& sr = search[m];
-    TileGeometry& g = geo[m];
-    const TileGeometry& cg = classes[class_of[m]].g;
-    const int nx = it.limits->num_x_cells, ny = it.limits->num_y_cells, nl = sr.nl;
-    const int side = 2 * nl + 1, n_pad = (it.n + 63) / 64 * 64;
-    g.T = cg.T; g.lp = cg.lp; g.th_img = cg.th_img; g.tile_image_bytes = cg.tile_image_bytes;
-    g.task_cap = cg.task_cap; g.list_lds = cg.list_lds; g.lds = cg.lds;
-    g.ntx = (span_x[m] + g.T - 1) / g.T;
-    g.nty = (span_y[m] + g.T - 1) / g.T;
-    // (rotations per workgroup: the class's -- its LDS is sized for that -- in as few groups as
-    // this match's own rotation count needs)
-    g.rw = std::min(cg.rw, sr.num_scans);
-    g.gmin = (sr.num_scans + g.rw - 1) / g.rw;
-    g.gmax = dbg.rt2d_groups > 0 ? std::max(I.fused ? 1 : g.gmin, std::min(dbg.rt2d_groups, sr.num_scans))
-                                 : std::max(g.gmin, std::min(sr.num_scans, 32));
-    g.target = target;
-    g.groups = 0;
-    if (I.fused) {                       // the planner's rule (Rt2DTilePrepKernel), on the host
-      const long long entries = static_cast<long long>(it.n) * sr.num_scans;
-      // (any number of groups: an item takes its rotations in rounds of g.rw)
-      long long G = std::max<long long>(1, (entries + target / 2) / target);
-      G = std::min<long long>(G, std::min(g.gmax, sr.num_scans));
-      g.groups = static_cast<int>(std::max<long long>(G, 1));
-    }
-    g.cap_s = n_pad + 16 * 4 * g.ntx * g.nty;
-    // the grid image: halo + grid, rows of whole 16-byte pieces, one zero row below (what lies
-    // right of or below it is zeros by definition: the tile DMA substitutes the zero corner)
-    g.gpitch = 2 * ((g.hl + nx + 7) & ~7);
-    g.grows = g.ht + ny + 1;
-    g.q_bytes = Align16(static_cast<size_t>(g.gpitch) * g.grows);
-    // the pooled planes (rt_2d_bounds.h) are part of the image whenever the window allows them,
-    // whichever kernel this call runs: a cached image serves both
-    g.m2_pitch = g.m2_rows = 0;
-    if (side <= 2 * kBoundMaxBlocks) {
-      // (room behind the last column a window reads: the bound kernel copies 8-byte pieces)
-      g.m2_pitch = (((nx + g.hl) >> 1) + 28 + 3) & ~3;
-      g.m2_rows = ((ny + g.ht) >> 1) + kBoundMaxBlocks + 2;
-    }
-    g.m4_pitch = g.m4_rows = 0;
-    if (side <= 2 * kBoundMaxBlocks) {
-      // (the sixteen phase planes of the 4 x 4 pooling: four block columns / rows and the 8-byte
-      // pieces of the LDS copy behind the last window start)
-      g.m4_pitch = (((nx + g.hl) >> 2) + 20 + 3) & ~3;
-      g.m4_rows = ((ny + g.ht) >> 2) + 4 + 2;
-    }
-    g.q8_bytes = g.m4_rows ? Align16(static_cast<size_t>(g.gpitch >> 1) * g.grows) : 0;
-    g.image_bytes = g.q_bytes + 4 * static_cast<size_t>(g.m2_pitch) * g.m2_rows +
-                    16 * static_cast<size_t>(g.m4_pitch) * g.m4_rows + g.q8_bytes;
-    {
-      const int nb = launch_nb;                         // (the kernel is instantiated for the largest)
-      // (rows are read as three aligned dwords and copied in 8-byte pieces; an odd number of
-      // 8-byte pieces: the rows of a wall on different banks)
-      g.b_lpb = ((g.T >> 1) + 12 + 4 + 7) & ~7;
-      if ((g.b_lpb & 15) == 0) g.b_lpb += 8;
-      g.b_lh = (g.T >> 1) + nb + 1;
-      // planes | zeros | cloud: what the finish of the match is laid out in afterwards
-      g.b_finish_room = 4 * static_cast<size_t>(g.b_lh) * g.b_lpb + ((static_cast<size_t>(nb) * g.b_lpb + 16 + 15) & ~size_t{15}) +
-                        8 * static_cast<size_t>(n_pad);
-      // | rotations | block sums (later: the summed candidates and their sums) | list | its sums
-      g.b_lds = 8 * ((static_cast<size_t>(sr.num_scans) + 1) & ~size_t{1}) +
-                4 * BoundSumWords(sr.num_scans * nb * nb) + 20 * size_t{kBoundListCap};   // (+ b_tail_at: below)
-      // 4 x 4 blocks: sixteen planes of (T / 4 + nb4 + 1) rows; a row holds T / 4 window starts,
-      // nb4 block columns, up to two columns in front (b4_c0 is a multiple of 4) and the seven
-      // bytes a shifted pair of dwords reads behind -- in an ODD number of 8-byte pieces (rows on
-      // different banks), the planes two banks apart (neighbouring cells lie in different planes)
-      const int nb4 = (launch_nb + 1) / 2;
-      g.b4_lpb = ((g.T >> 2) + nb4 + 9 + 7) & ~7;
-      if ((g.b4_lpb & 15) == 0) g.b4_lpb += 8;
-      g.b4_lh = (g.T >> 2) + nb4 + 1;
-      g.b4_pstride = g.b4_lh * g.b4_lpb;
-      g.b4_pstride += (8 - g.b4_pstride % 128 + 128) % 128;
-      g.b4_tail_at = 16 * static_cast<size_t>(g.b4_pstride) + ((static_cast<size_t>(nb4) * g.b4_lpb + 16 + 15) & ~size_t{15}) +
-                     8 * static_cast<size_t>(n_pad);
-      // the tail kernel's box of the byte image: every window start of the box plus the 4 nb4
-      // cells of the blocks, eight bytes for the shifted dword pair; an odd number of 8-byte pieces
-      g.b8_lp = (g.T + 4 * nb4 + 8 + 7) & ~7;
-      if ((g.b8_lp & 15) == 0) g.b8_lp += 8;
-      g.b8_lh = g.T + 4 * nb4;
-      g.t4_lds = BoundTail4Lds(g.b8_lp, g.b8_lh, n_pad, sr.num_scans, nb4);
-      // | rotations | block sums | discretisation constants (the tail kernel has LDS of its own)
-      g.b4_lds = g.b4_tail_at + 8 * ((static_cast<size_t>(sr.num_scans) + 1) & ~size_t{1}) +
-                 4 * ((static_cast<size_t>(sr.num_scans) * nb4 * nb4 + 3) & ~size_t{3}) +
-                 sizeof(BoundDisc) * static_cast<size_t>(sr.num_scans);
-    }
-    I.tile_lds = std::max(I.tile_lds, g.lds);
-    I.prep_lds = std::max<size_t>(I.prep_lds, 6 * static_cast<size_t>(n_pad) + 512);
-    I.lists_total += Align16(2 * static_cast<size_t>(sr.num_scans) * g.cap_s);
-    I.hdr_total += static_cast<size_t>(sr.num_scans) * g.ntx * g.nty * 4;
-    I.qsum_total += static_cast<size_t>(sr.num_scans) * side * side;
-    // (an upper bound of the planner's items: a tile's groups are capped by gmax and by its share
-    // of the entries, and the shares of a match's tiles add up to all its entries)
-    I.work_cap += I.fused ? g.groups
-                          : std::min<long long>(static_cast<long long>(g.ntx) * g.nty * g.gmax,
-                                                static_cast<long long>(it.n) * sr.num_scans / target +
-                                                    static_cast<long long>(g.ntx) * g.nty * (g.gmin + 1));
-    I.max_scans = std::max(I.max_scans, sr.num_scans);
-    const int stride = g.H * g.lp;
-    I.common_stride = m == 0 ? stride : (I.common_stride == stride ? stride : 0);
-    // finish kernel: cells + `group` probability rows + lists within 96 KB
-    const size_t fin_fixed = 4 * static_cast<size_t>(n_pad) + 4 * ((static_cast<size_t>(sr.num_scans) + 3) & ~size_t{3}) +
-                             12 * static_cast<size_t>(kStage1Cap) + 64 + 128;
-    const size_t row = 4 * (static_cast<size_t>(n_pad) + 4);
-    const size_t budget = 96 * 1024;
-    if (fin_fixed + row > budget) return false;
-    I.group = std::min<int>(I.group, static_cast<int>((budget - fin_fixed) / row));
-    I.finish_lds = std::max(I.finish_lds, fin_fixed);
-  }
+  Rt2DPlanCall call;
+  call.cus = I.cus; call.share = I.share; call.batch_matches = I.batch_matches;
+  call.dbg.rt2d_lds_kb = dbg.rt2d_lds_kb; call.dbg.rt2d_tile = dbg.rt2d_tile;
+  call.dbg.rt2d_unfused = dbg.rt2d_unfused; call.dbg.rt2d_groups = dbg.rt2d_groups;
+  call.dbg.rt2d_target = dbg.rt2d_target; call.dbg.rt2d_no_bounds = dbg.rt2d_no_bounds;
+  call.dbg.rt2d_bounds = dbg.rt2d_bounds; call.dbg.rt2d_bounds_verify = dbg.rt2d_bounds_verify;
+  call.dbg.rt2d_bounds_fused = dbg.rt2d_bounds_fused; call.dbg.rt2d_bounds_level = dbg.rt2d_bounds_level;
+  if (!PlanRt2DTiles(in.data(), num, call, &I.plan)) return false;
+  CMX_REQUIRE(I.plan.work_cap < (1ll << 24) && num <= 65535, "too many matches in one batch");
+  StageRt2DTiles(in.data(), num, I.plan, sizeof(Rt2DTileParams), &I.staging);
   {
-    size_t max_row = 0;
-    for (int m = 0; m < num; ++m) max_row = std::max<size_t>(max_row, 4 * (static_cast<size_t>((items[m].n + 63) / 64 * 64) + 4));
-    I.finish_lds += static_cast<size_t>(I.group) * max_row;
-  }
-  // ---- block bounds first (rt_2d_bounds.h): every match ONE work item of the bound kernel, two
-  // workgroups of 512 threads per CU where their LDS allows.  Not for windows beyond 16 x 16
-  // cells (the block columns of a row are one 8-byte read) -- the exhaustive tile kernel keeps
-  // those, and stays the parity partner behind the debug switch.
-  // From kBoundMinMatches matches per call on: below, the tile kernel's finer work items (a match
-  // in four or more, none of which waits for a last one) give the shorter call -- measured on C1,
-  // bounds / tiles: 1 match 62 / 52 us, 16: 92 / 74, 128: 114 - 126 / 117 (on 400 x 400 grids
-  // 139 - 161 / 106), 256: 144 / 168, 1024: 330 - 357 / 449 - 503 (profiles/r05_c1_bounds.txt).
-  // Debug switches: rt2d_bounds = 1 always, rt2d_no_bounds never.
-  I.bounds = I.fused && !dbg.rt2d_no_bounds && (I.batch_matches >= kBoundMinMatches || dbg.rt2d_bounds);
-  // (round 6) the tail of a match -- phases B, C and the finish: ~30 us of dependent round trips
-  // during which a workgroup's 70 KB of LDS and its place on the CU did nothing -- in a kernel of
-  // its own behind the bound kernel (Rt2DBoundTailKernel: 33 KB, every match of the part in flight
-  // at once).  rt2d_bounds_fused = 1: one kernel as in round 5 (the parity partner; verify mode).
-  I.split = I.bounds && !dbg.rt2d_bounds_verify && !dbg.rt2d_bounds_fused;
-  // (round 6) blocks of 4 x 4 translations first, their survivors refined by the tail kernel:
-  // rt2d_bounds_level = 2 keeps the 2 x 2 blocks as the first level (the parity partner)
-  I.level4 = I.bounds && !dbg.rt2d_bounds_fused && dbg.rt2d_bounds_level != 2;
-  for (int m = 0; m < num && I.bounds; ++m) {
-    const int side = 2 * search[m].nl + 1;
-    // (the fused bound kernel finishes a match itself, in the LDS of its planes and cloud -- a
-    // small box leaves less than the finish needs: the rest of the layout moves back)
-    geo[m].b_tail_at = I.split ? geo[m].b_finish_room : std::max(geo[m].b_finish_room, Align16(I.finish_lds));
-    I.tail_lds = std::max(I.tail_lds, BoundTailLds((items[m].n + 63) / 64 * 64, search[m].num_scans, launch_nb));
-    geo[m].b_lds += geo[m].b_tail_at;
-    I.bounds = side <= 2 * kBoundMaxBlocks && geo[m].b_lds <= 150 * size_t{1024};
-    I.bound_nb = std::max(I.bound_nb, (side + 1) / 2);
-    I.bound_lds = std::max(I.bound_lds, geo[m].b_lds);
-    I.bound4_lds = std::max(I.bound4_lds, geo[m].b4_lds);
-    I.tail4_lds = std::max(I.tail4_lds, geo[m].t4_lds);
-  }
-  I.level4 = I.level4 && I.bounds && I.bound4_lds <= 150 * size_t{1024};
-  if (I.level4) { I.split = true; I.bound_lds = I.bound4_lds; }
-  if (I.bounds) {
-    // rotation groups per match: about two items per CU over the whole call (an item stages the
-    // match's planes and cloud: ~4 us), one per match in large batches
-    const int per_cu = I.bound_lds <= 78 * size_t{1024} ? 2 : 1;
-    const int slots = std::max(1, per_cu * cus / I.share);
-    I.work_cap = 0;
-    for (int m = 0; m < num; ++m) {
-      const int G = dbg.rt2d_groups > 0 ? dbg.rt2d_groups : slots / num;
-      geo[m].groups = std::max(1, std::min(G, search[m].num_scans));
-      I.work_cap += geo[m].groups;
-    }
-  }
-  CMX_REQUIRE(I.work_cap < (1ll << 24) && num <= 65535, "too many matches in one batch");
-  {
-    I.table_at.resize(num);
-    size_t at = 0;
-    for (int m = 0; m < num; ++m) { I.table_at[m] = at; at += search[m].num_scans; }
-    I.tables.resize(at);
+    I.tables.resize(I.plan.tables_total);
     // (libm, ~5 ns per pair, a third of a match's host time and nothing shared: blocks of >= 32
-    // matches over the host pool)
     // matches, six blocks at most, over the host pool)
     const int blocks = std::min(6, (num + 31) / 32);
     ParallelFor(blocks, dbg.rt2d_tables_serial ? (1 << 30) : 3, [&](int b) {
       const int begin = static_cast<int>(static_cast<long long>(num) * b / blocks);
       const int end = static_cast<int>(static_cast<long long>(num) * (b + 1) / blocks);
       for (int m = begin; m < end; ++m)
-        FillRotationTable(search[m].step, search[m].na, I.tables.data() + I.table_at[m]);
+        FillRotationTable(search[m].step, search[m].na, I.tables.data() + I.plan.at[m].table);
     });
-  }
-  I.tile_grid = static_cast<int>(std::max<long long>(1, std::min<long long>(tile_slots, I.work_cap)));
-  if (I.bounds) {
-    const int per_cu = I.bound_lds <= 78 * size_t{1024} ? 2 : 1;
-    // (the whole chip even when the call is one part of a batch: the workgroups are persistent and
-    // two of them share a CU -- a part whose grid is its share of the CUs leaves a wavefront per
-    // SIMD short of hiding the LDS latency of phase A whenever the parts do not overlap)
-    I.tile_grid = static_cast<int>(std::max<long long>(1, std::min<long long>(per_cu * cus, I.work_cap)));
   }
   return true;
 }
 
-void Rt2DTileCall::Enqueue(hipStream_t on_stream) {
-  Impl& I = *impl_;
+// ---- staging buffer and scratch; the counters zeroed, the fused path's work items listed --------
+void Rt2DTileCall::Impl::ReserveBuffers(hipStream_t on_stream) {
   const DebugOptions& dbg = Debug();
-  const auto t_enter = std::chrono::steady_clock::now();
-  const auto lap_us = [&]() {
-    return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t_enter).count();
-  };
-  double t_images = 0, t_params = 0, t_upload = 0;
-  const Rt2DItem* items = I.items;
-  const Rt2DSearch* search = I.search;
-  const int num = I.num, device = I.device, rpl = I.rpl;
-  const std::vector<TileGeometry>& geo = I.geo;
-  // ---- staging: params | per item: xyz, rotations, cells | counters | misc ------------------
-  struct Off { size_t xyz, rot, cells; };
-  std::vector<Off> off(num);
-  size_t in_bytes = Align16(sizeof(Rt2DTileParams) * num);
-  for (int m = 0; m < num; ++m) {
-    const Rt2DItem& it = items[m];
-    off[m].xyz = in_bytes;
-    off[m].rot = off[m].xyz + (it.device_xyz ? 0 : Align16(3 * sizeof(float) * it.n));
-    off[m].cells = off[m].rot + Align16(sizeof(float2) * search[m].num_scans);
-    in_bytes = off[m].cells + (it.device_cells ? 0 : Align16(sizeof(uint16_t) * static_cast<size_t>(it.limits->num_x_cells) * it.limits->num_y_cells));
-  }
-  const size_t off_counters = in_bytes;               // [0] work items, [1] next item (zeroed)
-  in_bytes += 64;
-  const size_t off_tickets = in_bytes;                // block bounds: a ticket counter per match (zeroed)
-  if (I.bounds) in_bytes += Align16(sizeof(int) * static_cast<size_t>(num));
-  const size_t off_work = in_bytes;                   // fused: the work items, listed here
-  if (I.fused) in_bytes += Align16(3 * sizeof(int4) * static_cast<size_t>(I.work_cap));
-  const size_t off_misc = in_bytes;
-  in_bytes += Align16(sizeof(unsigned) * 128 * static_cast<size_t>(num));
-
-  I.ws.reset(new WorkspaceLease(device));
-  WorkspaceLease& ws = *I.ws;
+  const Rt2DPlan& L = plan;
+  const Rt2DStaging& S = staging;
+  const std::vector<TileGeometry>& geo = L.geo;
+  this->ws.reset(new WorkspaceLease(device));
+  WorkspaceLease& ws = *this->ws;
   if (on_stream) ws->stream = on_stream;      // (a lease sets its workspace's stream anew every time)
-  char* h_in = ws->pinned[0].ReserveAs<char>(in_bytes);
-  char* d_in = ws->dev[0].ReserveAs<char>(in_bytes);
-  uint16_t* d_lists = I.fused ? nullptr : reinterpret_cast<uint16_t*>(ws->dev[1].Reserve(I.lists_total + 64));
-  uint32_t* d_hdr = I.fused ? nullptr : ws->dev[2].ReserveAs<uint32_t>(I.hdr_total + 16);
-  int* d_qsum = ws->dev[3].ReserveAs<int>(I.qsum_total + 16);
-  I.d_overflow = ws->dev[4].ReserveAs<unsigned>(static_cast<size_t>(num) * 2 * (kFinalistCap - kFinalistHead));
-  int4* d_work = I.fused ? reinterpret_cast<int4*>(d_in + off_work)
-                         : ws->dev[8].ReserveAs<int4>(static_cast<size_t>(I.work_cap) + 1);
-  I.h_misc = ws->pinned[1].ReserveAs<unsigned>(static_cast<size_t>(num) * 128);
-  unsigned* d_misc = reinterpret_cast<unsigned*>(d_in + off_misc);
-  int* d_counters = reinterpret_cast<int*>(d_in + off_counters);
-  std::memset(h_in + off_counters, 0, 64);
-  if (I.bounds) std::memset(h_in + off_tickets, 0, Align16(sizeof(int) * static_cast<size_t>(num)));
+  h_in = ws->pinned[0].ReserveAs<char>(S.bytes);
+  d_in = ws->dev[0].ReserveAs<char>(S.bytes);
+  d_lists = L.fused ? nullptr : reinterpret_cast<uint16_t*>(ws->dev[1].Reserve(L.lists_total + 64));
+  d_hdr = L.fused ? nullptr : ws->dev[2].ReserveAs<uint32_t>(L.hdr_total + 16);
+  d_qsum = ws->dev[3].ReserveAs<int>(L.qsum_total + 16);
+  d_overflow = ws->dev[4].ReserveAs<unsigned>(static_cast<size_t>(num) * 2 * (kFinalistCap - kFinalistHead));
+  d_work = L.fused ? reinterpret_cast<int4*>(d_in + S.work)
+                   : ws->dev[8].ReserveAs<int4>(static_cast<size_t>(L.work_cap) + 1);
+  h_misc = ws->pinned[1].ReserveAs<unsigned>(static_cast<size_t>(num) * 128);
+  d_misc = reinterpret_cast<unsigned*>(d_in + S.misc);
+  d_counters = reinterpret_cast<int*>(d_in + S.counters);
+  std::memset(h_in + S.counters, 0, 64);
+  if (L.bounds) std::memset(h_in + S.tickets, 0, Align16(sizeof(int) * static_cast<size_t>(num)));
   // (block sums of matches bounded by several workgroups; read only where groups > 1)
-  std::vector<int> ub_at(num, 0);
-  size_t ub_total = 0;
-  for (int m = 0; m < num && I.bounds; ++m) {
-    ub_at[m] = static_cast<int>(ub_total);
-    const int nb_level = I.level4 ? (I.bound_nb + 1) / 2 : I.bound_nb;
-    ub_total += static_cast<size_t>(search[m].num_scans) * nb_level * nb_level;
-  }
-  int* d_ub = I.bounds ? ws->dev[6].ReserveAs<int>(ub_total + 16) : nullptr;
-  if (I.fused) {
-    int4* h_work = reinterpret_cast<int4*>(h_in + off_work);
+  d_ub = L.bounds ? ws->dev[6].ReserveAs<int>(L.ub_total + 16) : nullptr;
+  if (L.fused) {
+    int4* h_work = reinterpret_cast<int4*>(h_in + S.work);
     int count = 0;
     for (int m = 0; m < num; ++m) {
       const uintptr_t xyz = reinterpret_cast<uintptr_t>(
-          items[m].device_xyz ? items[m].device_xyz : reinterpret_cast<const float*>(d_in + off[m].xyz));
-      const uintptr_t rot = reinterpret_cast<uintptr_t>(d_in + off[m].rot);
+          items[m].device_xyz ? items[m].device_xyz : reinterpret_cast<const float*>(d_in + S.match[m].xyz));
+      const uintptr_t rot = reinterpret_cast<uintptr_t>(d_in + S.match[m].rot);
       for (int g = 0; g < geo[m].groups; ++g, ++count) {
         h_work[3 * count] = make_int4(m, 0, g, geo[m].groups);
         h_work[3 * count + 1] = make_int4(static_cast<int>(static_cast<uint32_t>(xyz)), static_cast<int>(static_cast<uint32_t>(xyz >> 32)),
@@ -1936,22 +1500,28 @@ void Rt2DTileCall::Enqueue(hipStream_t on_stream) {
         h_work[3 * count + 2] = make_int4(items[m].n, search[m].num_scans, 0, 0);
       }
     }
-    reinterpret_cast<int*>(h_in + off_counters)[0] = count;
+    reinterpret_cast<int*>(h_in + S.counters)[0] = count;
   }
-  const int timeline_tile_slots = I.tile_grid * 4;
+  timeline_tile_slots = L.tile_grid * 4;
   if (dbg.timeline) {
     const size_t bytes = (static_cast<size_t>(timeline_tile_slots) + num) * kTimelineStamps * 8;
-    I.d_timeline = static_cast<unsigned long long*>(ws->dev[7].Reserve(bytes));
-    CMX_HIP(hipMemsetAsync(I.d_timeline, 0, bytes, ws->stream));
+    d_timeline = static_cast<unsigned long long*>(ws->dev[7].Reserve(bytes));
+    CMX_HIP(hipMemsetAsync(d_timeline, 0, bytes, ws->stream));
   }
+}
 
-  // ---- grid images: a resident grid keeps its own (two buffers per grid); everything else is
-  // built into scratch by this call ---------------------------------------------------------
+// ---- grid images: a resident grid keeps its own (two buffers per grid); everything else is
+// built into scratch by this call ---------------------------------------------------------
+void Rt2DTileCall::Impl::AcquireImages() {
+  const DebugOptions& dbg = Debug();
+  const std::vector<TileGeometry>& geo = plan.geo;
+  WorkspaceLease& ws = *this->ws;
   size_t scratch_images = 0;
-  std::vector<uint16_t*> image_of(num, nullptr);
+  image_of.assign(num, nullptr);
   std::vector<long long> scratch_at(num, -1);       // offset in this call's scratch (-1: cached)
-  std::vector<int> build_image(num, 0), same_as(num, -1);
-  I.holds.stream = ws->stream;
+  build_image.assign(num, 0);
+  std::vector<int> same_as(num, -1);
+  holds.stream = ws->stream;
   std::unordered_map<GridKey, int, GridKeyHash> first_of;
   first_of.reserve(static_cast<size_t>(num));
   for (int m = 0; m < num; ++m) {
@@ -1970,7 +1540,7 @@ void Rt2DTileCall::Enqueue(hipStream_t on_stream) {
     if (c && items[m].device_cells && !dbg.rt2d_no_image_cache) {
       buffer = c->Acquire(items[m].grid_version, search[m].nl, g.gpitch, g.grows, g.image_bytes, &build);
       if (buffer >= 0) {
-        I.holds.holds.push_back(CacheHold{c, buffer, build, items[m].grid_version, search[m].nl, g.gpitch, g.grows});
+        holds.holds.push_back(CacheHold{c, buffer, build, items[m].grid_version, search[m].nl, g.gpitch, g.grows});
         image_of[m] = c->buffer[buffer].image;
       }
     }
@@ -1986,96 +1556,91 @@ void Rt2DTileCall::Enqueue(hipStream_t on_stream) {
     if (scratch_at[m] >= 0) image_of[m] = reinterpret_cast<uint16_t*>(d_images + scratch_at[m]);
   for (int m = 0; m < num; ++m)
     if (same_as[m] >= 0) image_of[m] = image_of[same_as[m]];
+}
 
-  t_images = lap_us();
-  // ---- parameters -------------------------------------------------------------------------------
+// ---- parameters: a block per match, with its cloud, rotation table and cells behind where they
+// are not resident ------------------------------------------------------------------------------
+void Rt2DTileCall::Impl::FillParams() {
+  const DebugOptions& dbg = Debug();
+  const Rt2DPlan& L = plan;
+  const Rt2DStaging& S = staging;
+  const std::vector<TileGeometry>& geo = L.geo;
+  const int rpl = L.rpl;
   Rt2DTileParams* h_params = reinterpret_cast<Rt2DTileParams*>(h_in);
-  {
-    size_t lists_at = 0, hdr_at = 0, qsum_at = 0;
-    std::vector<size_t> lists_off(num), hdr_off(num), qsum_off(num);
-    for (int m = 0; m < num; ++m) {
-      const TileGeometry& g = geo[m];
-      const int side = 2 * search[m].nl + 1;
-      lists_off[m] = lists_at; lists_at += Align16(2 * static_cast<size_t>(search[m].num_scans) * g.cap_s);
-      hdr_off[m] = hdr_at; hdr_at += static_cast<size_t>(search[m].num_scans) * g.ntx * g.nty * 4;
-      qsum_off[m] = qsum_at; qsum_at += static_cast<size_t>(search[m].num_scans) * side * side;
-    }
-    const cmx_rt_options* options = I.options;
-    unsigned long long* d_timeline = I.d_timeline;
-    unsigned* d_overflow = I.d_overflow;
-    // (resident grids and clouds: a fraction of a microsecond per match, and dispatching to the
-    // host pool costs ~25 us; host grids are copied into the staging buffer here: worth the pool)
-    bool copies = false;
-    for (int m = 0; m < num; ++m) copies = copies || !items[m].device_cells;
-    ParallelFor(num, copies ? 16 : (dbg.rt2d_host_par > 0 ? dbg.rt2d_host_par : 4096), [&](int m) {
-      const Rt2DItem& it = items[m];
-      const Rt2DSearch& sr = search[m];
-      const TileGeometry& g = geo[m];
-      const size_t cell_count = static_cast<size_t>(it.limits->num_x_cells) * it.limits->num_y_cells;
-      if (!it.device_xyz) std::memcpy(h_in + off[m].xyz, it.xyz, 3 * sizeof(float) * it.n);
-      std::memcpy(h_in + off[m].rot, I.tables.data() + I.table_at[m], sizeof(float2) * sr.num_scans);
-      if (!it.device_cells) std::memcpy(h_in + off[m].cells, it.cells, sizeof(uint16_t) * cell_count);
-      Rt2DTileParams P{};
-      P.cells = it.device_cells ? it.device_cells : reinterpret_cast<const uint16_t*>(d_in + off[m].cells);
-      P.nx = it.limits->num_x_cells; P.ny = it.limits->num_y_cells;
-      P.res = it.limits->resolution; P.max_x = it.limits->max_x; P.max_y = it.limits->max_y;
-      P.inv_res = 1.0 / P.res;
-      P.tx = static_cast<float>(it.initial->x);
-      P.ty = static_cast<float>(it.initial->y);
-      P.init_qw = sr.q0w; P.init_qz = sr.q0z;
-      P.nl = sr.nl; P.num_scans = sr.num_scans; P.num_angular = sr.na;
-      P.step = sr.step;
-      P.wt = options->translation_delta_cost_weight;
-      P.wr = options->rotation_delta_cost_weight;
-      P.scan_rot = reinterpret_cast<const float2*>(d_in + off[m].rot);
-      P.xyz = it.device_xyz ? it.device_xyz : reinterpret_cast<const float*>(d_in + off[m].xyz);
-      P.n = it.n; P.n_pad = (it.n + 63) / 64 * 64;
-      P.B = g.B; P.H = g.H; P.rpl = rpl; P.hl = g.hl; P.ht = g.ht;
-      P.qimage = image_of[m]; P.gpitch = g.gpitch; P.grows = g.grows; P.image_build = build_image[m];
-      P.box_x0 = g.box_x0; P.box_y0 = g.box_y0; P.T = g.T;
-      P.T_magic = static_cast<unsigned>((0x100000000ull + g.T - 1) / g.T);
-      P.ntx = g.ntx; P.nty = g.nty; P.lp = g.lp; P.th_img = g.th_img;
-      P.tile_image_bytes = g.tile_image_bytes; P.null_addr = g.th_img * g.lp;
-      P.lists = d_lists ? d_lists + lists_off[m] / 2 : nullptr; P.cap_s = g.cap_s;
-      P.hdr = d_hdr ? d_hdr + hdr_off[m] : nullptr;
-      P.fused = I.fused ? 1 : 0;
-      P.gmin = g.gmin; P.gmax = g.gmax; P.target = g.target; P.rw = g.rw;
-      P.list_lds = g.list_lds; P.task_cap = g.task_cap;
-      P.flush_atomic = g.ntx * g.nty > 1 ? 1 : 0;
-      P.qsum = d_qsum + qsum_off[m];
-      P.misc = d_misc + static_cast<size_t>(m) * 128;
-      P.overflow = d_overflow + static_cast<size_t>(m) * 2 * (kFinalistCap - kFinalistHead);
-      P.stage = P.misc + 126;
-      P.timeline = d_timeline;
-      P.timeline_finish_base = timeline_tile_slots;
-      P.m2 = g.m2_rows ? reinterpret_cast<const uint8_t*>(image_of[m]) + g.q_bytes : nullptr;
-      P.m2_pitch = g.m2_pitch; P.m2_rows = g.m2_rows;
-      P.b_c0 = (g.box_x0 >> 1) & ~3; P.b_r0 = g.box_y0 >> 1;
-      P.b_lpb = g.b_lpb; P.b_lh = g.b_lh; P.b_tail_at = static_cast<int>(g.b_tail_at);
-      P.m4 = g.m4_rows ? P.m2 + 4 * static_cast<size_t>(g.m2_pitch) * g.m2_rows : nullptr;
-      P.m4_pitch = g.m4_pitch; P.m4_rows = g.m4_rows;
-      P.b4_c0 = (g.box_x0 >> 2) & ~3; P.b4_r0 = g.box_y0 >> 2;
-      P.b4_lpb = g.b4_lpb; P.b4_lh = g.b4_lh; P.b4_pstride = g.b4_pstride;
-      P.b4_tail_at = static_cast<int>(g.b4_tail_at);
-      P.b4_ub_at = ub_at[m];
-      P.q8 = g.q8_bytes ? const_cast<uint8_t*>(P.m4) + 16 * static_cast<size_t>(g.m4_pitch) * g.m4_rows : nullptr;
-      P.b8_lp = g.b8_lp; P.b8_lh = g.b8_lh;
-      P.bstat = P.misc + 124;
-      P.b_verify = dbg.rt2d_bounds_verify ? 1 : 0;
-      P.b_ub_at = ub_at[m];
-      h_params[m] = P;
-    });
-  }
+  // (resident grids and clouds: a fraction of a microsecond per match, and dispatching to the
+  // host pool costs ~25 us; host grids are copied into the staging buffer here: worth the pool)
+  bool copies = false;
+  for (int m = 0; m < num; ++m) copies = copies || !items[m].device_cells;
+  ParallelFor(num, copies ? 16 : (dbg.rt2d_host_par > 0 ? dbg.rt2d_host_par : 4096), [&](int m) {
+    const Rt2DItem& it = items[m];
+    const Rt2DSearch& sr = search[m];
+    const TileGeometry& g = geo[m];
+    const Rt2DStagingAt& off = S.match[m];
+    const Rt2DMatchAt& at = L.at[m];
+    const size_t cell_count = static_cast<size_t>(it.limits->num_x_cells) * it.limits->num_y_cells;
+    if (!it.device_xyz) std::memcpy(h_in + off.xyz, it.xyz, 3 * sizeof(float) * it.n);
+    std::memcpy(h_in + off.rot, tables.data() + at.table, sizeof(float2) * sr.num_scans);
+    if (!it.device_cells) std::memcpy(h_in + off.cells, it.cells, sizeof(uint16_t) * cell_count);
+    Rt2DTileParams P{};
+    P.cells = it.device_cells ? it.device_cells : reinterpret_cast<const uint16_t*>(d_in + off.cells);
+    P.nx = it.limits->num_x_cells; P.ny = it.limits->num_y_cells;
+    P.res = it.limits->resolution; P.max_x = it.limits->max_x; P.max_y = it.limits->max_y;
+    P.inv_res = 1.0 / P.res;
+    P.tx = static_cast<float>(it.initial->x);
+    P.ty = static_cast<float>(it.initial->y);
+    P.init_qw = sr.q0w; P.init_qz = sr.q0z;
+    P.nl = sr.nl; P.num_scans = sr.num_scans; P.num_angular = sr.na;
+    P.step = sr.step;
+    P.wt = options->translation_delta_cost_weight;
+    P.wr = options->rotation_delta_cost_weight;
+    P.scan_rot = reinterpret_cast<const float2*>(d_in + off.rot);
+    P.xyz = it.device_xyz ? it.device_xyz : reinterpret_cast<const float*>(d_in + off.xyz);
+    P.n = it.n; P.n_pad = (it.n + 63) / 64 * 64;
+    P.B = g.B; P.H = g.H; P.rpl = rpl; P.hl = g.hl; P.ht = g.ht;
+    P.qimage = image_of[m]; P.gpitch = g.gpitch; P.grows = g.grows; P.image_build = build_image[m];
+    P.box_x0 = g.box_x0; P.box_y0 = g.box_y0; P.T = g.T;
+    P.T_magic = static_cast<unsigned>((0x100000000ull + g.T - 1) / g.T);
+    P.ntx = g.ntx; P.nty = g.nty; P.lp = g.lp; P.th_img = g.th_img;
+    P.tile_image_bytes = g.tile_image_bytes; P.null_addr = g.th_img * g.lp;
+    P.lists = d_lists ? d_lists + at.lists / 2 : nullptr; P.cap_s = g.cap_s;
+    P.hdr = d_hdr ? d_hdr + at.hdr : nullptr;
+    P.fused = L.fused ? 1 : 0;
+    P.gmin = g.gmin; P.gmax = g.gmax; P.target = g.target; P.rw = g.rw;
+    P.list_lds = g.list_lds; P.task_cap = g.task_cap;
+    P.flush_atomic = g.ntx * g.nty > 1 ? 1 : 0;
+    P.qsum = d_qsum + at.qsum;
+    P.misc = d_misc + static_cast<size_t>(m) * 128;
+    P.overflow = d_overflow + static_cast<size_t>(m) * 2 * (kFinalistCap - kFinalistHead);
+    P.stage = P.misc + 126;
+    P.timeline = d_timeline;
+    P.timeline_finish_base = timeline_tile_slots;
+    P.m2 = g.m2_rows ? reinterpret_cast<const uint8_t*>(image_of[m]) + g.q_bytes : nullptr;
+    P.m2_pitch = g.m2_pitch; P.m2_rows = g.m2_rows;
+    P.b_c0 = (g.box_x0 >> 1) & ~3; P.b_r0 = g.box_y0 >> 1;
+    P.b_lpb = g.b_lpb; P.b_lh = g.b_lh; P.b_tail_at = static_cast<int>(g.b_tail_at);
+    P.m4 = g.m4_rows ? P.m2 + 4 * static_cast<size_t>(g.m2_pitch) * g.m2_rows : nullptr;
+    P.m4_pitch = g.m4_pitch; P.m4_rows = g.m4_rows;
+    P.b4_c0 = (g.box_x0 >> 2) & ~3; P.b4_r0 = g.box_y0 >> 2;
+    P.b4_lpb = g.b4_lpb; P.b4_lh = g.b4_lh; P.b4_pstride = g.b4_pstride;
+    P.b4_tail_at = static_cast<int>(g.b4_tail_at);
+    P.b4_ub_at = at.ub;
+    P.q8 = g.q8_bytes ? const_cast<uint8_t*>(P.m4) + 16 * static_cast<size_t>(g.m4_pitch) * g.m4_rows : nullptr;
+    P.b8_lp = g.b8_lp; P.b8_lh = g.b8_lh;
+    P.bstat = P.misc + 124;
+    P.b_verify = dbg.rt2d_bounds_verify ? 1 : 0;
+    P.b_ub_at = at.ub;
+    h_params[m] = P;
+  });
   // (the stage counters ride in the last words of a match's slot: the finalist head must stop short)
   static_assert(2 + 2 * kFinalistHead <= 124, "a match's head, bound and stage counters share 128 words");
-  t_params = lap_us();
-  // (the matches' result words -- 512 bytes each, the last region of the buffer -- are zeroed by
-  // the copy kernel itself: 40 % of the upload did not have to cross the bus)
-  SmallCopyAsync(d_in, h_in, off_misc, /*to_device=*/true, ws->stream, d_in + off_misc, in_bytes - off_misc);
-  t_upload = lap_us();
-  const Rt2DTileParams* d_params = reinterpret_cast<const Rt2DTileParams*>(d_in);
+}
 
-  RecordEvent(ws->ev_begin, ws->stream);
+// ---- the derived images of the grids this call builds, then the lists of the unfused path -------
+void Rt2DTileCall::Impl::LaunchImageKernels(const Rt2DTileParams* d_params) {
+  const DebugOptions& dbg = Debug();
+  const Rt2DPlan& L = plan;
+  const std::vector<TileGeometry>& geo = L.geo;
+  WorkspaceLease& ws = *this->ws;
   {
     bool any_build = false;
     size_t max_vecs = 0, max_words = 0, max_words4 = 0;
@@ -2101,50 +1666,58 @@ void Rt2DTileCall::Enqueue(hipStream_t on_stream) {
         Rt2DPool4Kernel<<<dim3(DivUp(max_words4, 256), num), 256, 0, ws->stream>>>(d_params);
     }
   }
-  if (!I.fused)
-    Rt2DTilePrepKernel<<<dim3(I.max_scans, num), 256, I.prep_lds, ws->stream>>>(
-        d_params, d_counters, d_work, static_cast<int>(I.work_cap));
-  RecordEvent(ws->ev_k0, ws->stream);
+  if (!L.fused)
+    Rt2DTilePrepKernel<<<dim3(L.max_scans, num), 256, L.prep_lds, ws->stream>>>(
+        d_params, d_counters, d_work, static_cast<int>(L.work_cap));
+}
+
+// ---- the bound kernel and its tail, or the tile kernel; then the finish kernel where the matches
+// have not been finished yet ----------------------------------------------------------------------
+void Rt2DTileCall::Impl::LaunchMatchKernels(const Rt2DTileParams* d_params) {
+  const DebugOptions& dbg = Debug();
+  const Rt2DPlan& L = plan;
+  const int rpl = L.rpl;
+  WorkspaceLease& ws = *this->ws;
   {
     const auto launch = [&](auto kernel) {
       OptInLds(reinterpret_cast<const void*>(kernel), device, 160 * 1024 - 1024);   // (minus the static words)
       if (dbg.host_trace) {
         int resident = 0;
-        (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&resident, kernel, I.tile_threads, I.tile_lds);
+        (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&resident, kernel, L.tile_threads, L.tile_lds);
         fprintf(stderr, "[cmx host] rt2d tile kernel: %d workgroups of %d threads, %zu B of LDS each, "
-                        "%d resident per CU\n", I.tile_grid, I.tile_threads, I.tile_lds, resident);
+                        "%d resident per CU\n", L.tile_grid, L.tile_threads, L.tile_lds, resident);
       }
-      kernel<<<static_cast<unsigned>(I.tile_grid), I.tile_threads, I.tile_lds, ws->stream>>>(
-          d_params, d_work, d_counters, d_counters + 1, I.fused ? 3 : 1);
+      kernel<<<static_cast<unsigned>(L.tile_grid), L.tile_threads, L.tile_lds, ws->stream>>>(
+          d_params, d_work, d_counters, d_counters + 1, L.fused ? 3 : 1);
     };
     const auto launch_bounds = [&](auto kernel) {
       OptInLds(reinterpret_cast<const void*>(kernel), device, 160 * 1024 - 4096);
       if (dbg.host_trace) {
         int resident = 0;
-        (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&resident, kernel, kBoundThreads, I.bound_lds);
+        (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&resident, kernel, kBoundThreads, L.bound_lds);
         fprintf(stderr, "[cmx host] rt2d bound kernel<%d>: %d workgroups of %d threads, %zu B of LDS each, "
-                        "%d resident per CU\n", I.bound_nb, I.tile_grid, kBoundThreads, I.bound_lds, resident);
+                        "%d resident per CU\n", L.bound_nb, L.tile_grid, kBoundThreads, L.bound_lds, resident);
       }
-      kernel<<<static_cast<unsigned>(I.tile_grid), kBoundThreads, I.bound_lds, ws->stream>>>(
-          d_params, d_work, d_counters, d_counters + 1, reinterpret_cast<int*>(d_in + off_tickets), d_ub,
-          I.group, I.h_misc, I.split ? 1 : 0);
+      kernel<<<static_cast<unsigned>(L.tile_grid), kBoundThreads, L.bound_lds, ws->stream>>>(
+          d_params, d_work, d_counters, d_counters + 1, reinterpret_cast<int*>(d_in + staging.tickets), d_ub,
+          L.group, h_misc, L.split ? 1 : 0);
     };
     const auto launch_tail = [&](auto kernel) {
       OptInLds(reinterpret_cast<const void*>(kernel), device, 160 * 1024 - 4096);
-      kernel<<<static_cast<unsigned>(num), I.level4 ? kBoundTail4Threads : kBoundTailThreads,
-               I.level4 ? I.tail4_lds : I.tail_lds, ws->stream>>>(d_params, d_ub, I.h_misc);
+      kernel<<<static_cast<unsigned>(num), L.level4 ? kBoundTail4Threads : kBoundTailThreads,
+               L.level4 ? L.tail4_lds : L.tail_lds, ws->stream>>>(d_params, d_ub, h_misc);
     };
-    const int common_stride = I.common_stride;
-    if (I.level4) {
+    const int common_stride = L.common_stride;
+    if (L.level4) {
       // (ev_k1 between the two: the bound kernel's own span)
-      switch ((I.bound_nb + 1) / 2) {
+      switch ((L.bound_nb + 1) / 2) {
         case 1: launch_bounds(Rt2DBoundKernel<1, 2>); RecordEvent(ws->ev_k1, ws->stream); launch_tail(Rt2DBoundTail4Kernel<1>); break;
         case 2: launch_bounds(Rt2DBoundKernel<2, 2>); RecordEvent(ws->ev_k1, ws->stream); launch_tail(Rt2DBoundTail4Kernel<2>); break;
         case 3: launch_bounds(Rt2DBoundKernel<3, 2>); RecordEvent(ws->ev_k1, ws->stream); launch_tail(Rt2DBoundTail4Kernel<3>); break;
         default: launch_bounds(Rt2DBoundKernel<4, 2>); RecordEvent(ws->ev_k1, ws->stream); launch_tail(Rt2DBoundTail4Kernel<4>); break;
       }
-    } else if (I.bounds) {
-      switch (I.bound_nb) {
+    } else if (L.bounds) {
+      switch (L.bound_nb) {
         case 1: launch_bounds(Rt2DBoundKernel<1, 1>); break;
         case 2: launch_bounds(Rt2DBoundKernel<2, 1>); break;
         case 3: launch_bounds(Rt2DBoundKernel<3, 1>); break;
@@ -2154,8 +1727,8 @@ void Rt2DTileCall::Enqueue(hipStream_t on_stream) {
         case 7: launch_bounds(Rt2DBoundKernel<7, 1>); break;
         default: launch_bounds(Rt2DBoundKernel<8, 1>); break;
       }
-      if (I.split) {
-        switch (I.bound_nb) {
+      if (L.split) {
+        switch (L.bound_nb) {
           case 1: launch_tail(Rt2DBoundTailKernel<1>); break;
           case 2: launch_tail(Rt2DBoundTailKernel<2>); break;
           case 3: launch_tail(Rt2DBoundTailKernel<3>); break;
@@ -2166,7 +1739,7 @@ void Rt2DTileCall::Enqueue(hipStream_t on_stream) {
           default: launch_tail(Rt2DBoundTailKernel<8>); break;
         }
       }
-    } else if (I.d_timeline) {               // the instrumented instantiations (runtime row stride)
+    } else if (d_timeline) {               // the instrumented instantiations (runtime row stride)
       if (rpl == 1) launch(Rt2DTileKernel<1, 0, true>);
       else if (rpl == 2) launch(Rt2DTileKernel<2, 0, true>);
       else if (rpl == 3) launch(Rt2DTileKernel<3, 0, true>);
@@ -2183,23 +1756,48 @@ void Rt2DTileCall::Enqueue(hipStream_t on_stream) {
     else if (rpl <= 6) launch(Rt2DTileKernel<6, 0, false>);
     else launch(Rt2DTileKernel<8, 0, false>);
   }
-  if (!I.level4) RecordEvent(ws->ev_k1, ws->stream);
+  if (!L.level4) RecordEvent(ws->ev_k1, ws->stream);
   // (the bound kernel has finished its matches itself; in its verify mode it leaves every sum)
-  if (!I.bounds || dbg.rt2d_bounds_verify) {
-    if (I.level4) {     // (verify mode of the 4 x 4 level: byte sums)
+  if (!L.bounds || dbg.rt2d_bounds_verify) {
+    if (L.level4) {     // (verify mode of the 4 x 4 level: byte sums)
       OptInLds(reinterpret_cast<const void*>(Rt2DFinishKernel<kQ8Shift>), device, 128 * 1024);
-      Rt2DFinishKernel<kQ8Shift><<<num, kFinishThreads, I.finish_lds, ws->stream>>>(d_params, I.group, I.h_misc);
+      Rt2DFinishKernel<kQ8Shift><<<num, kFinishThreads, L.finish_lds, ws->stream>>>(d_params, L.group, h_misc);
     } else {
       OptInLds(reinterpret_cast<const void*>(Rt2DFinishKernel<kQShift>), device, 128 * 1024);
-      Rt2DFinishKernel<kQShift><<<num, kFinishThreads, I.finish_lds, ws->stream>>>(d_params, I.group, I.h_misc);
+      Rt2DFinishKernel<kQShift><<<num, kFinishThreads, L.finish_lds, ws->stream>>>(d_params, L.group, h_misc);
     }
   }
+}
+
+void Rt2DTileCall::Enqueue(hipStream_t on_stream) {
+  Impl& I = *impl_;
+  const auto t_enter = std::chrono::steady_clock::now();
+  const auto lap_us = [&]() {
+    return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t_enter).count();
+  };
+  I.ReserveBuffers(on_stream);
+  I.AcquireImages();
+  const double t_images = lap_us();
+  I.FillParams();
+  const double t_params = lap_us();
+  WorkspaceLease& ws = *I.ws;
+  // (the matches' result words -- 512 bytes each, the last region of the buffer -- are zeroed by
+  // the copy kernel itself: 40 % of the upload did not have to cross the bus)
+  const size_t off_misc = I.staging.misc, in_bytes = I.staging.bytes;
+  SmallCopyAsync(I.d_in, I.h_in, off_misc, /*to_device=*/true, ws->stream, I.d_in + off_misc, in_bytes - off_misc);
+  const double t_upload = lap_us();
+  const Rt2DTileParams* d_params = reinterpret_cast<const Rt2DTileParams*>(I.d_in);
+
+  RecordEvent(ws->ev_begin, ws->stream);
+  I.LaunchImageKernels(d_params);
+  RecordEvent(ws->ev_k0, ws->stream);
+  I.LaunchMatchKernels(d_params);
   CMX_HIP(hipGetLastError());
   RecordEvent(ws->ev_end, ws->stream);
   I.enqueued = true;
-  if (dbg.host_trace)
+  if (Debug().host_trace)
     fprintf(stderr, "[cmx host] rt2d enqueue(%d): workspace + images %.0f, parameters %.0f, upload call %.0f, "
-                    "launches %.0f us (%zu bytes up)\n", num, t_images, t_params, t_upload, lap_us(), in_bytes);
+                    "launches %.0f us (%zu bytes up)\n", I.num, t_images, t_params, t_upload, lap_us(), in_bytes);
 }
 
 bool Rt2DTileCall::Collect(cmx_match_stats* stats, std::vector<int>* redo) {
@@ -2216,8 +1814,8 @@ bool Rt2DTileCall::Collect(cmx_match_stats* stats, std::vector<int>* redo) {
   I.synced = true;
   I.holds.built = true;
   if (I.d_timeline) {
-    ReportTimeline(I.bounds ? "Rt2DBoundKernel" : "Rt2DTileKernel", I.d_timeline, I.tile_grid * 4, ws->stream);
-    ReportTimeline("Rt2DFinishKernel", I.d_timeline + static_cast<size_t>(I.tile_grid) * 4 * kTimelineStamps,
+    ReportTimeline(I.plan.bounds ? "Rt2DBoundKernel" : "Rt2DTileKernel", I.d_timeline, I.plan.tile_grid * 4, ws->stream);
+    ReportTimeline("Rt2DFinishKernel", I.d_timeline + static_cast<size_t>(I.plan.tile_grid) * 4 * kTimelineStamps,
                    num, ws->stream);
   }
   // Matches the bulk path could not decide -- a flat score landscape (more blocks or candidates
@@ -2284,7 +1882,7 @@ bool Rt2DTileCall::Collect(cmx_match_stats* stats, std::vector<int>* redo) {
     // (what the device summed: the whole search space, or -- block bounds -- one bound per
     // 2 x 2 block of translations plus the four candidates of the blocks that reach the bound)
     // (head[124]: 2 x 2 blocks summed, four candidates each -- or, 4 x 4 level, the candidates summed)
-    total.coarse_candidates += I.bounds ? static_cast<long long>(head[125]) + (I.level4 ? 1ll : 4ll) * head[124] : cands;
+    total.coarse_candidates += I.plan.bounds ? static_cast<long long>(head[125]) + (I.plan.level4 ? 1ll : 4ll) * head[124] : cands;
     total.num_scans += search[m].num_scans;
     total.refined_candidates += head[126];        // candidates re-summed with exact integers
     total.finalists += head[127] & 0xffffu;       // candidates scored with the reference's f32 chain

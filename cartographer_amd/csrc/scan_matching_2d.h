@@ -285,7 +285,8 @@ void Rt2DComputeSearch(const cmx_rt_options* options, const Rt2DItem& item, Rt2D
 void Rt2DFinishOnHost(const cmx_rt_options* options, const Rt2DItem& item, const Rt2DSearch& search,
                       const std::pair<int, float>* finalists, size_t count);
 // rt_2d_tiles.hip: the bulk path for probability grids, in three steps so that one host thread
-// keeps the parts of a large batch in flight on streams of their own (see there).
+// keeps the parts of a large batch in flight on streams of their own (see there).  What Plan()
+// decides is rt_2d_plan.h (plain C++, checked on the host: tests/native/rt2d_plan_check.cc).
 class Rt2DTileCall {
  public:
   // `concurrent_calls`: how many calls of this kind share the device at the same time (the parts

@@ -927,3 +927,51 @@ def test_rt2d_resident_batch_and_image_cache_follow_the_grid(sm, oracle, synth):
                                 inits[k], scans[k], 0.1, math.radians(5.0), 0.1, 0.1)
         assert s2[k] == ref["score"], k
     check_all()
+
+
+def _square_room(size, res, half_side, true_pose, beams, far_point):
+    """A square room of walls `half_side` metres from the centre of a size x size grid whose centre
+    is the map's origin, and the scan of it from `true_pose` (x, y, yaw): the walls' cells
+    occupied, their neighbours half so, the inside free, everything else unknown.  The scan's last
+    point is `far_point` metres out: it fixes the longest range, hence the rotation step and the
+    box of the search."""
+    off = np.abs(np.arange(size) + 0.5 - size / 2)            # cells from the centre, per axis
+    d = np.maximum(off[:, None], off[None, :]) - half_side / res   # ... and from the walls
+    cells = np.where(np.abs(d) <= 0.5, 2000, np.where(np.abs(d) <= 1.5, 12000, np.where(d < 0, 30000, 0)))
+    cells = cells.astype(np.uint16)
+    tx, ty, yaw = true_pose
+    a = np.linspace(-math.pi, math.pi, beams, endpoint=False) + 0.001
+    c, s = np.cos(a + yaw), np.sin(a + yaw)
+    d = np.minimum(np.where(c > 0, (half_side - tx) / c, (-half_side - tx) / c),
+                   np.where(s > 0, (half_side - ty) / s, (-half_side - ty) / s))
+    scan = np.zeros((beams, 3), np.float32)
+    scan[:, 0], scan[:, 1] = d * np.cos(a), d * np.sin(a)
+    scan[-1] = (far_point, 0.0, 0.0)
+    return cells, scan
+
+
+def test_rt2d_replanned_window_class_next_to_a_several_tile_class(sm, debug):
+    """Two matches, two window classes (the case `replan` of tests/native/rt2d_plan_check.cc, at its
+    recorded shapes): a 200 x 200 grid at 6 cm whose 4.9 m scan fits ONE tile of more LDS than two
+    workgroups per CU leave each other, next to a 600 x 600 grid at 5 cm whose 12 m scan needs 4 x 4
+    tiles -- a launch has one shape, so the planner lays the first class out again within the
+    two-per-CU budget.  Scores and poses equal the per-candidate kernels', bit for bit."""
+    from cartographer_amd import _lib, grid_2d
+    m = sm.RealTimeCorrelativeScanMatcher2D(0.29, math.radians(2.0), 0.1, 0.1)
+    grids, scans = [], []
+    for size, res, half_side, far in ((200, 0.06, 3.4, 4.9), (600, 0.05, 8.4, 12.0)):
+        cells, scan = _square_room(size, res, half_side, (0.07, -0.05, 0.01), 1000, far)
+        grids.append(grid_2d.ProbabilityGridOnDevice(res, (0.5 * size * res, 0.5 * size * res), size, size,
+                                                     cells=cells))
+        scans.append(scan)
+    inits = [sm.Rigid2d(0.0, 0.0, 0.0), sm.Rigid2d(0.0, 0.0, 0.0)]
+    debug(rt2d_legacy=1)
+    ref_scores, ref_poses, _ = sm.rt2d_match_batch(m, grids, inits, scans)
+    _lib.debug_reset()
+    scores, poses, stats = sm.rt2d_match_batch(m, grids, inits, scans)
+    for k in range(2):
+        assert scores[k] == ref_scores[k], k
+        assert (poses[k].x, poses[k].y, poses[k].theta) == (ref_poses[k].x, ref_poses[k].y, ref_poses[k].theta), k
+        assert scores[k] > 0.3, (k, scores[k])                          # (a peaked landscape, not a flat one)
+    assert stats["candidates_scored"] == 7 * 11 * 11 + 19 * 13 * 13, stats   # the recorded rotations and windows
+    assert 0 < stats["refined_candidates"] < stats["candidates_scored"], stats   # the tile path ran
