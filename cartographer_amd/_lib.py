@@ -118,6 +118,29 @@ class DebugFilterCallPlan(C.Structure):
                 ("num_sets", C.c_int32)]
 
 
+HISTOGRAM_NONE, HISTOGRAM_BATCHED, HISTOGRAM_SINGLE = 0, 1, 2
+
+
+class HistogramJob(C.Structure):
+    """cmx_histogram_job: one cloud and histogram size of cmx_compute_histogram_batch."""
+    _fields_ = [("point_cloud_xyz", C.c_void_p), ("num_points", C.c_int32),
+                ("histogram_size", C.c_int32), ("histogram", C.c_void_p)]
+
+
+class DebugHistogramJobPlan(C.Structure):
+    """cmx_debug_histogram_job_plan: where a job of cmx_compute_histogram_batch runs."""
+    _fields_ = [("route", C.c_int32), ("set", C.c_int32), ("launch", C.c_int32),
+                ("slot", C.c_int32), ("N", C.c_int32), ("cloud_slot", C.c_int32),
+                ("lds_bytes", C.c_int64)]
+
+
+class DebugHistogramCallPlan(C.Structure):
+    """cmx_debug_histogram_call_plan: the launches and the staging of a
+    cmx_compute_histogram_batch call."""
+    _fields_ = [("staged_bytes", C.c_int64), ("num_launches", C.c_int32),
+                ("num_sets", C.c_int32)]
+
+
 class DebugRt3DMatchPlan(C.Structure):
     """cmx_debug_rt3d_match_plan: window, route and blocks of a match of cmx_rt3d_match_grid_batch."""
     _fields_ = [("L", C.c_int32), ("A", C.c_int32), ("T", C.c_int64), ("R", C.c_int64),
@@ -291,7 +314,7 @@ EXPORTED_SYMBOLS = [
     "cmx_pack_best_key", "cmx_unpack_best_key",
     "cmx_voxel_filter", "cmx_voxel_filter_indices", "cmx_adaptive_voxel_filter",
     "cmx_adaptive_voxel_filter_indices", "cmx_filter_batch",
-    "cmx_compute_histogram",
+    "cmx_compute_histogram", "cmx_compute_histogram_batch",
     "cmx_intensity_grid3d_create", "cmx_intensity_grid3d_destroy",
     "cmx_grid3d_insert_with_intensities", "cmx_intensity_grid3d_download",
     "cmx_ceres3d_match_grids_intensity",
@@ -302,6 +325,7 @@ EXPORTED_SYMBOLS = [
 DEBUG_SYMBOLS = ["cmx_debug_set", "cmx_debug_reset", "cmx_debug_fast2d_plan",
                  "cmx_debug_grid2d_insert_plan", "cmx_debug_grid3d_insert_plan",
                  "cmx_debug_tsdf2d_insert_plan", "cmx_debug_filter_batch_plan",
+                 "cmx_debug_histogram_batch_plan",
                  "cmx_debug_rt3d_batch_plan"]
 
 _lib = None
@@ -499,6 +523,11 @@ def lib():
         L.cmx_debug_filter_batch_plan.argtypes = [P(FilterJob), C.c_int32, P(DebugFilterJobPlan),
                                                   P(DebugFilterCallPlan)]
     L.cmx_compute_histogram.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]
+    if hasattr(L, "cmx_compute_histogram_batch"):   # (absent from an older library an A/B tool loads)
+        L.cmx_compute_histogram_batch.argtypes = [P(HistogramJob), C.c_int32, C.c_int32]
+        L.cmx_debug_histogram_batch_plan.argtypes = [P(HistogramJob), C.c_int32,
+                                                     P(DebugHistogramJobPlan),
+                                                     P(DebugHistogramCallPlan)]
     L.cmx_comm_init.argtypes = [C.c_void_p, C.c_int32, P(C.c_void_p)]
     L.cmx_comm_destroy.argtypes = [C.c_void_p]
     L.cmx_comm_destroy.restype = None

@@ -123,6 +123,7 @@ cmx_status Guard(F&& body) {
   X(tsdf2d_insert_chain)  /* most insertions per set of launches of a round of cmx_tsdf2d_insert_batch (0: default; tests: splits a round) */ \
   X(filters_generic)     /* 1: voxel filters of small clouds through the multi-launch path too */ \
   X(filter_batch_set_kb) /* most KB of staged clouds, and of result slots, per set of launches of cmx_filter_batch (0: default; tests: splits a call) */ \
+  X(histogram_batch_set_kb) /* most KB of staged clouds, and of result slots, per set of launches of cmx_compute_histogram_batch (0: default; tests: splits a call) */ \
   X(fast3d_byte_loads)    /* 1: every child cell with its own byte load */                         \
   X(fast3d_affinity)      /* 1: nodes of a problem on any XCD, 2: on one */                        \
   X(fast3d_no_families)   /* 1: one node per block in the 3D expansion */                          \

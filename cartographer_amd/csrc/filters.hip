@@ -31,6 +31,7 @@
 #include "cmx_common.h"
 #include "cmx_device.h"
 #include "filters_small_device.h"
+#include "histogram_common.h"
 
 namespace cmx {
 namespace {
@@ -291,8 +292,6 @@ bool UseSmallFilter(int n) { return n >= 1 && n <= kSmallCloud && Debug().filter
 // ---------------------------------------------------------------------------
 // RotationalScanMatcher::ComputeHistogram
 // ---------------------------------------------------------------------------
-constexpr float kMinDistance = 0.2f, kMaxDistance = 0.9f, kSliceHeight = 0.2f;
-
 __global__ void SliceKeyKernel(const float* __restrict__ xyz, int n, unsigned* __restrict__ keys,
                                unsigned* __restrict__ index) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -364,8 +363,6 @@ SliceAngleKernel(const float* __restrict__ xyz, const unsigned* __restrict__ sor
 //     reference's expressions and libm's atan2f arithmetic, written at the point's position in
 //     the global (slice, angle) order -- the order in which the reference adds them.
 // The additions themselves are HistogramChainKernel's.
-constexpr unsigned kNoVote = 0xffffu;      // bucket key of a point without a vote (> any bucket)
-
 __global__ void __launch_bounds__(256)
 SliceWalkKernel(const float* __restrict__ xyz, const unsigned long long* __restrict__ sorted_keys2,
                 const unsigned* __restrict__ sorted_index2, const int* __restrict__ slice_begin,
@@ -796,21 +793,8 @@ cmx_status cmx_compute_histogram(const float* point_cloud_xyz, int32_t num_point
     unsigned* vote_value = index;
     unsigned* vote_bucket_sorted = keys_sorted;
     unsigned* vote_value_sorted = index_sorted;
-    // distance < kMin <=> d2 < min_sq, distance > kMax <=> d2 > max_sq for the correctly rounded
-    // f32 square root of the reference (monotone): the smallest d2 whose root reaches kMin, the
-    // largest whose root does not exceed kMax.
-    static const float min_sq = [] {
-      float x = cmx::kMinDistance * cmx::kMinDistance;
-      while (std::sqrt(x) >= cmx::kMinDistance) x = std::nextafter(x, 0.f);
-      while (std::sqrt(x) < cmx::kMinDistance) x = std::nextafter(x, 1.f);
-      return x;
-    }();
-    static const float max_sq = [] {
-      float x = cmx::kMaxDistance * cmx::kMaxDistance;
-      while (std::sqrt(x) <= cmx::kMaxDistance) x = std::nextafter(x, 2.f);
-      while (std::sqrt(x) > cmx::kMaxDistance) x = std::nextafter(x, 0.f);
-      return x;
-    }();
+    // (the thresholds of the walk: histogram_common.h)
+    const float min_sq = cmx::HistogramMinDistanceSq(), max_sq = cmx::HistogramMaxDistanceSq();
     cmx::SliceWalkKernel<<<num_slices, 256, 0, st>>>(d_xyz, keys2_sorted, index2_sorted,
                                                      slice_begin, num_slices, n, histogram_size,
                                                      min_sq, max_sq, vote_bucket, vote_value);

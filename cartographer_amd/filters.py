@@ -131,3 +131,50 @@ def compute_histogram(point_cloud, histogram_size, device=0):
     _lib.check(_lib.lib().cmx_compute_histogram(xyz.ctypes.data, n, histogram_size, device,
                                                 out.ctypes.data))
     return out
+
+
+def _histogram_jobs(clouds, histogram_size):
+    """The cmx_histogram_job array of `clouds`, the converted clouds it borrows and the sizes."""
+    sizes = [histogram_size] * len(clouds) if np.isscalar(histogram_size) else list(histogram_size)
+    if len(sizes) != len(clouds):
+        raise ValueError("histogram_size: an int, or one per cloud")
+    items = (_lib.HistogramJob * max(len(clouds), 1))()
+    borrowed = {}
+    for k, cloud in enumerate(clouds):
+        # the same array object is the same cloud of the call: converted and staged once
+        if id(cloud) not in borrowed:
+            borrowed[id(cloud)] = (cloud, _cloud(cloud)[0])
+        xyz = borrowed[id(cloud)][1]
+        items[k].point_cloud_xyz, items[k].num_points = xyz.ctypes.data, xyz.shape[0]
+        items[k].histogram_size = int(sizes[k])
+    return items, borrowed, sizes
+
+
+def compute_histogram_batch(clouds, histogram_size, device=0):
+    """``compute_histogram`` of many clouds in one call (``cmx_compute_histogram_batch``).
+    `clouds` is a list of arrays (the same array object twice is one cloud, uploaded once),
+    `histogram_size` an int or one per cloud.  Returns a list of float32 arrays: what
+    ``compute_histogram(clouds[k], histogram_size[k])`` returns."""
+    items, borrowed, sizes = _histogram_jobs(clouds, histogram_size)
+    out = [np.zeros(max(int(size), 0), np.float32) for size in sizes]
+    for k, histogram in enumerate(out):
+        items[k].histogram = histogram.ctypes.data
+    _lib.check(_lib.lib().cmx_compute_histogram_batch(items, len(clouds), device))
+    return out
+
+
+def histogram_batch_plan(clouds, histogram_size):
+    """Where the jobs of ``compute_histogram_batch(clouds, histogram_size)`` would run
+    (``cmx_debug_histogram_batch_plan``; no device needed): per job a dict of route, set, launch,
+    slot, N, cloud_slot and lds_bytes, and for the call a dict of staged_bytes, num_launches and
+    num_sets."""
+    items, borrowed, sizes = _histogram_jobs(clouds, histogram_size)
+    wanted = np.zeros(4, np.float32)      # (the plan never looks into the histograms)
+    for k in range(len(clouds)):
+        items[k].histogram = wanted.ctypes.data
+    plans = (_lib.DebugHistogramJobPlan * max(len(clouds), 1))()
+    call = _lib.DebugHistogramCallPlan()
+    _lib.check(_lib.lib().cmx_debug_histogram_batch_plan(items, len(clouds), plans, C.byref(call)))
+    return ([{name: getattr(plans[k], name) for name, _ in _lib.DebugHistogramJobPlan._fields_}
+             for k in range(len(clouds))],
+            {name: getattr(call, name) for name, _ in _lib.DebugHistogramCallPlan._fields_})

@@ -53,6 +53,10 @@
  *                                  call, a filter's output handed to the next on the device: the
  *                                  filter chains of LocalTrajectoryBuilder2D / 3D::AddRangeData
  *                                  (sensor/internal/voxel_filter.cc), or those of many trajectories
+ *   cmx_compute_histogram_batch    RotationalScanMatcher::ComputeHistogram for many clouds in one
+ *                                  call: the histograms of the nodes that
+ *                                  LocalTrajectoryBuilder3D::InsertIntoSubmap inserts
+ *                                  (3d/local_trajectory_builder_3d.cc:399-404), for many trajectories
  *
  * Conventions
  *   - Plain C, POD only.  Host pointers are borrowed for the duration of the
@@ -1140,6 +1144,30 @@ cmx_status cmx_filter_batch(const cmx_filter_job* jobs, int32_t num_jobs, int32_
  * Same accumulation order as the reference; atan2f is the device's (<= 1 ulp from libm's). */
 cmx_status cmx_compute_histogram(const float* point_cloud_xyz, int32_t num_points,
                                  int32_t histogram_size, int32_t device, float* histogram);
+/* ComputeHistogram for many clouds in one call: the histogram of every node that
+ * LocalTrajectoryBuilder3D::InsertIntoSubmap inserts (3d/local_trajectory_builder_3d.cc:399-404),
+ * for a fleet.  Job i returns, bit for bit, what cmx_compute_histogram(point_cloud_xyz,
+ * num_points, histogram_size, device, histogram) returns for it -- including the single call's
+ * order for points of equal angle inside a slice: ascending input index (both of its radix sorts
+ * are stable).  The cloud is what the caller would hand to ComputeHistogram: the rotation into
+ * the gravity-aligned frame stays with the caller.  Equal point_cloud_xyz pointers are one
+ * cloud, with equal num_points, and are uploaded once; two jobs may ask different histogram_size
+ * of one cloud.  A job without points yields zeros.
+ * Clouds of 1 .. 4096 finite points run one workgroup per job out of LDS: one upload, one launch
+ * and one synchronisation for all of them (calls that stage more than 32 MB go out in
+ * consecutive parts).  A cloud above 4096 points, or with a non-finite coordinate, runs inside
+ * the call as the single call does: same result, nothing gained.
+ * Every argument check is made for every job before the device is touched;
+ * CMX_INVALID_ARGUMENT names the job ("job <index>") in cmx_last_error and no histogram has
+ * been written.  num_jobs >= 1. */
+typedef struct cmx_histogram_job {
+  const float* point_cloud_xyz;  /* host cloud, xyz triples; may be NULL iff num_points == 0 */
+  int32_t num_points;            /* 0 .. 2^24 */
+  int32_t histogram_size;        /* 1 .. 8192 */
+  float* histogram;              /* histogram_size floats, written by the call */
+} cmx_histogram_job;
+cmx_status cmx_compute_histogram_batch(const cmx_histogram_job* jobs, int32_t num_jobs,
+                                       int32_t device);
 
 /* ---- multi-GPU: one scan against submaps spread over the GPUs of a node ---------------- */
 /* The (node, submap) searches of a ConstraintBuilder fan-out are independent

@@ -161,6 +161,39 @@ cmx_status cmx_debug_filter_batch_plan(const cmx_filter_job* jobs, int32_t num_j
                                        cmx_debug_filter_job_plan* job_plans,
                                        cmx_debug_filter_call_plan* call_plan);
 
+/* The plan of one cmx_compute_histogram_batch call: the route of every job -- CMX_HISTOGRAM_NONE
+ * (no points: zeros), CMX_HISTOGRAM_BATCHED (1 .. 4096 finite points: one workgroup of the batch
+ * kernel) or CMX_HISTOGRAM_SINGLE (more points, or a non-finite coordinate: the single path
+ * inside the call; the clouds of up to 4096 points are read for it) -- and for a batched job its
+ * set (the consecutive parts a call goes out in; switch histogram_batch_set_kb: the bound on a
+ * part's staged clouds and on its result block, default 32 MB), its launch within the set, its
+ * descriptor slot, N (the LDS carve: the points rounded up to a power of two, at least 64) and the
+ * dynamic LDS its N asks for; else set, launch and slot -1, N and lds_bytes 0.  A set has one
+ * launch per class of N that changes how many workgroups a compute unit holds, each with the
+ * LDS of its largest N.  The launch path asks the same function; this entry launches nothing and
+ * needs no device.  The errors are those of the call itself, naming the job. */
+enum { CMX_HISTOGRAM_NONE = 0, CMX_HISTOGRAM_BATCHED = 1, CMX_HISTOGRAM_SINGLE = 2 };
+typedef struct cmx_debug_histogram_job_plan {
+  int32_t route;
+  int32_t set;
+  int32_t launch;              /* within its set */
+  int32_t slot;                /* its descriptor in the table of its set */
+  int32_t N;
+  int32_t cloud_slot;          /* a job with points: which of the call's distinct clouds (equal
+                                  pointers, equal slot); else -1 */
+  int64_t lds_bytes;
+} cmx_debug_histogram_job_plan;
+
+typedef struct cmx_debug_histogram_call_plan {
+  int64_t staged_bytes;        /* the clouds uploaded for the workgroups of all sets */
+  int32_t num_launches;
+  int32_t num_sets;
+} cmx_debug_histogram_call_plan;
+
+cmx_status cmx_debug_histogram_batch_plan(const cmx_histogram_job* jobs, int32_t num_jobs,
+                                          cmx_debug_histogram_job_plan* job_plans,
+                                          cmx_debug_histogram_call_plan* call_plan);
+
 /* The plan of one cmx_rt3d_match_grid_batch call from the options and, per match, the resolution
  * of its grid, its number of points and the largest norm of a point (a NaN or infinity stands for
  * a cloud with a non-finite coordinate, planned with the window of the smallest range, three
