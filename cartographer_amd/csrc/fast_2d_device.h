@@ -1,7 +1,8 @@
 // Device helpers of the fast 2D matcher that kernels of more than one translation unit use: the
-// score conversions (the front end, fast_2d_coarse.hip, writes scores the tree search,
-// fast_2d.hip, prunes with) and the re-derivation of a scan's cells from the point cloud
-// (bit-identical to what the front end scored).
+// score conversions (the front end, fast_2d_coarse.hip, writes scores the tree search --
+// fast_2d_seed.hip, fast_2d_levels.hip, fast_2d_queue.hip, fast_2d.hip -- prunes with) and the
+// re-derivation of a scan's cells from the point cloud (bit-identical to what the front end
+// scored).  What only the tree search's kernels share: fast_2d_search_device.h.
 #ifndef CMX_FAST_2D_DEVICE_H_
 #define CMX_FAST_2D_DEVICE_H_
 

@@ -1,7 +1,11 @@
 // What the translation units of the fast 2D matcher share on the host:
 //   fast_2d_stack.hip    precomputation stack (Fast2DMatcher)
 //   fast_2d_coarse.hip   scan preparation + lowest-resolution scoring (the front end)
-//   fast_2d.hip          branch and bound
+//   fast_2d.hip          branch and bound: scratch layout, depth 1, the fall-back ladder
+//   fast_2d_seed.hip       ... what runs before either strategy: seeds + dive, filter
+//   fast_2d_queue.hip      ... the work-queue strategy
+//   fast_2d_levels.hip     ... the level-synchronous strategy (its SubtreeKernel: fast_2d_seed.hip)
+//                        (what these four hand each other: fast_2d_search.h)
 //   fast_2d_match.hip    MatchBatch, tie resolution, C ABI
 //   fast_2d_pairs.hip    lists of (node, submap) pairs: grouping into MatchBatch calls, C ABI
 // Every unit owns its kernels and exposes the host functions declared here; no kernel is launched
@@ -45,7 +49,7 @@ struct PreparedBatch {
   ProblemState* d_states = nullptr;
   std::vector<Fast2DProblem> h_problems;
   // Search scratch carved before the first kernel so that it can clear the counters.
-  char* d_misc = nullptr;          // (ReserveSearchScratch; laid out by fast_2d.hip)
+  char* d_misc = nullptr;          // (ReserveSearchScratch; layout: fast_2d_search.h)
   int num_counter_words = 0;       // ints at the start of d_misc that the first kernel of a call clears
   bool write_all_discrete = false; // debug entry point: keep every discretised scan
   unsigned long long* d_timeline = nullptr;   // CMX_TIMELINE=1
@@ -120,7 +124,7 @@ void PrepareAndScoreCoarse(Workspace& ws, const Fast2DMatcher* const* matchers, 
 // otherwise), in place.
 void RescoreExact(Workspace& ws, const PreparedBatch& batch, int p);
 
-// ---- fast_2d.hip
+// ---- fast_2d.hip (QueueSearchWanted: fast_2d_queue.hip)
 // Whether a batch of `num` problems over n points goes to the work-queue search (it keeps the
 // cells of surviving scans, which the front end has to know).
 bool QueueSearchWanted(int n, int num);

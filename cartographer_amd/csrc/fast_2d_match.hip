@@ -1,8 +1,9 @@
 // FastCorrelativeScanMatcher2D on gfx950: a match from end to end (MatchBatch), the exact
-// resolution of ties and the C ABI.  The work itself lives in three units of its own:
+// resolution of ties and the C ABI.  The work itself lives in units of its own:
 //   fast_2d_stack.hip    precomputation-grid stack construction
 //   fast_2d_coarse.hip   scan preparation, lowest-resolution scoring
-//   fast_2d.hip          the batched branch and bound
+//   fast_2d.hip          the batched branch and bound: its driver, over fast_2d_seed.hip (dive,
+//                        filter), fast_2d_queue.hip and fast_2d_levels.hip (the two strategies)
 // Lists of (node, submap) pairs, each with its own cloud, are split into MatchBatch calls by
 // fast_2d_pairs.hip.
 // (shared declarations: fast_2d_internal.h, shared device helpers: fast_2d_device.h).

@@ -721,7 +721,7 @@ Dive3DKernel(const Fast3DProblem* __restrict__ problems, List3 leaves,
 }
 
 // Among the recorded leaves with the best score, the one the reference's
-// depth-first search meets first (see fast_2d.hip SelectBestKernel).
+// depth-first search meets first (see fast_2d_search_device.h SelectBestBody).
 // grid (problems): block p looks at the leaves of problem p only.
 // Block p also PUBLISHES problem p's record -- and block 0 the counters and the problems' states,
 // complete since the kernels before this one -- into the caller's pinned mirror of `misc` (mapped

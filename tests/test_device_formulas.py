@@ -149,10 +149,11 @@ def test_rotate_z_equals_the_full_quaternion_rotation():
 
 
 def test_parent_cell_is_max_of_child_cells(oracle, synth):
-    """The identity behind the early exit of node expansions (fast_2d.hip): a width-2h
-    precomputation cell equals the maximum of the four width-h cells its children read
-    (cells outside a level read 0), on the oracle's own PrecomputationGrid2D levels -- which
-    the device stack equals bit for bit (tests/test_gpu_2d.py)."""
+    """The identity behind the early exit of node expansions (ExpandWaveKernel in
+    fast_2d_levels.hip, TreeQueueKernel in fast_2d_queue.hip): a width-2h precomputation
+    cell equals the maximum of the four width-h cells its children read (cells outside
+    a level read 0), on the oracle's own PrecomputationGrid2D levels -- which the device
+    stack equals bit for bit (tests/test_gpu_2d.py)."""
     cells, _, _ = synth.make_submap(5, 70, 53, 0.05, 6, 200, 30.0, 0.01)
     ny, nx = cells.shape
     for h in (1, 2, 4, 8, 16):

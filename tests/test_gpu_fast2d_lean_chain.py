@@ -1,4 +1,4 @@
-"""The lean chain step of the work-queue tree search (fast_2d.hip, TreeQueueKernel<0>; debug switch
+"""The lean chain step of the work-queue tree search (fast_2d_queue.hip, TreeQueueKernel<0>; debug switch
 fast2d_chain = 0, the default) against the step that waits for the bound wherever it uses it
 (TreeQueueKernel<1>, fast2d_chain = 1: the kernel as it was) and against the oracle.  The lean step
 picks the best node of a list round before it looks at the bound, decides about the round and the

@@ -1,4 +1,4 @@
-"""The dive of the fast 2D matcher by one wavefront per seed (fast_2d.hip, DiveWaveKernel; debug
+"""The dive of the fast 2D matcher by one wavefront per seed (fast_2d_seed.hip, DiveWaveKernel; debug
 switch fast2d_dive = 2) against the dive by one workgroup per seed (DiveKernel, fast2d_dive = 1) and
 against the oracle, and the fused front end (fast_2d_coarse.hip, PrepScoreFusedKernel) against the
 oracle's cells, bounds and sums.  Bars as in test_gpu_queue.py: found flag and f32 score bit-equal,

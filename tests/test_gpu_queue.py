@@ -1,5 +1,5 @@
-"""The work-queue branch and bound of round 6 (fast_2d.hip, TreeQueueKernel) against the oracle and
-against the level-synchronous launches it replaces (debug switch fast2d_queue = 2), on searches
+"""The work-queue branch and bound (fast_2d_queue.hip, TreeQueueKernel) against the oracle and
+against the level-synchronous launches (fast_2d_levels.hip; debug switch fast2d_queue = 2), on searches
 that expand from 1 600 to 60 000 nodes, in every shape the queue can take: one workgroup, a grid
 that does not divide the list, sub-queues so small that they overflow (the fall-back paths), the
 queue for a batch, eight host threads at once.  Bars as in test_gpu_2d.py: found flag and f32 score
