@@ -271,6 +271,11 @@ class DebugFast2DProblemPlan(C.Structure):
                 ("acc", C.c_int64)]
 
 
+class DebugFast3DNode(C.Structure):
+    """cmx_debug_fast3d_node: a node of cmx_debug_fast3d_child_sums (a candidate offset at a level)."""
+    _fields_ = [("level", C.c_int32), ("ox", C.c_int32), ("oy", C.c_int32), ("oz", C.c_int32)]
+
+
 class DebugFast2DLaunchPlan(C.Structure):
     _fields_ = [("fused_lds", C.c_int64), ("fused_acc", C.c_int64),
                 ("plane_acc_cells", C.c_int64), ("any_group", C.c_int32),
@@ -326,7 +331,7 @@ DEBUG_SYMBOLS = ["cmx_debug_set", "cmx_debug_reset", "cmx_debug_fast2d_plan",
                  "cmx_debug_grid2d_insert_plan", "cmx_debug_grid3d_insert_plan",
                  "cmx_debug_tsdf2d_insert_plan", "cmx_debug_filter_batch_plan",
                  "cmx_debug_histogram_batch_plan",
-                 "cmx_debug_rt3d_batch_plan"]
+                 "cmx_debug_rt3d_batch_plan", "cmx_debug_fast3d_child_sums"]
 
 _lib = None
 
@@ -593,6 +598,10 @@ def lib():
                                               C.c_void_p, C.c_void_p]
     L.cmx_fast3d_level_info.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
     L.cmx_fast3d_level_cells.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
+    if hasattr(L, "cmx_debug_fast3d_child_sums"):   # (absent from an older library an A/B tool loads)
+        L.cmx_debug_fast3d_child_sums.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
+                                                  C.c_int32, P(DebugFast3DNode), C.c_int32,
+                                                  C.c_int32, C.c_uint32, C.c_void_p, C.c_void_p]
     if hasattr(L, "cmx_debug_set"):        # (absent from the round-3 library the A/B tools load)
         L.cmx_debug_set.argtypes = [C.c_char_p, C.c_int32]
         L.cmx_debug_reset.restype = None

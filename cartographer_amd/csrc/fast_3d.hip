@@ -23,6 +23,7 @@
 #include <algorithm>
 #include <cstring>
 
+#include "../../include/cartographer_mi355x_debug.h"
 #include "fast_3d_internal.h"
 
 namespace cmx {
@@ -184,11 +185,33 @@ __device__ __forceinline__ float LowResolutionScore(const Fast3DProblem& P, cons
 // Debug switch fast3d_byte_loads (tools / tests): every child cell with its own byte load.
 __device__ int g_fast3d_byte_loads = 0;
 
+// Which loads sum the children of a node whose two x positions lie `dx` cells apart at the child
+// level (oct words O): ChildSums3D and FamilySums3D ask here, nowhere else.  `family`: the node
+// leads a family of 2 .. 8; the family loop takes it only with at most 256 points per lane
+// (`stride` lanes share `n` points), else its members go one by one.
+enum SumsPath3D {
+  kSumsOctBuffer = CMX_FAST3D_SUMS_OCT_BUFFER,  // oct words through a buffer resource, packed 16-bit accumulators
+  kSumsOctPlain = CMX_FAST3D_SUMS_OCT_PLAIN,  // oct words through plain loads (an oct array of 2 GB or more)
+  kSumsWindows = CMX_FAST3D_SUMS_WINDOWS,  // no oct words, dx <= 4: four 8-byte windows per point
+  kSumsBytes = CMX_FAST3D_SUMS_BYTES,  // one byte load per child cell
+  kSumsFamily = CMX_FAST3D_SUMS_FAMILY,  // FamilyLoop3D
+};
+__device__ __forceinline__ int SumsPath3DOf(const OctDesc& O, int dx, bool family, int n,
+                                            int stride) {
+  if (O.cells != nullptr && O.s == dx && !g_fast3d_byte_loads) {
+    const bool buffer = OctBytes(O) != 0;
+    if (family && buffer && n <= 256 * stride) return kSumsFamily;   // (packed sums: FamilyLoop3D)
+    return buffer ? kSumsOctBuffer : kSumsOctPlain;
+  }
+  return dx <= 4 && !g_fast3d_byte_loads ? kSumsWindows : kSumsBytes;
+}
+
 // Integer sums of the <= 8 children of `nd` over the points first, first + stride, ...
 // (ScoreCandidates at the child level, :332-355): the eight child cells of a point are addressed
 // from per-axis clamped offsets (two positions per axis), loads of several points in flight.
-__device__ __forceinline__ void ChildSums3D(const Fast3DProblem& P, const Node3D& nd, int first,
-                                            int stride, int sum[8]) {
+// Returns the path that summed them.
+__device__ __forceinline__ int ChildSums3D(const Fast3DProblem& P, const Node3D& nd, int first,
+                                           int stride, int sum[8]) {
   {
     const int child_depth = nd.level - 1;
     const int half = 1 << child_depth;
@@ -206,7 +229,8 @@ __device__ __forceinline__ void ChildSums3D(const Fast3DProblem& P, const Node3D
     // both: half the gather instructions of the search, which are what bounds it.
     const int dx = fx[1] - fx[0];
     const OctDesc O = P.oct[child_depth];
-    if (O.cells != nullptr && O.s == dx && !g_fast3d_byte_loads) {
+    const int path = SumsPath3DOf(O, dx, false, P.n, stride);
+    if (path == kSumsOctBuffer || path == kSumsOctPlain) {
       // One 8-byte gather per point: the eight child cells (see OctDesc).  Bytes are summed
       // as packed 16-bit pairs, widened every 256 points.
       const int ox = fx[0] + O.s, oy = fy[0] + O.s, oz = fz[0] + O.s;
@@ -221,7 +245,7 @@ __device__ __forceinline__ void ChildSums3D(const Fast3DProblem& P, const Node3D
       for (int q0 = first; q0 < n; q0 += 256 * stride) {
         unsigned e0 = 0, o0 = 0, e1 = 0, o1 = 0;
         const int stop = min(n, q0 + 256 * stride);
-        if (oct_bytes != 0) {
+        if (path == kSumsOctBuffer) {
           constexpr int kPoints = 4;             // cells first, then their four gathers
           for (int q = q0; q < stop; q += kPoints * stride) {
             I4 cv[kPoints];
@@ -266,7 +290,7 @@ __device__ __forceinline__ void ChildSums3D(const Fast3DProblem& P, const Node3D
         sum[4] += e1 & 0xffffu; sum[6] += e1 >> 16;
         sum[5] += o1 & 0xffffu; sum[7] += o1 >> 16;
       }
-    } else if (dx <= 4 && !g_fast3d_byte_loads) {
+    } else if (path == kSumsWindows) {
 #pragma unroll 2
       for (int q = first; q < P.n; q += stride) {
         const int3 d = DepthIndex(cells[q], e, -P.wxy, -P.wxy, -P.wz);
@@ -329,6 +353,7 @@ __device__ __forceinline__ void ChildSums3D(const Fast3DProblem& P, const Node3D
         sum[k] += (okx[k & 1] && oky[(k >> 1) & 1] && okz[(k >> 2) & 1]) ? v[k] : 0u;
     }
     }
+    return path;
   }
 }
 
@@ -492,17 +517,14 @@ __device__ __forceinline__ void FinishExpand3D(const Fast3DProblem& P, const Nod
   }
 }
 
-// Expansion of one node by the whole block (see above).  dive = 0: children that can still
-// matter are appended to `out`; dive = 1: the best child is left in sh->next.
-__device__ __forceinline__ void ExpandNode3D(const Fast3DProblem& P, const Node3D& nd, float best,
-                                             int dive, int strict, const List3& out,
-                                             const List3& leaves,
-                                             Counters3* __restrict__ counters, int sub_id,
-                                             ExpandShared* sh) {
+// The eight child sums of `nd` by the whole block (256 threads), left in sh->fam_total[0] by
+// threads 0 .. 7 (a barrier makes them everybody's).  Returns the path that summed them.
+__device__ __forceinline__ int NodeSums3D(const Fast3DProblem& P, const Node3D& nd,
+                                          ExpandShared* sh) {
   const int lane = threadIdx.x & 63;
   const int wave = threadIdx.x >> 6;
   int sum[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  ChildSums3D(P, nd, threadIdx.x, 256, sum);
+  const int path = ChildSums3D(P, nd, threadIdx.x, 256, sum);
 #pragma unroll
   for (int k = 0; k < 8; ++k) {
     const int total = WaveSum(sum[k]);
@@ -512,6 +534,17 @@ __device__ __forceinline__ void ExpandNode3D(const Fast3DProblem& P, const Node3
   if (threadIdx.x < 8)
     sh->fam_total[0][threadIdx.x] = sh->partial[0][threadIdx.x] + sh->partial[1][threadIdx.x] +
                                     sh->partial[2][threadIdx.x] + sh->partial[3][threadIdx.x];
+  return path;
+}
+
+// Expansion of one node by the whole block (see above).  dive = 0: children that can still
+// matter are appended to `out`; dive = 1: the best child is left in sh->next.
+__device__ __forceinline__ void ExpandNode3D(const Fast3DProblem& P, const Node3D& nd, float best,
+                                             int dive, int strict, const List3& out,
+                                             const List3& leaves,
+                                             Counters3* __restrict__ counters, int sub_id,
+                                             ExpandShared* sh) {
+  NodeSums3D(P, nd, sh);
   FinishExpand3D(P, nd, sh->fam_total[0], best, dive, strict, out, leaves, counters, sub_id, sh);
 }
 
@@ -599,14 +632,12 @@ __device__ __forceinline__ bool FamilySums3D(const Fast3DProblem& P, const Node3
   const int e = max(0, child_depth - P.full_resolution_depth + 1);
   const Brick L = P.level[child_depth];
   const OctDesc O = P.oct[child_depth];
-  if (O.cells == nullptr || g_fast3d_byte_loads) return false;
-  if ((((fam_nodes[0].ox + half) >> e) - (fam_nodes[0].ox >> e)) != O.s) return false;
-  const unsigned long long oct_bytes = OctBytes(O);
-  if (oct_bytes == 0) return false;                 // (the per-node path has plain loads)
-  const __amdgpu_buffer_rsrc_t oct = UniformBuffer(O.cells, oct_bytes);
+  // (no oct words, plain loads only, or more than 256 points per lane: the members one by one)
+  const int dx = ((fam_nodes[0].ox + half) >> e) - (fam_nodes[0].ox >> e);
+  if (SumsPath3DOf(O, dx, true, P.n, stride) != kSumsFamily) return false;
+  const __amdgpu_buffer_rsrc_t oct = UniformBuffer(O.cells, OctBytes(O));
   const auto* cells = AsGlobal(
       reinterpret_cast<const I4*>(P.cells + static_cast<size_t>(fam_nodes[0].scan) * P.n));
-  if (P.n > 256 * stride) return false;            // (packed sums: see FamilyLoop3D)
   int mx[8], my[8], mz[8];                          // block-uniform (the family lies in LDS)
 #pragma unroll
   for (int m = 0; m < 8; ++m) {
@@ -626,6 +657,19 @@ __device__ __forceinline__ bool FamilySums3D(const Fast3DProblem& P, const Node3
     default: FamilyLoop3D<8>(oct, O, cells, n, e, wxy, wz, mx, my, mz, live, first, stride, sh); break;
   }
   return true;
+}
+
+// After FamilySums3D returned true: the members' child sums, the four waves added, in
+// sh->fam_total[member][child] for every thread (rows of dead members hold no sums: nobody
+// reads them).
+__device__ __forceinline__ void FamilyTotals3D(ExpandShared* sh) {
+  __syncthreads();
+  if (threadIdx.x < 64) {
+    const int m = threadIdx.x >> 3, k = threadIdx.x & 7;
+    sh->fam_total[m][k] = sh->fam_partial[0][m][k] + sh->fam_partial[1][m][k] +
+                          sh->fam_partial[2][m][k] + sh->fam_partial[3][m][k];
+  }
+  __syncthreads();
 }
 
 // (One wavefront per node for the levels above the leaves -- four times as many nodes in
@@ -673,15 +717,7 @@ Expand3DKernel(const Fast3DProblem* __restrict__ problems, List3 in, int strict,
     bool summed = false;
     if (fam > 1 && use_families) {
       summed = FamilySums3D(P, sh.fam, fam, live, threadIdx.x, 256, &sh);
-      if (summed) {
-        __syncthreads();
-        if (threadIdx.x < 64) {
-          const int m = threadIdx.x >> 3, k = threadIdx.x & 7;
-          sh.fam_total[m][k] = sh.fam_partial[0][m][k] + sh.fam_partial[1][m][k] +
-                               sh.fam_partial[2][m][k] + sh.fam_partial[3][m][k];
-        }
-        __syncthreads();
-      }
+      if (summed) FamilyTotals3D(&sh);
     }
     for (int m = 0; m < fam; ++m) {
       if (!(live >> m & 1)) continue;
@@ -718,6 +754,42 @@ Dive3DKernel(const Fast3DProblem* __restrict__ problems, List3 leaves,
     __syncthreads();   // everyone has read sh.next before the next expansion resets it
   }
   FlushWork3D(&sh, counters);
+}
+
+// cmx_debug_fast3d_child_sums: the child sums of `nodes` by the device functions of the search.
+// as_family = 0: workgroup i sums node i as ExpandNode3D does (NodeSums3D).  as_family = 1: one
+// workgroup takes the nodes as a family, as Expand3DKernel does -- FamilySums3D and
+// FamilyTotals3D, or, where the family loop refuses, the live members one by one.  sums
+// [num_nodes][8] and path [num_nodes] (SumsPath3D); the rows of dead members are not written.
+__global__ void __launch_bounds__(256)
+DebugChildSums3DKernel(const Fast3DProblem* __restrict__ problem, const Node3D* __restrict__ nodes,
+                       int num_nodes, int as_family, unsigned live, int* __restrict__ sums,
+                       int* __restrict__ path) {
+  __shared__ ExpandShared sh;
+  const Fast3DProblem& P = *problem;
+  if (!as_family) {
+    const int i = blockIdx.x;
+    const Node3D nd = nodes[i];
+    const int took = NodeSums3D(P, nd, &sh);     // (threads 0 .. 7 hold the totals they wrote)
+    if (threadIdx.x < 8) sums[8 * i + threadIdx.x] = sh.fam_total[0][threadIdx.x];
+    if (threadIdx.x == 0) path[i] = took;
+    return;
+  }
+  if (threadIdx.x < num_nodes) sh.fam[threadIdx.x] = nodes[threadIdx.x];
+  __syncthreads();
+  const bool summed = FamilySums3D(P, sh.fam, num_nodes, live, threadIdx.x, 256, &sh);
+  if (summed) FamilyTotals3D(&sh);
+  for (int m = 0; m < num_nodes; ++m) {
+    if (!(live >> m & 1)) continue;                                         // block-uniform
+    int took = kSumsFamily;
+    if (!summed) {
+      const Node3D nd = sh.fam[m];
+      took = NodeSums3D(P, nd, &sh);
+    }
+    if (threadIdx.x < 8) sums[8 * m + threadIdx.x] = sh.fam_total[summed ? m : 0][threadIdx.x];
+    if (threadIdx.x == 0) path[m] = took;
+    __syncthreads();   // (the scratch of NodeSums3D is reused by the next member)
+  }
 }
 
 // Among the recorded leaves with the best score, the one the reference's
@@ -842,15 +914,20 @@ VerifyCoarseLeaves3DKernel(const Fast3DProblem* __restrict__ problems, List3 lea
 
 }  // namespace
 
-void ReserveSearchScratch3D(Workspace& ws, Chain3D* chain) {
-  {
-    const int byte_loads = Debug().fast3d_byte_loads ? 1 : 0;
-    static int uploaded = -1;              // (tools only: not meant to be toggled concurrently)
-    if (uploaded != byte_loads) {
-      CMX_HIP(hipMemcpyToSymbol(HIP_SYMBOL(g_fast3d_byte_loads), &byte_loads, sizeof(int)));
-      uploaded = byte_loads;
-    }
+namespace {
+// The debug switch fast3d_byte_loads as the kernels of this unit read it.
+void UploadByteLoadsSwitch3D() {
+  const int byte_loads = Debug().fast3d_byte_loads ? 1 : 0;
+  static int uploaded = -1;              // (tools only: not meant to be toggled concurrently)
+  if (uploaded != byte_loads) {
+    CMX_HIP(hipMemcpyToSymbol(HIP_SYMBOL(g_fast3d_byte_loads), &byte_loads, sizeof(int)));
+    uploaded = byte_loads;
   }
+}
+}  // namespace
+
+void ReserveSearchScratch3D(Workspace& ws, Chain3D* chain) {
+  UploadByteLoadsSwitch3D();
   // The debug switch frontier_capacity shrinks the frontier buffers (tests only): overflow ->
   // strict retry.
   const int cap_req = Debug().frontier_capacity;
@@ -1003,4 +1080,97 @@ void RunBranchAndBound3D(Workspace& ws, const Chain3D& c, float first_min_score,
   searched->leaf_counts = h_counters->leaves;
 }
 
+namespace {
+
+// cmx_debug_fast3d_child_sums after its argument checks: a problem of one scan whose cells are
+// given, the nodes, and the caller's `sums` and `path` go up in one block; DebugChildSums3DKernel
+// overwrites the rows it computes and the block's tail comes back (rows it left alone unchanged).
+void DebugChildSums3D(const Fast3DMatcher& m, const int32_t* cells_xyz, int n, int wxy, int wz,
+                      const cmx_debug_fast3d_node* nodes, int num_nodes, int as_family,
+                      unsigned live_mask, int32_t* sums, int32_t* path) {
+  const size_t off_nodes = sizeof(Fast3DProblem);
+  const size_t off_cells = (off_nodes + sizeof(Node3D) * num_nodes + 15) / 16 * 16;
+  const size_t off_sums = off_cells + sizeof(int4) * n;
+  const size_t off_path = off_sums + sizeof(int) * 8 * num_nodes;
+  const size_t bytes = off_path + sizeof(int) * num_nodes;
+  static_assert(sizeof(Fast3DProblem) % 16 == 0, "alignment");
+  WorkspaceLease ws(m.device);
+  UploadByteLoadsSwitch3D();
+  char* d = static_cast<char*>(ws->dev[0].Reserve(bytes));
+  char* h = static_cast<char*>(ws->pinned[0].Reserve(bytes));
+  const int depth = m.options.branch_and_bound_depth;
+  Fast3DProblem P{};
+  for (int l = 0; l < depth; ++l) P.level[l] = m.levels[l]->desc;
+  for (size_t l = 0; l < m.oct_desc.size(); ++l) P.oct[l] = m.oct_desc[l];
+  P.depth = depth;
+  P.full_resolution_depth = m.options.full_resolution_depth;
+  P.resolution = m.resolution;
+  P.wxy = wxy; P.wz = wz;
+  P.num_scans = 1; P.n = n;
+  P.cells = reinterpret_cast<const int4*>(d + off_cells);
+  std::memcpy(h, &P, sizeof(P));
+  Node3D* h_nodes = reinterpret_cast<Node3D*>(h + off_nodes);
+  for (int i = 0; i < num_nodes; ++i) {
+    Node3D nd{};
+    nd.level = nodes[i].level;
+    nd.ox = nodes[i].ox; nd.oy = nodes[i].oy; nd.oz = nodes[i].oz;
+    nd.family = as_family ? (i == 0 ? num_nodes : 0) : 1;
+    h_nodes[i] = nd;
+  }
+  int4* h_cells = reinterpret_cast<int4*>(h + off_cells);
+  for (int i = 0; i < n; ++i)
+    h_cells[i] = make_int4(cells_xyz[3 * i], cells_xyz[3 * i + 1], cells_xyz[3 * i + 2], 0);
+  std::memcpy(h + off_sums, sums, sizeof(int) * 8 * num_nodes);
+  std::memcpy(h + off_path, path, sizeof(int) * num_nodes);
+  CMX_HIP(hipMemcpyAsync(d, h, bytes, hipMemcpyHostToDevice, ws->stream));
+  DebugChildSums3DKernel<<<as_family ? 1 : num_nodes, 256, 0, ws->stream>>>(
+      reinterpret_cast<const Fast3DProblem*>(d), reinterpret_cast<const Node3D*>(d + off_nodes),
+      num_nodes, as_family, live_mask, reinterpret_cast<int*>(d + off_sums),
+      reinterpret_cast<int*>(d + off_path));
+  CMX_HIP(hipGetLastError());
+  CMX_HIP(hipMemcpyAsync(h + off_sums, d + off_sums, bytes - off_sums, hipMemcpyDeviceToHost,
+                         ws->stream));
+  CMX_HIP(hipStreamSynchronize(ws->stream));
+  std::memcpy(sums, h + off_sums, sizeof(int) * 8 * num_nodes);
+  std::memcpy(path, h + off_path, sizeof(int) * num_nodes);
+}
+
+}  // namespace
 }  // namespace cmx
+
+extern "C" {
+
+cmx_status cmx_debug_fast3d_child_sums(const cmx_fast3d* matcher, const int32_t* cells_xyz,
+                                       int32_t num_points, int32_t wxy, int32_t wz,
+                                       const cmx_debug_fast3d_node* nodes, int32_t num_nodes,
+                                       int32_t as_family, uint32_t live_mask, int32_t* sums,
+                                       int32_t* path) {
+  using namespace cmx;
+  return Guard([&] {
+    CMX_REQUIRE(matcher && cells_xyz && nodes && sums && path, "null argument");
+    CMX_REQUIRE(num_points >= 1 && num_points <= (1 << 24), "num_points %d outside [1, 2^24]",
+                num_points);
+    CMX_REQUIRE(wxy >= 0 && wz >= 0 && wxy < (1 << 20) && wz < (1 << 20), "bad search window");
+    CMX_REQUIRE(as_family == 0 || as_family == 1, "as_family must be 0 or 1");
+    if (as_family)
+      CMX_REQUIRE(num_nodes >= 2 && num_nodes <= 8, "a family has 2 .. 8 nodes, not %d", num_nodes);
+    else
+      CMX_REQUIRE(num_nodes >= 1 && num_nodes <= 65535, "num_nodes %d outside [1, 65535]",
+                  num_nodes);
+    const int depth = matcher->impl.options.branch_and_bound_depth;
+    for (int i = 0; i < num_nodes; ++i) {
+      CMX_REQUIRE(nodes[i].level >= 1 && nodes[i].level <= depth - 1,
+                  "node %d: level %d outside [1, %d]", i, nodes[i].level, depth - 1);
+      CMX_REQUIRE(!as_family || nodes[i].level == nodes[0].level,
+                  "node %d: the nodes of a family share a level", i);
+      // (candidate offsets lie within the window; anything an index of a 2^21 grid can meet)
+      CMX_REQUIRE(std::abs(nodes[i].ox) <= (1 << 22) && std::abs(nodes[i].oy) <= (1 << 22) &&
+                      std::abs(nodes[i].oz) <= (1 << 22),
+                  "node %d: offset beyond 2^22 cells", i);
+    }
+    DebugChildSums3D(matcher->impl, cells_xyz, num_points, wxy, wz, nodes, num_nodes, as_family,
+                     live_mask, sums, path);
+  });
+}
+
+}  // extern "C"

@@ -431,16 +431,46 @@ class FastCorrelativeScanMatcher3D:
                                                       C.byref(result), C.byref(stats)))
         return self._finish(found, result, stats)
 
-    def level(self, depth):
-        """Non-zero cells of one precomputation level, int32 [n,4] (x,y,z,value) sorted (z,y,x)."""
+    def level_box(self, depth):
+        """Lowest cell and extent (x, y, z) of one precomputation level's dense array."""
         lo = np.zeros(3, np.int32)
         dims = np.zeros(3, np.int32)
         check(_lib.lib().cmx_fast3d_level_info(self._h, depth, lo.ctypes.data, dims.ctypes.data))
+        return lo, dims
+
+    def level(self, depth):
+        """Non-zero cells of one precomputation level, int32 [n,4] (x,y,z,value) sorted (z,y,x)."""
+        lo, dims = self.level_box(depth)
         cells = np.empty((dims[2], dims[1], dims[0]), np.uint8)
         check(_lib.lib().cmx_fast3d_level_cells(self._h, depth, cells.ctypes.data))
         z, y, x = np.nonzero(cells)
         out = np.stack([x + lo[0], y + lo[1], z + lo[2], cells[z, y, x]], 1).astype(np.int32)
         return out
+
+    def debug_child_sums(self, cells_xyz, wxy, wz, nodes, as_family=False, live_mask=0xff,
+                         sums=None, path=None):
+        """``cmx_debug_fast3d_child_sums`` (tests): the eight integer child sums of every node of
+        ``nodes`` -- int32 [m,4] rows (level, ox, oy, oz) -- over the full-resolution cell indices
+        ``cells_xyz`` (int32 [n,3]) of one scan, by the device code of the search.  With
+        ``as_family`` the nodes are one family and bit i of ``live_mask`` says whether member i is
+        summed.  Returns (sums int32 [m,8], path int32 [m]); ``sums`` / ``path`` given: filled in
+        place, the rows of dead members untouched."""
+        cells = np.ascontiguousarray(cells_xyz, np.int32).reshape(-1, 3)
+        rows = np.ascontiguousarray(nodes, np.int32).reshape(-1, 4)
+        c_nodes = (_lib.DebugFast3DNode * max(rows.shape[0], 1))()
+        for node, (level, ox, oy, oz) in zip(c_nodes, rows.tolist()):
+            node.level, node.ox, node.oy, node.oz = level, ox, oy, oz
+        if sums is None:
+            sums = np.zeros((rows.shape[0], 8), np.int32)
+        if path is None:
+            path = np.full(rows.shape[0], -1, np.int32)
+        assert sums.dtype == np.int32 and sums.shape == (rows.shape[0], 8) and \
+            sums.flags.c_contiguous
+        assert path.dtype == np.int32 and path.shape == (rows.shape[0],) and path.flags.c_contiguous
+        check(_lib.lib().cmx_debug_fast3d_child_sums(
+            self._h, cells.ctypes.data, cells.shape[0], wxy, wz, c_nodes, rows.shape[0],
+            1 if as_family else 0, live_mask, sums.ctypes.data, path.ctypes.data))
+        return sums, path
 
 
 def fast3d_create_batch(sources, *, device=0, **options):

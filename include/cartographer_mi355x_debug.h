@@ -219,6 +219,43 @@ cmx_status cmx_debug_rt3d_batch_plan(const cmx_rt_options* options, int32_t num_
                                      const float* max_point_norms,
                                      cmx_debug_rt3d_match_plan* plans);
 
+/* The eight integer child sums the fast 3D branch and bound computes for a node (ScoreCandidates
+ * at the node's child level, before ToProbability), by the device functions the search itself
+ * calls -- a small kernel around them, nothing restated.  `cells_xyz` [num_points][3]: the
+ * full-resolution cell indices of ONE discretised scan (any int32; what lies outside a level
+ * reads 0); `wxy`, `wz`: the search window in voxels, in [0, 2^20).  A node is a candidate offset
+ * at `level` in [1, branch_and_bound_depth - 1]; child k of it has the offset + 2^(level - 1) *
+ * (k & 1, k >> 1 & 1, k >> 2 & 1).  as_family = 0: every node on its own, 1 .. 65535 of them.
+ * as_family = 1: the nodes are one family (2 .. 8 nodes of one level, the children one parent
+ * kept) and bit m of `live_mask` says whether member m is summed; a family the family loop does
+ * not take (no oct words, more than 65536 points) goes member by member, as in the search.
+ * `sums` [num_nodes][8] and `path` [num_nodes] out; the rows of dead members are left as they
+ * were.  `path`: the loads that produced the row -- CMX_FAST3D_SUMS_OCT_BUFFER (oct words through
+ * a buffer resource: the shipped default), _OCT_PLAIN (an oct array of 2 GB or more), _WINDOWS
+ * (no oct words, child cells at most 4 apart: four 8-byte windows per point), _BYTES (a byte load
+ * per child cell: switch fast3d_byte_loads, or no oct words and child cells 8 or more apart) or
+ * _FAMILY (the family loop).  The switches fast3d_byte_loads (at the call) and fast3d_no_oct (at
+ * the matcher's creation) apply as they do to a search.  CMX_INVALID_ARGUMENT: a null pointer,
+ * num_points outside [1, 2^24], a level outside its range, a family of mixed levels or of a size
+ * outside 2 .. 8, an offset beyond 2^22 cells. */
+enum {
+  CMX_FAST3D_SUMS_OCT_BUFFER = 0,
+  CMX_FAST3D_SUMS_OCT_PLAIN = 1,
+  CMX_FAST3D_SUMS_WINDOWS = 2,
+  CMX_FAST3D_SUMS_BYTES = 3,
+  CMX_FAST3D_SUMS_FAMILY = 4
+};
+typedef struct cmx_debug_fast3d_node {
+  int32_t level;
+  int32_t ox, oy, oz;
+} cmx_debug_fast3d_node;
+
+cmx_status cmx_debug_fast3d_child_sums(const cmx_fast3d* matcher, const int32_t* cells_xyz,
+                                       int32_t num_points, int32_t wxy, int32_t wz,
+                                       const cmx_debug_fast3d_node* nodes, int32_t num_nodes,
+                                       int32_t as_family, uint32_t live_mask, int32_t* sums,
+                                       int32_t* path);
+
 #ifdef __cplusplus
 }
 #endif

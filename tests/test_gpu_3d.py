@@ -669,13 +669,7 @@ def test_ceres3d_invalid_arguments(sm3, synth):
     assert e.value.status == INVALID_ARGUMENT
 
 
-@pytest.mark.parametrize("oct", ["1", "0"])
-def test_fast3d_oct_layout_equals_the_oracle(sm3, oracle, synth, debug, oct):
-    """Child cells from the 8-byte "oct" words (one gather per point and node) and from the level
-    bricks themselves (debug switch fast3d_no_oct at matcher creation): the oracle's result either way, on
-    the C5-shaped submap (full and half resolution levels, strides 1, 2, 4) and on a shallow
-    stack with a window reaching far outside the grid."""
-    debug(fast3d_no_oct=1 if oct == "0" else 0)
+def _c5_shaped_scene_equals_the_oracle(sm3, oracle, synth):
     size = (15.0, 15.0, 7.5)
     grid, world = synth.make_submap_3d(42, 0.1, size, 8, 32, 512)
     low, _ = synth.make_submap_3d(42, 0.45, size, 8, 32, 512)
@@ -697,6 +691,20 @@ def test_fast3d_oct_layout_equals_the_oracle(sm3, oracle, synth, debug, oct):
     got = gm.match(sm3.Rigid3d(tuple(node[:3]), tuple(node[3:])), sm3.Rigid3d(),
                    sm3.TrajectoryNodeData(hi, lo, scan_hist), 0.2)
     _assert_result(ref, got)
+
+
+@pytest.mark.parametrize("oct", ["1", "0", "bytes"])
+def test_fast3d_oct_layout_equals_the_oracle(sm3, oracle, synth, debug, oct):
+    """Child cells from the 8-byte "oct" words (one gather per point and node) and from the level
+    bricks themselves (debug switch fast3d_no_oct at matcher creation): the oracle's result either way, on
+    the C5-shaped submap (full and half resolution levels, strides 1, 2, 4) and on a shallow
+    stack with a window reaching far outside the grid.  "bytes": the shallow scene with every
+    child cell from a byte load of its own (debug switch fast3d_byte_loads)."""
+    if oct == "bytes":
+        debug(fast3d_byte_loads=1)
+    else:
+        debug(fast3d_no_oct=1 if oct == "0" else 0)
+        _c5_shaped_scene_equals_the_oracle(sm3, oracle, synth)
     # shallow stack, full-submap search (window beyond the grid on every side)
     g2, w2 = synth.make_submap_3d(5, 0.2, (6.0, 6.0, 3.0), 4, 8, 96)
     v2 = g2.voxels()
