@@ -207,6 +207,17 @@ extern "C" cmx_status cmx_grid2d_create(const cmx_grid2d_limits* limits, const u
     CMX_REQUIRE(limits && out, "null argument");
     CMX_REQUIRE(limits->resolution > 0. && limits->num_x_cells >= 1 && limits->num_y_cells >= 1,
                 "bad map limits");
+    // A grid between two updates carries no update marker (Grid2D::FinishUpdate has cleared them),
+    // and the finish sweep of an insertion could not tell a marker that came with the cells from
+    // its own: such cells are refused, before the device is touched.
+    if (cells) {
+      const size_t count = static_cast<size_t>(limits->num_x_cells) * limits->num_y_cells;
+      for (size_t i = 0; i != count; ++i)
+        CMX_REQUIRE(cells[i] < cmx::kUpdateMarker,
+                    "cell %zu (x %zu, y %zu) has value %u: bit 15, the update marker, is set", i,
+                    i % limits->num_x_cells, i / limits->num_x_cells,
+                    static_cast<unsigned>(cells[i]));
+    }
     cmx::UseDevice(device);
     std::unique_ptr<cmx_grid2d> g(new cmx_grid2d);
     g->device = device;

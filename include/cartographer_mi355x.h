@@ -229,7 +229,11 @@ cmx_status cmx_rt2d_score_candidates(const cmx_rt_options* options,
  * 78-80, :288-289) then moves only the scan across PCIe.
  *   cmx_grid2d_create     ProbabilityGrid(limits) (all unknown) or a copy of `cells`; the cost
  *                         bounds of `limits` are ignored, the grid always has the probability
- *                         range (so cmx_fast2d_create_from_grid never meets another one)
+ *                         range (so cmx_fast2d_create_from_grid never meets another one).
+ *                         `cells` are those of a grid between two updates, values 0 .. 32767: a
+ *                         cell with bit 15 (the update marker) set is refused with
+ *                         CMX_INVALID_ARGUMENT, cmx_last_error naming the cell, before the device
+ *                         is touched -- an insertion could not tell such a marker from its own
  *   cmx_grid2d_insert     ProbabilityGridRangeDataInserter2D::Insert + FinishUpdate
  *                         (mapping/2d/probability_grid_range_data_inserter_2d.cc:33-96,
  *                          mapping/internal/2d/ray_to_pixel_mask.cc:34-156); grows the

@@ -141,3 +141,29 @@ def test_debug_switches_the_bench_and_the_tools_rely_on_exist():
             _lib.debug_set(no_such_switch=1)
     finally:
         _lib.debug_reset()
+
+
+@pytest.mark.parametrize("where", [0, 37, 16 * 12 - 1])
+def test_grid2d_create_refuses_cells_that_carry_the_update_marker(where):
+    """A probability grid between two updates never has bit 15 set, and the finish sweep of an
+    insertion could not tell a marker that came with the cells from its own: one marked cell
+    anywhere is CMX_INVALID_ARGUMENT, named in cmx_last_error, before the device is touched (so
+    also where there is none).  The same cells with the bit cleared pass that check; that they are
+    accepted is test_gpu_grid_exact.py's, where a device exists."""
+    from cartographer_amd import _lib, grid_2d
+    L = _lib.lib()
+    cells = (np.arange(16 * 12, dtype=np.uint16) * 171 % 32768).reshape(12, 16)
+    marked = cells.copy()
+    marked.flat[where] |= 0x8000
+    with pytest.raises(_lib.CmxError) as e:
+        grid_2d.ProbabilityGridOnDevice(0.05, (1.0, 1.0), 16, 12, cells=marked)
+    assert e.value.status == _lib.INVALID_ARGUMENT
+    assert "cell %d (x %d, y %d)" % (where, where % 16, where // 16) in str(e.value), str(e.value)
+    assert "marker" in str(e.value)
+    # the unmarked cells get past the argument checks: accepted, or no device to put them on
+    limits = _lib.Grid2DLimits(0.05, 1.0, 1.0, 16, 12, 0.0, 0.0)
+    handle = C.c_void_p()
+    status = L.cmx_grid2d_create(C.byref(limits), cells.ctypes.data, 0, C.byref(handle))
+    assert status in (_lib.OK, _lib.DEVICE_ERROR), L.cmx_last_error()
+    if status == _lib.OK:
+        L.cmx_grid2d_destroy(handle)

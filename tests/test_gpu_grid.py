@@ -76,8 +76,13 @@ def test_insert_parity_with_growth(g2, synth, seed, free_space):
 
 
 def test_axis_aligned_and_corner_rays(g2, synth):
-    """Rays along the grid axes and exactly through pixel corners (the cases
-    ray_to_pixel_mask_test.cc exercises), in all eight octants."""
+    """Rays from a cell centre along the grid axes, along both diagonals and at slopes 2:1 and 3:2
+    (the directions ray_to_pixel_mask_test.cc exercises), given as float metres at resolution
+    0.05.  These are not exact rays: 0.025 lands on sub-pixel 499 or 500 by the rounding of
+    (max - p) / fine_resolution - 0.5, the main diagonal meets pixel corners only because both
+    coordinates round the same way, and the anti-diagonal and the 2:1 and 3:2 slopes meet none.
+    Rays through exact corners in every class, and of every length the lane stride cares about,
+    are in tests/test_gpu_grid_exact.py (cases: tests/ray_mask_cases.py)."""
     host = synth.ProbabilityGrid(0.05, (1.0, 1.0), 40, 40)
     dev = g2.ProbabilityGridOnDevice(0.05, (1.0, 1.0), 40, 40)
     origin = [0.025, 0.025]          # a cell centre
