@@ -203,6 +203,29 @@ class CeresSummary(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved"}
 
 
+class Ceres2DJob(C.Structure):
+    """cmx_ceres2d_job: one robot's match of cmx_ceres2d_match_grid_batch; exactly one of grid /
+    tsdf and exactly one of point_cloud_xyz / cloud is set."""
+    _fields_ = [("grid", C.c_void_p), ("tsdf", C.c_void_p), ("point_cloud_xyz", C.c_void_p),
+                ("cloud", C.c_void_p), ("num_points", C.c_int32), ("reserved", C.c_int32),
+                ("target_translation_xy", C.c_double * 2), ("initial_pose_estimate", Pose2d)]
+
+
+CERES2D_PROBABILITY_GRID, CERES2D_TSDF = 0, 1
+
+
+class DebugCeres2DJobPlan(C.Structure):
+    """cmx_debug_ceres2d_job_plan: kind and staged cloud of a job of cmx_ceres2d_match_grid_batch."""
+    _fields_ = [("kind", C.c_int32), ("cloud_slot", C.c_int32), ("cloud_offset", C.c_int64)]
+
+
+class DebugCeres2DCallPlan(C.Structure):
+    """cmx_debug_ceres2d_call_plan: the upload block and the launches of a
+    cmx_ceres2d_match_grid_batch call."""
+    _fields_ = [("total_bytes", C.c_int64), ("problem_bytes", C.c_int64),
+                ("num_clouds", C.c_int32), ("num_launches", C.c_int32)]
+
+
 class Ceres3DOptions(C.Structure):
     _fields_ = [("occupied_space_weight", C.c_double * 3), ("translation_weight", C.c_double),
                 ("rotation_weight", C.c_double), ("num_pairs", C.c_int32),
@@ -324,6 +347,7 @@ EXPORTED_SYMBOLS = [
     "cmx_grid3d_insert_with_intensities", "cmx_intensity_grid3d_download",
     "cmx_ceres3d_match_grids_intensity",
     "cmx_rt3d_match_grid_batch", "cmx_ceres3d_match_grids_batch",
+    "cmx_ceres2d_match_grid_batch",
 ]
 
 # include/cartographer_mi355x_debug.h (test and tool switches, not part of the boundary).
@@ -331,7 +355,8 @@ DEBUG_SYMBOLS = ["cmx_debug_set", "cmx_debug_reset", "cmx_debug_fast2d_plan",
                  "cmx_debug_grid2d_insert_plan", "cmx_debug_grid3d_insert_plan",
                  "cmx_debug_tsdf2d_insert_plan", "cmx_debug_filter_batch_plan",
                  "cmx_debug_histogram_batch_plan",
-                 "cmx_debug_rt3d_batch_plan", "cmx_debug_fast3d_child_sums"]
+                 "cmx_debug_rt3d_batch_plan", "cmx_debug_fast3d_child_sums",
+                 "cmx_debug_ceres2d_batch_plan"]
 
 _lib = None
 
@@ -476,6 +501,12 @@ def lib():
     L.cmx_ceres2d_refine_batch_tsdf.argtypes = [P(Ceres2DOptions), P(C.c_void_p), C.c_int32,
                                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
                                                 C.c_void_p, C.c_void_p]
+    if hasattr(L, "cmx_ceres2d_match_grid_batch"):   # (absent from an older library an A/B tool loads)
+        L.cmx_ceres2d_match_grid_batch.argtypes = [P(Ceres2DOptions), P(Ceres2DJob), C.c_int32,
+                                                   C.c_void_p, C.c_void_p]
+        L.cmx_debug_ceres2d_batch_plan.argtypes = [C.c_void_p, P(C.c_void_p), C.c_void_p,
+                                                   C.c_void_p, C.c_int32, P(DebugCeres2DJobPlan),
+                                                   P(DebugCeres2DCallPlan)]
     if hasattr(L, "cmx_fast2d_match_pairs"):   # (absent from an older library an A/B tool loads)
         L.cmx_fast2d_match_pairs.argtypes = [P(C.c_void_p), C.c_int32, C.c_void_p, C.c_void_p,
                                              C.c_void_p, P(C.c_void_p), C.c_void_p, C.c_void_p,

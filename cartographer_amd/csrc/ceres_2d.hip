@@ -34,12 +34,18 @@
 // false (.cc:61): the evaluation fails, which the trust-region loop treats as the stand-in solver
 // does (oracle/ref_shims/ceres/ceres.h: a failed initial evaluation ends the solve with FAILURE,
 // a failed candidate costs DBL_MAX and is rejected).
+//
+// Many trajectories' matches in one call (cmx_ceres2d_match_grid_batch, the Ceres match of
+// LocalTrajectoryBuilder2D::ScanMatch for a fleet): Ceres2DJobKernel, one workgroup per job on a
+// resident grid of either kind, the upload block laid out by ceres_2d_batch_plan.h.
 #include <cfloat>
 #include <climits>
 #include <cmath>
 #include <map>
 #include <vector>
 
+#include "../../include/cartographer_mi355x_debug.h"
+#include "ceres_2d_batch_plan.h"
 #include "ceres_trust_region.h"
 #include "scan_matching_2d.h"
 
@@ -341,6 +347,47 @@ Ceres2DKernel(const Ceres2DProblem* __restrict__ problems) {
   }
 }
 
+// One job of Ceres2DJobKernel on a grid of one kind: Ceres2DKernel's solve and its eight output
+// doubles (a job is never skipped).
+template <bool kTsdf>
+__device__ __forceinline__ void SolveJob(const Ceres2DProblem& P,
+                                         double (*scratch)[Sums<kTsdf>::kCount]) {
+  Pose2DProblem<kTsdf> problem{P, scratch};
+  TrResult<3> r;
+  if (!MinimizeTrustRegion(problem, P.init, P.use_nonmonotonic_steps != 0, P.max_num_iterations,
+                           &r)) {
+    // The initial evaluation failed: FAILURE, as in Ceres2DKernel.
+    if (threadIdx.x == 0) {
+      P.out[0] = P.init[0]; P.out[1] = P.init[1]; P.out[2] = P.init[2];
+      P.out[3] = -1.; P.out[4] = -1.; P.out[5] = -1.; P.out[6] = -1.; P.out[7] = 2.;
+    }
+    return;
+  }
+  if (threadIdx.x == 0) {
+    P.out[0] = r.x[0]; P.out[1] = r.x[1]; P.out[2] = r.x[2];
+    P.out[3] = r.initial_cost; P.out[4] = r.final_cost;
+    P.out[5] = r.successful; P.out[6] = r.unsuccessful; P.out[7] = r.termination;
+  }
+}
+
+// cmx_ceres2d_match_grid_batch: one workgroup per job, probability grids and TSDFs in one launch.
+// A problem with a weight plane is a TSDF's.  The branch is taken by the whole workgroup alike (it
+// depends on blockIdx.x only), so the barriers of BlockSumF64 inside either solve are met by all of
+// its threads; each side is the code of Ceres2DKernel<kTsdf> with the same thread count and the
+// same order of sums, so a job's result is that of its single call.  One LDS block serves both:
+// it is sized for the TSDF's 4 x 14 partial sums, a probability grid uses 4 x 10 of it.
+__global__ void __launch_bounds__(kCeresThreads)
+Ceres2DJobKernel(const Ceres2DProblem* __restrict__ problems) {
+  const Ceres2DProblem& P = problems[blockIdx.x];
+  __shared__ double scratch[4 * Sums<true>::kCount];
+  static_assert(Sums<true>::kCount >= Sums<false>::kCount, "the block is sized for the TSDF sums");
+  if (P.weights != nullptr) {
+    SolveJob<true>(P, reinterpret_cast<double (*)[Sums<true>::kCount]>(scratch));
+  } else {
+    SolveJob<false>(P, reinterpret_cast<double (*)[Sums<false>::kCount]>(scratch));
+  }
+}
+
 // Residuals and Jacobian of TSDFMatchCostFunction2D alone (cmx_ceres2d_tsdf_residuals): S and G
 // first, then per point r = u / S and J = (a - r G) / S as the Jet division forms them.
 __global__ void __launch_bounds__(kCeresThreads)
@@ -396,6 +443,41 @@ void CheckOptions(const cmx_ceres2d_options* o) {
                   o->rotation_weight > 0.,
               "occupied_space / translation / rotation weights must be > 0");
   CMX_REQUIRE(o->max_num_iterations > 0, "max_num_iterations must be > 0");
+}
+
+// What the options and the item decide of a problem; where its grid, its cloud and its result
+// lie is the caller's to add.
+void FillProblem(const cmx_ceres2d_options* options, const RefineItem& it, Ceres2DProblem* problem) {
+  Ceres2DProblem& P = *problem;
+  P.max_weight = it.max_weight;
+  P.nx = it.limits.num_x_cells; P.ny = it.limits.num_y_cells;
+  P.res = it.limits.resolution; P.max_x = it.limits.max_x; P.max_y = it.limits.max_y;
+  P.min_cc = it.limits.min_correspondence_cost; P.max_cc = it.limits.max_correspondence_cost;
+  P.n = it.n;
+  P.init[0] = it.initial.x; P.init[1] = it.initial.y; P.init[2] = it.initial.theta;
+  P.target_x = it.target[0]; P.target_y = it.target[1];
+  P.occupied_scaling = options->occupied_space_weight / std::sqrt(static_cast<double>(it.n));
+  P.translation_weight = options->translation_weight;
+  P.rotation_weight = options->rotation_weight;
+  P.use_nonmonotonic_steps = options->use_nonmonotonic_steps ? 1 : 0;
+  P.max_num_iterations = options->max_num_iterations;
+  P.skip = it.skip;
+}
+
+// The eight doubles every problem leaves, as poses and summaries.
+void UnpackResults(const double* h_out, int num, cmx_pose2d* poses, cmx_ceres_summary* summaries) {
+  for (int p = 0; p < num; ++p) {
+    const double* o = h_out + 8 * static_cast<size_t>(p);
+    poses[p].x = o[0]; poses[p].y = o[1]; poses[p].theta = o[2];
+    if (summaries) {
+      summaries[p].initial_cost = o[3];
+      summaries[p].final_cost = o[4];
+      summaries[p].num_successful_steps = static_cast<int32_t>(o[5]);
+      summaries[p].num_unsuccessful_steps = static_cast<int32_t>(o[6]);
+      summaries[p].termination = static_cast<int32_t>(o[7]);
+      summaries[p].reserved = 0;
+    }
+  }
 }
 
 // One launch, one result copy and one synchronisation for `num` problems, each with the cloud
@@ -472,20 +554,8 @@ void RefineBatch(const cmx_ceres2d_options* options, const RefineItem* items, in
                   2 * static_cast<size_t>(it.limits.num_x_cells) * it.limits.num_y_cells);
       P.weights = reinterpret_cast<const uint16_t*>(d_in + off_weights[p]);
     }
-    P.max_weight = it.max_weight;
-    P.nx = it.limits.num_x_cells; P.ny = it.limits.num_y_cells;
-    P.res = it.limits.resolution; P.max_x = it.limits.max_x; P.max_y = it.limits.max_y;
-    P.min_cc = it.limits.min_correspondence_cost; P.max_cc = it.limits.max_correspondence_cost;
+    FillProblem(options, it, &P);
     P.xyz = it.device_xyz ? it.device_xyz : reinterpret_cast<const float*>(d_in + off_xyz[p]);
-    P.n = it.n;
-    P.init[0] = it.initial.x; P.init[1] = it.initial.y; P.init[2] = it.initial.theta;
-    P.target_x = it.target[0]; P.target_y = it.target[1];
-    P.occupied_scaling = options->occupied_space_weight / std::sqrt(static_cast<double>(it.n));
-    P.translation_weight = options->translation_weight;
-    P.rotation_weight = options->rotation_weight;
-    P.use_nonmonotonic_steps = options->use_nonmonotonic_steps ? 1 : 0;
-    P.max_num_iterations = options->max_num_iterations;
-    P.skip = it.skip;
     P.out = d_out + 8 * static_cast<size_t>(p);
     h_prob[p] = P;
   }
@@ -499,18 +569,7 @@ void RefineBatch(const cmx_ceres2d_options* options, const RefineItem* items, in
   CMX_HIP(hipGetLastError());
   SmallCopyAsync(h_out, d_out, 64 * static_cast<size_t>(num), /*to_device=*/false, ws->stream);
   CMX_HIP(hipStreamSynchronize(ws->stream));
-  for (int p = 0; p < num; ++p) {
-    const double* o = h_out + 8 * static_cast<size_t>(p);
-    poses[p].x = o[0]; poses[p].y = o[1]; poses[p].theta = o[2];
-    if (summaries) {
-      summaries[p].initial_cost = o[3];
-      summaries[p].final_cost = o[4];
-      summaries[p].num_successful_steps = static_cast<int32_t>(o[5]);
-      summaries[p].num_unsuccessful_steps = static_cast<int32_t>(o[6]);
-      summaries[p].termination = static_cast<int32_t>(o[7]);
-      summaries[p].reserved = 0;
-    }
-  }
+  UnpackResults(h_out, num, poses, summaries);
 }
 
 // A host TSDF2D's item: the planes are uploaded with the call.
@@ -905,6 +964,156 @@ cmx_status cmx_ceres2d_tsdf_residuals(const cmx_grid2d_limits* limits, const uin
                                                    truncation_distance, max_weight);
     cmx::TsdfResiduals(item, residual_scaling_factor, pose, point_cloud_xyz, num_points, device,
                        residuals, jacobian, valid);
+  });
+}
+
+}  // extern "C"
+
+// ---- many trajectories' matches on resident grids: cmx_ceres2d_match_grid_batch -------------
+namespace cmx {
+namespace {
+
+void CheckJobShapes(const std::vector<Ceres2DJobShape>& shapes) {
+  CheckCeres2DJobShapes(shapes.data(), static_cast<int>(shapes.size()),
+                        [](int job, const char* what) { CMX_REQUIRE(false, "job %d: %s", job, what); });
+}
+
+// The jobs of a call as items on one device, after every check of the contract; nothing here
+// touches the device.  (A handle's limits and TSDF ranges were checked when it was created.)
+std::vector<RefineItem> JobItems(const cmx_ceres2d_job* jobs, int num,
+                                 std::vector<Ceres2DJobShape>* shapes, int* device) {
+  shapes->resize(num);
+  for (int k = 0; k < num; ++k) {
+    const cmx_ceres2d_job& J = jobs[k];
+    CMX_REQUIRE(J.grid || J.tsdf, "job %d: neither grid nor tsdf is set", k);
+    CMX_REQUIRE(!(J.grid && J.tsdf), "job %d: both grid and tsdf are set", k);
+    CMX_REQUIRE(J.reserved == 0, "job %d: reserved must be 0", k);
+    Ceres2DJobShape& S = (*shapes)[k];
+    S.kind = J.tsdf ? kCeres2DTsdf : kCeres2DProbabilityGrid;
+    S.host_xyz = J.point_cloud_xyz;
+    S.resident = J.cloud != nullptr;
+    S.num_points = J.num_points;
+    if (J.cloud && !J.point_cloud_xyz) {
+      CMX_REQUIRE(J.num_points == 0 || J.num_points == J.cloud->num_points,
+                  "job %d: num_points (%d) is neither 0 nor the count of its cloud (%d)", k,
+                  J.num_points, J.cloud->num_points);
+      S.num_points = J.cloud->num_points;
+    }
+  }
+  CheckJobShapes(*shapes);
+  std::vector<RefineItem> items(num);
+  for (int k = 0; k < num; ++k) {
+    const cmx_ceres2d_job& J = jobs[k];
+    RefineItem& it = items[k];
+    int device_k = 0;
+    if (J.tsdf) {
+      it = ResidentTsdfItem(J.tsdf, &device_k);
+    } else {
+      it.device_cells = Grid2DDeviceCells(J.grid, &it.limits, &device_k);
+    }
+    if (k == 0) *device = device_k;
+    CMX_REQUIRE(device_k == *device, "job %d: its grid is on device %d, the grid of job 0 on %d", k,
+                device_k, *device);
+    if (J.cloud) {
+      CMX_REQUIRE(J.cloud->device == *device,
+                  "job %d: its cloud is on device %d, the grid of job 0 on %d", k, J.cloud->device,
+                  *device);
+      it.device_xyz = J.cloud->xyz;
+    } else {
+      it.host_xyz = J.point_cloud_xyz;
+    }
+    it.n = (*shapes)[k].num_points;
+    it.target[0] = J.target_translation_xy[0];
+    it.target[1] = J.target_translation_xy[1];
+    it.initial = J.initial_pose_estimate;
+  }
+  return items;
+}
+
+// One upload block laid out by the plan (problems | distinct host clouds), one launch of
+// Ceres2DJobKernel, one result copy and one synchronisation.
+void RunJobs(const cmx_ceres2d_options* options, const std::vector<RefineItem>& items,
+             const Ceres2DBatchPlan& plan, int device, cmx_pose2d* poses,
+             cmx_ceres_summary* summaries) {
+  const int num = static_cast<int>(items.size());
+  WorkspaceLease ws(device);
+  char* h_in = ws->pinned[0].ReserveAs<char>(plan.total_bytes);
+  char* d_in = ws->dev[0].ReserveAs<char>(plan.total_bytes);
+  double* d_out = ws->dev[1].ReserveAs<double>(8 * static_cast<size_t>(num));
+  double* h_out = ws->pinned[1].ReserveAs<double>(8 * static_cast<size_t>(num));
+  for (const Ceres2DCloudSlot& cloud : plan.clouds)
+    std::memcpy(h_in + cloud.at, cloud.host_xyz, 12 * static_cast<size_t>(cloud.num_points));
+  Ceres2DProblem* h_prob = reinterpret_cast<Ceres2DProblem*>(h_in);
+  for (int k = 0; k < num; ++k) {
+    const RefineItem& it = items[k];
+    Ceres2DProblem P{};
+    P.cells = it.device_cells;
+    P.weights = it.device_weights;       // null on a probability grid: the kernel's kind
+    FillProblem(options, it, &P);
+    // (a job without points reads no cloud: its pointer is the block's start, as in RefineBatch)
+    P.xyz = it.device_xyz ? it.device_xyz
+                          : reinterpret_cast<const float*>(d_in + (plan.jobs[k].cloud_slot >= 0
+                                                                       ? plan.jobs[k].cloud_at
+                                                                       : plan.problem_bytes));
+    P.out = d_out + 8 * static_cast<size_t>(k);
+    h_prob[k] = P;
+  }
+  SmallCopyAsync(d_in, h_in, plan.total_bytes, /*to_device=*/true, ws->stream);
+  static_assert(kCeres2DBatchLaunches == 1, "the plan counts this launch");
+  Ceres2DJobKernel<<<num, kCeresThreads, 0, ws->stream>>>(
+      reinterpret_cast<const Ceres2DProblem*>(d_in));
+  CMX_HIP(hipGetLastError());
+  SmallCopyAsync(h_out, d_out, 64 * static_cast<size_t>(num), /*to_device=*/false, ws->stream);
+  CMX_HIP(hipStreamSynchronize(ws->stream));
+  UnpackResults(h_out, num, poses, summaries);
+}
+
+}  // namespace
+}  // namespace cmx
+
+extern "C" {
+
+cmx_status cmx_ceres2d_match_grid_batch(const cmx_ceres2d_options* options,
+                                        const cmx_ceres2d_job* jobs, int32_t num_jobs,
+                                        cmx_pose2d* pose_estimates,
+                                        cmx_ceres_summary* summaries) {
+  return Guard([&] {
+    CMX_REQUIRE(options && jobs && pose_estimates, "null argument");
+    CMX_REQUIRE(num_jobs >= 1, "num_jobs must be at least 1");
+    cmx::CheckOptions(options);
+    std::vector<cmx::Ceres2DJobShape> shapes;
+    int device = 0;
+    const std::vector<cmx::RefineItem> items = cmx::JobItems(jobs, num_jobs, &shapes, &device);
+    const cmx::Ceres2DBatchPlan plan =
+        cmx::PlanCeres2DBatch(shapes.data(), num_jobs, sizeof(cmx::Ceres2DProblem));
+    cmx::RunJobs(options, items, plan, device, pose_estimates, summaries);
+  });
+}
+
+cmx_status cmx_debug_ceres2d_batch_plan(const int32_t* kinds, const float* const* point_clouds_xyz,
+                                        const int32_t* num_points, const int32_t* resident,
+                                        int32_t num_jobs, cmx_debug_ceres2d_job_plan* job_plans,
+                                        cmx_debug_ceres2d_call_plan* call_plan) {
+  return Guard([&] {
+    CMX_REQUIRE(kinds && point_clouds_xyz && num_points && job_plans && call_plan, "null argument");
+    CMX_REQUIRE(num_jobs >= 1, "num_jobs must be at least 1");
+    std::vector<cmx::Ceres2DJobShape> shapes(num_jobs);
+    for (int k = 0; k < num_jobs; ++k) {
+      shapes[k].kind = kinds[k];
+      shapes[k].host_xyz = point_clouds_xyz[k];
+      shapes[k].resident = resident && resident[k] != 0;
+      shapes[k].num_points = num_points[k];
+    }
+    cmx::CheckJobShapes(shapes);
+    const cmx::Ceres2DBatchPlan plan =
+        cmx::PlanCeres2DBatch(shapes.data(), num_jobs, sizeof(cmx::Ceres2DProblem));
+    for (int k = 0; k < num_jobs; ++k)
+      job_plans[k] = cmx_debug_ceres2d_job_plan{plan.jobs[k].kind, plan.jobs[k].cloud_slot,
+                                                static_cast<int64_t>(plan.jobs[k].cloud_at)};
+    *call_plan = cmx_debug_ceres2d_call_plan{static_cast<int64_t>(plan.total_bytes),
+                                             static_cast<int64_t>(plan.problem_bytes),
+                                             static_cast<int32_t>(plan.clouds.size()),
+                                             plan.num_launches};
   });
 }
 

@@ -618,6 +618,96 @@ class CeresScanMatcher2D:
         return self._refine_pairs(_lib.lib().cmx_ceres2d_refine_pairs_tsdf, None, grids, found,
                                   pose_estimates, point_clouds)
 
+    def match_batch(self, target_translations, initial_pose_estimates, point_clouds, grids):
+        """cmx_ceres2d_match_grid_batch: `match` for many robots in one call, one upload, one
+        launch and one synchronisation -- the Ceres match of LocalTrajectoryBuilder2D::ScanMatch
+        for a fleet.  Job i matches point_clouds[i] (an array or a PointCloudOnDevice; the same
+        array object listed twice is one cloud, staged once) against grids[i] (a
+        ProbabilityGridOnDevice or a TSDF2DOnDevice, in any mixture; a grid may repeat) from
+        initial_pose_estimates[i] towards target_translations[i].  Returns (poses, summaries),
+        per job what `match` returns for it, bit for bit."""
+        from .grid_2d import ProbabilityGridOnDevice, TSDF2DOnDevice
+        num = len(grids)
+        if not (len(target_translations) == len(initial_pose_estimates) == len(point_clouds)
+                == num):
+            raise ValueError("one target, initial pose, cloud and grid per job")
+        jobs = (_lib.Ceres2DJob * max(num, 1))()
+        converted = {}
+        for i, (target, initial, cloud, grid) in enumerate(
+                zip(target_translations, initial_pose_estimates, point_clouds, grids)):
+            job = jobs[i]
+            if isinstance(grid, TSDF2DOnDevice):
+                job.tsdf = grid._h
+            elif isinstance(grid, ProbabilityGridOnDevice):
+                job.grid = grid._h
+            else:
+                raise TypeError(f"job {i}: the grid is neither a ProbabilityGridOnDevice nor a "
+                                "TSDF2DOnDevice")
+            if isinstance(cloud, PointCloudOnDevice):
+                job.cloud = cloud._h
+            else:
+                if id(cloud) not in converted:
+                    converted[id(cloud)] = _cloud(cloud)[0]
+                xyz = converted[id(cloud)]
+                job.point_cloud_xyz = xyz.ctypes.data if xyz.shape[0] else None
+                job.num_points = xyz.shape[0]
+            target = np.asarray(target, np.float64).reshape(2)
+            job.target_translation_xy[0], job.target_translation_xy[1] = target[0], target[1]
+            job.initial_pose_estimate = initial.to_c()
+        poses = (Pose2d * max(num, 1))()
+        summaries = (CeresSummary * max(num, 1))()
+        check(_lib.lib().cmx_ceres2d_match_grid_batch(C.byref(self.options), jobs, num,
+                                                      C.cast(poses, C.c_void_p),
+                                                      C.cast(summaries, C.c_void_p)))
+        del converted
+        return ([Rigid2d(p.x, p.y, p.theta) for p in poses[:num]],
+                [s_.as_dict() for s_ in summaries[:num]])
+
+
+def ceres2d_batch_plan(kinds, point_clouds_or_counts, resident=None):
+    """cmx_debug_ceres2d_batch_plan: the plan of a CeresScanMatcher2D.match_batch call -- the
+    layout of its one upload block and its number of launches -- without a grid or a device.
+    kinds[i] is 0 (probability grid) or 1 (TSDF).  point_clouds_or_counts[i] is an array (the
+    same object twice is one cloud), a PointCloudOnDevice (resident), an int (a host cloud of its
+    own with that many points; 0: none), or a pair (array, count) that names the array's memory
+    with another count.  `resident` (flags per job) marks int entries as resident clouds.
+    Returns (jobs, call): per job {"kind", "cloud_slot", "cloud_offset"}, for the call
+    {"total_bytes", "problem_bytes", "num_clouds", "num_launches"}."""
+    num = len(kinds)
+    kinds = np.ascontiguousarray(kinds, np.int32)
+    pointers = (C.c_void_p * max(num, 1))()
+    counts = np.zeros(max(num, 1), np.int32)
+    flags = np.zeros(max(num, 1), np.int32)
+    if resident is not None:
+        flags[:num] = np.asarray(resident, np.int32)
+    keep = {}
+    for i, entry in enumerate(point_clouds_or_counts):
+        count = None
+        if isinstance(entry, tuple):
+            entry, count = entry
+        if isinstance(entry, PointCloudOnDevice):
+            flags[i], counts[i] = 1, entry.num_points
+        elif isinstance(entry, (int, np.integer)):
+            counts[i] = entry
+            if entry > 0 and not flags[i]:
+                # an identity of its own: one float per job, never read
+                keep[("own", i)] = np.zeros(1, np.float32)
+                pointers[i] = keep[("own", i)].ctypes.data
+        else:
+            if id(entry) not in keep:
+                keep[id(entry)] = _cloud(entry)[0]
+            xyz = keep[id(entry)]
+            counts[i] = xyz.shape[0] if count is None else count
+            pointers[i] = xyz.ctypes.data if xyz.shape[0] else None
+    job_plans = (_lib.DebugCeres2DJobPlan * max(num, 1))()
+    call_plan = _lib.DebugCeres2DCallPlan()
+    check(_lib.lib().cmx_debug_ceres2d_batch_plan(kinds.ctypes.data, pointers, counts.ctypes.data,
+                                                  flags.ctypes.data, num, job_plans,
+                                                  C.byref(call_plan)))
+    del keep
+    fields = lambda s_: {k: getattr(s_, k) for k, _ in s_._fields_}
+    return [fields(p) for p in job_plans[:num]], fields(call_plan)
+
 
 def tsdf_match_residuals(grid, residual_scaling_factor, pose, point_cloud, device=0):
     """TSDFMatchCostFunction2D::Evaluate (tsdf_match_cost_function_2d.cc:40-66) on a host TSDF2D

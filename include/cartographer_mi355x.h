@@ -23,6 +23,10 @@
  *                                  CeresScanMatcher2D::Match, SM2/ceres_scan_matcher_2d.cc:63-107
  *   cmx_ceres2d_match_tsdf, cmx_ceres2d_match_tsdf_grid, cmx_ceres2d_refine_batch_tsdf
  *                                  the same method on a TSDF2D (.cc:83-90, the GridType::TSDF case)
+ *   cmx_ceres2d_match_grid_batch   the same method for many trajectories in one call, on resident
+ *                                  probability grids and TSDF2Ds alike: the Ceres match of
+ *                                  LocalTrajectoryBuilder2D::ScanMatch
+ *                                  (mapping/internal/2d/local_trajectory_builder_2d.cc:64-107)
  *   cmx_ceres2d_tsdf_residuals     TSDFMatchCostFunction2D::Evaluate,
  *                                  SM2/tsdf_match_cost_function_2d.cc:40-66
  *   cmx_ceres3d_match, cmx_fast3d_refine_batch, cmx_fast3d_refine_pairs
@@ -606,6 +610,52 @@ cmx_status cmx_ceres2d_refine_batch_tsdf(const cmx_ceres2d_options* options,
                                          const float* point_cloud_xyz, int32_t num_points,
                                          cmx_pose2d* pose_estimates_out,
                                          cmx_ceres_summary* summaries);
+
+/* ---- many trajectories' Ceres matches on resident grids ------------------------------------ */
+/* CeresScanMatcher2D::Match for many robots in one call: with
+ * use_online_correlative_scan_matching = false (trajectory_builder_2d.lua's default) the whole
+ * scan match of LocalTrajectoryBuilder2D::ScanMatch (local_trajectory_builder_2d.cc:64-107), else
+ * its second half.  Unlike the refine entries above, every job brings its own target translation
+ * (the pose prediction's) and its own initial estimate.  num_jobs >= 1.
+ *   - pose_estimates[i] and summaries[i] (summaries may be NULL) are bit for bit what the single
+ *     call returns for the same arguments: cmx_ceres2d_match_grid for a job with `grid`,
+ *     cmx_ceres2d_match_tsdf_grid for a job with `tsdf` -- the FAILURE of a TSDF job whose
+ *     interpolated weights are all 0 included (the pose is the initial estimate, costs -1, both
+ *     step counts -1), and max_num_iterations too.  `options` are one set for the whole call, as
+ *     a LocalTrajectoryBuilder2D has one.
+ *   - Probability grids and TSDFs may alternate freely in one list; a grid may appear in several
+ *     jobs (the call only reads its grids).
+ *   - A job's cloud is host memory (point_cloud_xyz, num_points) or a cloud uploaded with
+ *     cmx_cloud_upload (cloud; num_points is then 0 or the cloud's own count); both kinds may be
+ *     mixed.  Equal point_cloud_xyz pointers are one cloud, staged once, and must come with equal
+ *     counts.  A TSDF job may have num_points == 0 with both cloud fields NULL: it ends with
+ *     FAILURE as the single call does.  A probability-grid job needs at least one point.
+ *   - One upload, ONE launch (Ceres2DJobKernel, one workgroup per job whatever its kind), one
+ *     read-back and one synchronisation per call: the launches do not grow with num_jobs.  The
+ *     call runs on the stream of cmx_set_stream when the calling thread has set one.
+ *   - All grids and resident clouds of a call live on one device.
+ *   - Every check is made before the device is touched: null options / jobs / pose_estimates,
+ *     num_jobs < 1, the option checks of the single calls, and per job: neither or both of grid /
+ *     tsdf, neither or both of point_cloud_xyz / cloud, a count outside 1 .. 2^24 (0 .. 2^24 for a
+ *     TSDF job), reserved != 0, one pointer with two counts, a grid or cloud on another device
+ *     than job 0's grid.  Each is CMX_INVALID_ARGUMENT, cmx_last_error names "job <index>", and no
+ *     output is written (nor on any other error).
+ *   - Without a HIP device, valid arguments give CMX_DEVICE_ERROR ("no CPU fallback"). */
+typedef struct cmx_ceres2d_job {
+  const cmx_grid2d* grid;          /* exactly one of grid / tsdf is set            */
+  const cmx_tsdf2d* tsdf;
+  const float* point_cloud_xyz;    /* exactly one of point_cloud_xyz / cloud is set */
+  const cmx_cloud* cloud;          /* uploaded with cmx_cloud_upload                */
+  int32_t num_points;              /* of point_cloud_xyz; with `cloud`: 0 or the cloud's own count */
+  int32_t reserved;                /* 0 */
+  double target_translation_xy[2];
+  cmx_pose2d initial_pose_estimate;
+} cmx_ceres2d_job;
+
+cmx_status cmx_ceres2d_match_grid_batch(const cmx_ceres2d_options* options,
+                                        const cmx_ceres2d_job* jobs, int32_t num_jobs,
+                                        cmx_pose2d* pose_estimates,      /* num_jobs */
+                                        cmx_ceres_summary* summaries);   /* num_jobs, may be NULL */
 
 /* ---- many nodes against 2D submaps: lists of (node, submap) pairs ------------------------- */
 /* The other half of PoseGraph2D::ComputeConstraintsForNode (pose_graph_2d.cc:383-393: when a

@@ -219,6 +219,38 @@ cmx_status cmx_debug_rt3d_batch_plan(const cmx_rt_options* options, int32_t num_
                                      const float* max_point_norms,
                                      cmx_debug_rt3d_match_plan* plans);
 
+/* The plan of one cmx_ceres2d_match_grid_batch call from, per job, the kind of its grid
+ * (CMX_CERES2D_PROBABILITY_GRID or CMX_CERES2D_TSDF), the identity of its host cloud
+ * (`point_clouds_xyz`: compared, never read; NULL for a resident cloud and for a TSDF job without
+ * points), its number of points (a resident cloud's own count) and whether its cloud is resident
+ * (`resident` may be NULL: none is): the staging layout of the call's one upload block -- the
+ * problem array to a 256-byte boundary (`problem_bytes`), then one slot per distinct host cloud
+ * in first-seen order, each to a 256-byte boundary -- with every job's kind, cloud slot and the
+ * slot's byte offset (a resident or empty cloud: slot -1, offset 0), and for the call the bytes of
+ * the block, the number of distinct host clouds and the number of launches, which does not depend
+ * on the list.  The launch path asks the same function; this entry launches nothing and needs no
+ * device.  The errors are those of the call itself that these inputs decide, naming the job: an
+ * unknown kind, a job with a host cloud and a resident one, a job with points and neither, a
+ * count outside 1 .. 2^24 (0 .. 2^24 for a TSDF job), one pointer with two counts. */
+enum { CMX_CERES2D_PROBABILITY_GRID = 0, CMX_CERES2D_TSDF = 1 };
+typedef struct cmx_debug_ceres2d_job_plan {
+  int32_t kind;
+  int32_t cloud_slot;
+  int64_t cloud_offset;
+} cmx_debug_ceres2d_job_plan;
+
+typedef struct cmx_debug_ceres2d_call_plan {
+  int64_t total_bytes;
+  int64_t problem_bytes;
+  int32_t num_clouds;
+  int32_t num_launches;
+} cmx_debug_ceres2d_call_plan;
+
+cmx_status cmx_debug_ceres2d_batch_plan(const int32_t* kinds, const float* const* point_clouds_xyz,
+                                        const int32_t* num_points, const int32_t* resident,
+                                        int32_t num_jobs, cmx_debug_ceres2d_job_plan* job_plans,
+                                        cmx_debug_ceres2d_call_plan* call_plan);
+
 /* The eight integer child sums the fast 3D branch and bound computes for a node (ScoreCandidates
  * at the node's child level, before ToProbability), by the device functions the search itself
  * calls -- a small kernel around them, nothing restated.  `cells_xyz` [num_points][3]: the
